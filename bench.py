@@ -1,10 +1,13 @@
 """Headline benchmark: denoising steps/sec, EzAudio-XL, 10 s latent (500 frames), CFG on.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size xl] [--prompts P]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size xl] [--prompts P] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path: CFG denoiser evaluation (cond + uncond rows) + CFG combine +
 guidance rescale + DDIM update for every prompt of the batch.  Weights are random-init of
 the named architecture, inputs are synthetic T5 embeddings and seeded noise (no network here).
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what takes work of its own: the
+measured-traffic lookup in profiles/, the dominant-kernel probe, the 4-prompts/GPU shard (`config4_shard`) and the CPU baseline.
+`--dump-outputs DIR` writes the final latents of the timed loop to DIR/latents.npy (float32), same bits for the same arguments.
 N > 1: one rank per GPU over RCCL (torch.distributed backend "nccl").  Either launch it under
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (RANK / WORLD_SIZE in the environment) or just
 call `python bench.py --gpus N`: without a launcher environment the script re-executes itself under
@@ -85,7 +88,7 @@ def dominant_kernel_probe(unet, cfg, M, stream, iters=20):
 
 def shard4_measure(unet, params, cfg, dev, n_ddim, use_graph, steps=100, warmup=50):
     """BASELINE.json config #4 (32 prompts over 8 GPUs) seen from ONE GPU: 4 prompts = 8 denoiser rows per launch, same sampler, same
-    kernels, same clock discipline as the headline loop.  Reported as an extra key of the default line; never the headline `value`."""
+    kernels, same clock discipline as the headline loop.  Reported as an extra key of the `--full` line; never the headline `value`."""
     from ezaudio_amd.sampler import LatentSampler
     from ezaudio_amd.scheduler import DDIMScheduler
     P, L, Lc = 4, 10 * params['autoencoder']['latent_sr'], params['text_encoder']['max_length']
@@ -132,6 +135,22 @@ def shard4_measure(unet, params, cfg, dev, n_ddim, use_graph, steps=100, warmup=
             # executed: the single-key shortcut skips 2 L D^2 + 2 L Lc D MACs per block and unconditional row (see the headline line's flops_note)
             'roofline_frac_executed': ach * (1.0 - 2.0 * P * (cfg['depth'] + 1) * (2 * L * cfg['embed_dim'] ** 2 + 2 * L * Lc * cfg['embed_dim']) / fl) / PEAK_BF16_TFLOPS,
             'kernel_launches_per_step': unet.last_launch_count}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each output of the timed path to out_dir/<name>.npy as float32, so that two builds can be compared output for output.
+    Outputs above DUMP_LIMIT_BYTES in all keep a fixed, seeded sample of their leading-axis rows (sorted, same rows on every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    for name, v in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, int(v.shape[0] * DUMP_LIMIT_BYTES // total))
+            v = v[np.sort(np.random.default_rng(0).choice(v.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(v))
 
 
 def relaunch_command(n_gpus, argv, port=None):
@@ -271,13 +290,19 @@ def main():
                                                            '(test mode: latents are gathered through host memory)')
     ap.add_argument('--shared-device', action='store_true',
                     help='test mode for 1-GPU boxes: every rank uses cuda:0 (needs --dist-backend gloo; RCCL refuses duplicate devices)')
-    ap.add_argument('--no-shard4', action='store_true', help="skip the extra 4-prompts/GPU measurement (BASELINE config #4's per-GPU shard) of the default line")
+    ap.add_argument('--no-shard4', action='store_true', help="skip the extra 4-prompts/GPU measurement (BASELINE config #4's per-GPU shard) of the --full line")
     ap.add_argument('--dump-latents', default='', help='rank 0 saves the gathered final latents [prompts x world, C, L] here (torch.save): placement tests')
     ap.add_argument('--as-rank', type=int, default=-1, help='single process: seed the synthetic inputs as rank R of a multi-rank job would (placement tests)')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='rank 0 writes the final latents of the timed loop [prompts x world, C, L] to DIR/latents.npy (float32)')
+    ap.add_argument('--full', action='store_true', help='also the measurements that take work of their own: measured traffic, dominant-kernel '
+                                                        'probe, config-#4 shard, CPU baseline (each still switched off by its --no-* flag)')
     ap.add_argument('--cpu-baseline-worker', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--threads', type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument('--budget', type=float, default=20.0, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
     if a.cpu_baseline_worker:
         cpu_baseline_worker(a.size, a.threads or usable_cpus(), a.budget)
         return
@@ -396,6 +421,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     assert torch.isfinite(lat).all(), 'non-finite latents'
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {'latents': all_lat})
 
     if rank == 0:
         B = 2 * P
@@ -435,7 +462,7 @@ def main():
                                        'so their cross-attention + out-projection is the constant W_o v + b_o added by the attention-out projection; the cross-attention q projection, '
                                        'attention and out-projection of those rows -- 2 L D^2 + 2 L Lc D of the 18 L D^2 + ... MACs per block and unconditional row, 5.4 % of flops_per_step -- are not executed)'},
         }
-        if a.size == 'xl' and P == 1 and not a.controlnet and L == 500:
+        if a.full and a.size == 'xl' and P == 1 and not a.controlnet and L == 500:
             mt = measured_traffic()
             if mt is not None:   # separate rocprofv3 --pmc passes of this same command, on THIS tree's kernels (else: null)
                 res['roofline']['traffic'] = mt[1]['traffic_bytes_per_step']
@@ -443,17 +470,17 @@ def main():
                 res['roofline']['traffic_source'] = f'profiles/{mt[0]} (src_hash {mt[1]["src_hash"]}; FETCH_SIZE x2 + WRITE_SIZE)'
                 res['roofline']['traffic_over_weights'] = mt[1]['traffic_bytes_per_step'] / float(unet._blob.numel())
                 res['roofline']['mfma_busy_frac_pmc'] = mt[1].get('mfma_busy_frac')
-        if not a.no_probe:
+        if a.full and not a.no_probe:
             try:
                 res['roofline']['dominant_kernel'] = dominant_kernel_probe(unet, cfg, B * L, smp.stream)
             except Exception as e:  # the probe must never cost the headline number
                 res['roofline']['dominant_kernel'] = {'error': repr(e)}
-        if world == 1 and P == 1 and a.size == 'xl' and not a.controlnet and not a.no_shard4 and a.as_rank < 0:
+        if a.full and world == 1 and P == 1 and a.size == 'xl' and not a.controlnet and not a.no_shard4 and a.as_rank < 0:
             try:   # after the headline loop: it re-binds the workspace for 8 rows
                 res['config4_shard'] = shard4_measure(unet, params, cfg, dev, n_ddim, use_graph)
             except Exception as e:
                 res['config4_shard'] = {'error': repr(e)}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             res['cpu_baseline'] = cpu_baseline(a.size)
         print(json.dumps(res))
     if dist:

@@ -195,6 +195,22 @@ def _assert_placement_independent(root, env, multi, size_args, tmp_path):
 
 
 @pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run times exactly --steps steps, prints the headline keys without the --full extras, and --dump-outputs writes the
+    latents the timed loop handed back (the same tensor --dump-latents saves) as float32."""
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    res, lat = _bench_dump(root, env, ['--gpus', '1', '--size', 'l', '--steps', '7', '--warmup', '2', '--dump-outputs', str(tmp_path / 'out')],
+                           str(tmp_path / 'lat.pt'))
+    assert res['steps'] == 7 and res['warmup'] == 2 and res['ms_per_step'] > 0 and res['value'] > 0
+    assert {'metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'} <= set(res)
+    assert 'cpu_baseline' not in res and 'config4_shard' not in res and 'dominant_kernel' not in res['roofline']
+    dumped = np.load(tmp_path / 'out' / 'latents.npy')
+    assert dumped.dtype == np.float32 and np.array_equal(dumped, lat.numpy())
+
+
+@pytest.mark.gpu
 def test_bench_spawns_two_rccl_ranks_when_two_gpus_are_present(tmp_path):
     """`python bench.py --gpus 2` -- the form the driver uses -- must start its own ranks (torch.distributed.run on 127.0.0.1),
     shard the prompts, all-gather over RCCL and print ONE JSON line.  Needs >= 2 GPUs (skipped on the 1-GPU test boxes)."""

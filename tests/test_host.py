@@ -407,7 +407,8 @@ def test_pmc_step_summary_folds_the_lds_and_l2_passes(tmp_path):
 def test_bench_line_extras_are_wired():
     """The keys and flags round 3 added to bench.py: the config-#4 shard measurement, the placement-test dump flags and the traffic label."""
     src = open(os.path.join(ROOT, 'bench.py')).read()
-    for needle in ("'config4_shard'", '--no-shard4', '--dump-latents', '--as-rank', 'L2<->fabric bytes per step', 'k_gemm_pp<128,288,4,2,3,EPI_GEGLU,1,64>'):
+    for needle in ("'config4_shard'", '--no-shard4', '--dump-latents', '--as-rank', 'L2<->fabric bytes per step', 'k_gemm_pp<128,288,4,2,3,EPI_GEGLU,1,64>',
+                   '--full', '--dump-outputs'):
         assert needle in src, needle
     import importlib.util
     spec = importlib.util.spec_from_file_location('bench_mod2', os.path.join(ROOT, 'bench.py'))
@@ -417,6 +418,26 @@ def test_bench_line_extras_are_wired():
     # the XL step's algorithmic work the roofline fraction is computed from: 1.541 TFLOP for B = 2, L = 500, Lc = 100
     cfg = bench.model_section('xl')['model']
     assert abs(bench.flops_per_step(cfg, 2, 500, 100) / 1e12 - 1.541) < 1e-3
+
+
+def test_bench_dump_outputs_writes_float32_and_a_fixed_sample_above_the_limit(tmp_path):
+    """bench.py --dump-outputs: every output as <name>.npy in float32; above the size limit the same seeded rows on every call."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_mod3', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.DUMP_LIMIT_BYTES == 64 << 20
+    lat = torch.randn(3, 8, 10, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / 'a'), {'latents': lat})
+    got = np.load(tmp_path / 'a' / 'latents.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, lat.float().numpy())
+    bench.DUMP_LIMIT_BYTES = 2 * 8 * 10 * 4
+    big = torch.arange(5.0).reshape(5, 1, 1).expand(5, 8, 10)
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), {'latents': big})
+    b, c = np.load(tmp_path / 'b' / 'latents.npy'), np.load(tmp_path / 'c' / 'latents.npy')
+    assert b.shape == (2, 8, 10) and b.nbytes <= bench.DUMP_LIMIT_BYTES and np.array_equal(b, c)
+    assert list(b[:, 0, 0]) == sorted(set(b[:, 0, 0]))              # distinct rows, in their original order
 
 
 _ISA_CACHE = {}
