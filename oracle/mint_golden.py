@@ -221,6 +221,69 @@ def mint_sampler(name, size, L, Lc, steps, seed_w, seed_in, guidance_scale, guid
     print('wrote', path, out.shape, float(out.std()))
 
 
+def sampler_prompt_inputs(cfg, L, Lc, steps, prompt):
+    """Per-prompt inputs of mint_sampler_prompts (and of tests/util.py's loader): the text / negative-text embeddings and key masks,
+    the init noise and the step noises, all pure functions of the prompt's `seed_in` and key ranges.  With cond keys = [(0, 12)] and
+    uncond keys = [(0, 1)] they are exactly mint_sampler's inputs for the same seed."""
+    from .weights import make_inputs, uniform_pm1
+    seed = prompt['seed_in']
+    inp = make_inputs(cfg, B=2, L=L, Lc=Lc, seed=seed)
+    masks = np.zeros((2, Lc), dtype=bool)
+    for row, key in ((0, 'cond_keys'), (1, 'uncond_keys')):
+        for a, b in prompt[key]:
+            masks[row, a:b] = True
+    C = cfg['out_chans']
+    s3 = np.float32(np.sqrt(3.0))
+    init = (uniform_pm1('smp.init', C * L, seed) * s3).reshape(1, C, L)
+    noises = [(uniform_pm1(f'smp.z{i}', C * L, seed) * s3).reshape(1, C, L) for i in range(steps)]
+    return inp['ctx'], masks, init, noises
+
+
+# mint_sampler_prompts' four prompts: key ranges [(start, stop), ...] of the cond row and of the uncond row (a negative prompt when
+# `neg_text`, else the empty prompt's one key), chosen for the batch-level edges of ezdit_prepare_context.  p1 is smp_xl's prompt.
+SAMPLER_PROMPTS = [
+    dict(seed_in=41, cond_keys=[(7, 8)], uncond_keys=[(0, 5)], neg_text=True),    # single-key cond (not a prefix), multi-key uncond
+    dict(seed_in=21, cond_keys=[(0, 12)], uncond_keys=[(0, 1)], neg_text=False),  # == smp_xl
+    dict(seed_in=42, cond_keys=[(0, 100)], uncond_keys=[(0, 1)], neg_text=False),  # every key valid
+    dict(seed_in=43, cond_keys=[(0, 37)], uncond_keys=[(0, 1)], neg_text=False),   # ragged key tile
+]
+
+
+def mint_sampler_prompts(name, size, L, Lc, steps, seed_w, prompts, guidance_scale, guidance_rescale, eta, out_dir='tests/golden'):
+    """One unmodified reference inference() run per prompt (the reference samples one prompt at a time), each with its own context,
+    negative context, init noise and step noises, through mint_sampler's fakes; latent[p] is prompt p's result."""
+    import torch
+    from .weights import model_config
+    _, inference = _import_reference()
+    cfg = model_config(size)
+    m, _ = build_reference(cfg, seed_w)
+    params = dict(text_encoder=dict(max_length=Lc), model=cfg, autoencoder=dict(scale=1.0, shift=0.0))
+    lat, cmask, umask = [], [], []
+    for p, pr in enumerate(prompts):
+        ctx, masks, init, noises = sampler_prompt_inputs(cfg, L, Lc, steps, pr)
+        tok = _FakeTok({'prompt': (np.array([[0]]), masks[0:1].astype(np.int64)),
+                        'neg' if pr['neg_text'] else '': (np.array([[1]]), masks[1:2].astype(np.int64))})
+        t5 = _FakeT5({0: ctx[0:1], 1: ctx[1:2]})
+        sched = _OracleScheduler(DIFF, noises)
+        real_randn = torch.randn
+        torch.randn = lambda *a, **k: torch.from_numpy(init.copy())
+        try:
+            torch.set_num_threads(os.cpu_count())
+            out = inference(lambda embedding: embedding, m, None, None, tok, t5, params, sched,
+                            ['prompt'], ['neg'] if pr['neg_text'] else None, L, guidance_scale, guidance_rescale, steps, eta, 2024, 'cpu')
+        finally:
+            torch.randn = real_randn
+        lat.append(out.numpy().astype(np.float32)[0])
+        cmask.append(masks[0])
+        umask.append(masks[1])
+        print('minted', name, 'prompt', p, out.shape, float(out.std()), flush=True)
+    meta = dict(size=size, L=L, Lc=Lc, steps=steps, seed_w=seed_w, prompts=[dict(pr) for pr in prompts],
+                guidance_scale=guidance_scale, guidance_rescale=guidance_rescale, eta=eta)
+    path = os.path.join(out_dir, f'sampler_{name}.npz')
+    np.savez(path, meta=np.array(repr(meta)), latent=np.stack(lat), cond_mask=np.stack(cmask), uncond_mask=np.stack(umask))
+    print('wrote', path)
+
+
 def mint_cn_sampler(name, size, L, Lc, steps, seed_w, seed_in, guidance_scale, guidance_rescale, eta, scale, out_dir='tests/golden'):
     """Run the reference's UNMODIFIED ControlNet sampler, src/inference_controlnet.py:27-129 `inference`, on the reference's own MaskDiT +
     DiTControlNet (synthetic checkpoints), with the duck-typed tokenizer / T5 / scheduler fakes of mint_sampler."""
@@ -396,8 +459,11 @@ JOBS = {
     # BASELINE.json configs #2 / #3: the shipped L and XL models through the reference's unmodified 50-step inference() loop
     'smp_l':     (mint_sampler, dict(size='l', L=500, Lc=100, steps=50, seed_w=1234, seed_in=21, guidance_scale=5.0, guidance_rescale=0.75, eta=1.0)),
     'smp_xl':    (mint_sampler, dict(size='xl', L=500, Lc=100, steps=50, seed_w=1234, seed_in=21, guidance_scale=5.0, guidance_rescale=0.75, eta=1.0)),
+    # config #4's per-GPU loop: four independent reference runs, batched as 4 prompts = 8 denoiser rows (M = 4000) on the GPU
+    'smp_xl_p4': (mint_sampler_prompts, dict(size='xl', L=500, Lc=100, steps=50, seed_w=1234, prompts=SAMPLER_PROMPTS,
+                                             guidance_scale=5.0, guidance_rescale=0.75, eta=1.0)),
     # config #4's per-GPU shape: 4 prompts = 8 denoiser rows (M = 4000 token rows) at XL width
-    'xl_b8':     (mint_forward, dict(size='xl', L=500, Lc=100, timesteps=[499], seed_w=1234, seed_in=14, n_valid=(12, 1, 30, 1, 5, 1, 100, 1), B=8)),
+    'xl_b8':    (mint_forward, dict(size='xl', L=500, Lc=100, timesteps=[499], seed_w=1234, seed_in=14, n_valid=(12, 1, 30, 1, 5, 1, 100, 1), B=8)),
     # config #5: XL width + the energy_l.yml controlnet section, 10 s latent; residual rows sampled every 25 tokens
     'cn_xl':     (mint_controlnet, dict(size='xl', L=500, Lc=100, t=[979, 499], seed_w=1234, seed_in=33, scale=1.0, row_stride=25)),
     # the ONE ControlNet configuration the reference ships: EzAudio-L + ckpts/controlnet/energy_l.yml, 10 s latent

@@ -14,7 +14,7 @@ import torch
 from oracle.dit import DiTOracle
 from oracle.sampler import sample as oracle_sample
 from oracle.weights import make_inputs, make_state_dict, model_config, uniform_pm1
-from tests.util import DIFF, golden_case, record, rel_l2, sampler_case
+from tests.util import DIFF, golden_case, record, rel_l2, sampler_case, sampler_prompts_case
 
 pytestmark = pytest.mark.gpu
 
@@ -553,14 +553,36 @@ def test_forward_per_row_timesteps_and_determinism(lib, dev):
     assert torch.equal(m(x, torch.tensor(499), ctx, context_mask=msk)[0], a)  # bitwise repeatable
 
 
-@pytest.mark.parametrize('name', ['xl', 'xl_b8'])
+def _repro_case(name):
+    """(size, seed_w, inputs, t, forward kwargs) of a bit-reproducibility case, without building a state dict (get_model builds its own)."""
+    from tests.util import load_golden
+    if name in ('xl_b4', 'xl_b6'):
+        # two and three prompts in the CFG layout [cond.. | uncond..] (M = 2000 / 3000); B = 6 with a single-key cond first: the shortcut's range starts at element 1
+        n_valid = {'xl_b4': (12, 30, 1, 1), 'xl_b6': (1, 30, 5, 9, 1, 1)}[name]
+        return 'xl', 1234, make_inputs(model_config('xl'), B=len(n_valid), L=500, Lc=100, n_valid=n_valid, seed=15), 499, {}
+    g, meta = load_golden('dit_' + name.replace('_cn', ''))
+    cfg = model_config(meta['size'])
+    inp = make_inputs(cfg, B=meta.get('B', 2), L=meta['L'], Lc=meta['Lc'], n_valid=tuple(meta['n_valid']), seed=meta['seed_in'], with_gt=meta['with_gt'])
+    kw = {}
+    if name.endswith('_cn'):   # ControlNet residuals on every in-block, built as golden_case builds them for xs_cn: the row-kernel skip path at full width
+        D, L = cfg['embed_dim'], meta['L']
+        kw['controlnet_skips'] = [(0.1 * uniform_pm1(f'in.cn{i}', 2 * L * D, meta['seed_in'])).reshape(2, L, D) for i in range(cfg['depth'] // 2)]
+    return meta['size'], meta['seed_w'], inp, meta['timesteps'][0], kw
+
+
+@pytest.mark.parametrize('name', ['xl', 'xl_b8', 'l', 'xl_b4', 'xl_b6', 'xl_cn'])
 def test_forward_is_bit_reproducible_at_full_width(lib, dev, name):
     """Twenty forwards of the XL shape (one prompt: k_gemm_ks producers; four prompts: the ping-pong producer) on the same inputs give the same bits.  A kernel that reads a
     register an inline-asm load has not filled yet, or a K tile a counted wait did not cover, shows up as a different result once in ten runs, only at full width and
-    under register pressure (round 6: the COPY2 form's gain vector; tools/diag_determinism.py finds the launch)."""
-    cfg, sd, inp, kw, g, meta = golden_case(name)
-    m = get_model(meta['size'], meta['seed_w'])
-    t = meta['timesteps'][0]
+    under register pressure (round 6: the COPY2 form's gain vector; tools/diag_determinism.py finds the launch).  Also: the L width, two and three prompts at XL
+    width (M = 2000: k_gemm_ks with write-through stores and without the affine / panel row variants; M = 3000: the ping-pong producer with a ragged last row tile),
+    and XL with ControlNet residuals (the skip path through the row kernel)."""
+    if name in ('xl', 'xl_b8'):
+        cfg, sd, inp, kw, g, meta = golden_case(name)
+        size, seed_w, t = meta['size'], meta['seed_w'], meta['timesteps'][0]
+    else:
+        size, seed_w, inp, t, kw = _repro_case(name)
+    m = get_model(size, seed_w)
     first = _forward(m, inp, t, kw).cpu().numpy()
     for i in range(19):
         again = _forward(m, inp, t, kw).cpu().numpy()
@@ -581,22 +603,34 @@ def test_forward_input_validation(lib, dev):
 # sampler level
 # ---------------------------------------------------------------------------------------------------
 def _run_sampler(m, inp, init, noises, meta, use_graph=True, P=1):
+    """Prompt 0 of a sampler_case fixture, P times."""
+    prompt = dict(ctx=inp['ctx'], mask=inp['ctx_mask'], init=init, noises=noises)
+    gt = gm = None
+    if meta['with_gt']:
+        gt, gm = inp['gt'][0:1].repeat(P, 0), inp['gt_mask'][0:1].repeat(P, 0)
+    return _run_prompts(m, [prompt] * P, meta, use_graph=use_graph, gt=gt, gt_mask=gm)
+
+
+def _run_prompts(m, prompts, meta, use_graph=True, gt=None, gt_mask=None):
+    """One sampler call over len(prompts) prompts, each with its own text / negative text (ctx [2, Lc, Dc]), key masks (mask [2, Lc]), init noise [1, C, L]
+    and step noises (steps x [1, C, L]): the CFG batch is [cond of every prompt | uncond of every prompt]."""
     from ezaudio_amd.sampler import LatentSampler
     from ezaudio_amd.scheduler import DDIMScheduler
     smp = LatentSampler(m, DDIMScheduler(**DIFF))
     steps = meta['steps']
-    text, tm = t_(inp['ctx'][0:1]).repeat(P, 1, 1), t_(inp['ctx_mask'][0:1]).repeat(P, 1)
-    un, um = t_(inp['ctx'][1:2]).repeat(P, 1, 1), t_(inp['ctx_mask'][1:2]).repeat(P, 1)
-    gt = t_(inp['gt'][0:1]).repeat(P, 1, 1) if meta['with_gt'] else None
-    gm = t_(inp['gt_mask'][0:1]).repeat(P, 1, 1) if meta['with_gt'] else None
-    sn = torch.stack([t_(z) for z in noises], 0).repeat(1, P, 1, 1) if meta['eta'] > 0 else None
-    smp.prepare(text, tm, un, um, t_(init).repeat(P, 1, 1), sn, meta['guidance_scale'], meta['guidance_rescale'], steps,
+    text, tm = t_(np.stack([p['ctx'][0] for p in prompts])), t_(np.stack([p['mask'][0] for p in prompts]))
+    un, um = t_(np.stack([p['ctx'][1] for p in prompts])), t_(np.stack([p['mask'][1] for p in prompts]))
+    init = t_(np.concatenate([p['init'] for p in prompts], 0))
+    sn = torch.stack([t_(np.concatenate([p['noises'][i] for p in prompts], 0)) for i in range(steps)], 0) if meta['eta'] > 0 else None
+    gt = None if gt is None else t_(gt)
+    gm = None if gt_mask is None else t_(gt_mask)
+    smp.prepare(text, tm, un, um, init, sn, meta['guidance_scale'], meta['guidance_rescale'], steps,
                 meta['eta'], gt=gt, gt_mask=gm)
     smp.run(use_graph=use_graph)
     lat = smp.finish()
     torch.cuda.synchronize()
     lat = lat.clone()
-    if meta['with_gt']:
+    if gt is not None:
         lat = torch.where(gm, lat, gt)  # src/inference.py:104-105
     return lat
 
@@ -624,6 +658,83 @@ def test_sampler_graph_equals_eager_and_batch_equals_single(lib, dev):
     c = _run_sampler(m, inp, init, noises, meta, use_graph=True, P=3)
     for i in range(3):
         assert torch.equal(c[i:i + 1], a)   # samples never interact -> sharding-invariant, bitwise
+
+
+_P4 = {}
+
+
+def _p4_case():
+    if not _P4:
+        _P4['case'] = sampler_prompts_case('smp_xl_p4')
+    return _P4['case']
+
+
+@pytest.mark.parametrize('order', [(0,), (0, 1), (0, 1, 2), (0, 1, 2, 3), (1, 2, 3, 0), (3,)])
+def test_batched_sampler_matches_reference_loop_golden(lib, dev, order):
+    """BASELINE config #4's per-GPU loop: several prompts per sampler call, each with its own context, negative context and noises, against four independent
+    runs of the reference's unmodified inference() (sampler_smp_xl_p4).  The batch of 2P CFG rows is [cond.. | uncond..], so the order of the prompts decides
+    which kernels run: (0,) M = 1000 with a negative prompt and a single-key cond row; (0, 1) M = 2000 (k_gemm_ks with write-through stores, no affine / panel
+    row variants); (0, 1, 2) M = 3000 (> 2048 rows: the ping-pong producers, the co-resident QKV GEMM, a ragged last row tile); (0, 1, 2, 3) M = 4000 with
+    the single-key shortcut on over the multi-key elements [1, 5) -- cross-attention rows start at 1 x L, no multiple of a tile height; (1, 2, 3, 0) M = 4000
+    with multi-key elements {0, 1, 2, 7}, not contiguous: the general path; (3,) the ragged-key prompt alone at M = 1000, the one-prompt yardstick of its
+    batched rows.  Gate: smp_xl's 2e-2 per prompt.  At M = 4000 the run is repeated with xkey1 = 0 (every row through cross-attention): bitwise the same
+    where the general path ran anyway, a different computation inside the same gate where the shortcut ran."""
+    cfg, prompts, g, meta = _p4_case()
+    m = get_model(meta['size'], meta['seed_w'])
+    sel = [prompts[p] for p in order]
+
+    def run_and_check(tag):
+        lat = _run_prompts(m, sel, meta).cpu().numpy()
+        assert np.isfinite(lat).all()
+        rs = []
+        for i, p in enumerate(order):
+            r = rel_l2(lat[i], g['latent'][p])
+            record(f'smp_xl_p4 order={list(order)}{tag} prompt {p} (row {i}): final-latent rel-L2 {r:.3e}')
+            rs.append(r)
+        assert max(rs) < 2e-2, (order, tag, rs)
+        return lat
+
+    lat = run_and_check('')
+    if len(order) == 4:
+        try:
+            assert lib.ezdit_set_option(m._h, b'xkey1', 0) == 0   # before prepare: ezdit_prepare_context decides the layout
+            base = run_and_check(' xkey1=0')
+        finally:
+            assert lib.ezdit_set_option(m._h, b'xkey1', 1) == 0
+        multi = [e for e, msk in enumerate([p['mask'][0] for p in sel] + [p['mask'][1] for p in sel]) if msk.sum() > 1]
+        shortcut = {(0, 1, 2, 3): True, (1, 2, 3, 0): False}[order]
+        assert (multi == list(range(multi[0], multi[-1] + 1))) == shortcut, multi   # the layout this order is meant to produce
+        if shortcut:
+            assert not np.array_equal(lat, base)     # the shortcut ran
+            record(f'smp_xl_p4 order={list(order)}: shortcut vs general path rel-L2 {rel_l2(lat, base):.3e}')
+        else:
+            np.testing.assert_array_equal(lat, base)
+
+
+def test_four_prompt_sampler_graph_equals_eager_and_every_prompt_equals_the_one_prompt_golden(lib, dev):
+    """smp_xl's prompt four times in one sampler call (M = 4000: the large-M kernel forms; the single-key shortcut on, cross-attention over the cond elements [0, 4) only): every latent
+    inside smp_xl's gate of its golden, all four bitwise equal (samples never interact), and the captured-graph replay bitwise the eager loop."""
+    from tests.util import load_golden
+    cfg, prompts, g4, meta = _p4_case()
+    g, meta1 = load_golden('sampler_smp_xl')
+    assert _is_smp_xl_prompt(meta, meta1)
+    m = get_model(meta['size'], meta['seed_w'])
+    a = _run_prompts(m, [prompts[1]] * 4, meta, use_graph=True)
+    b = _run_prompts(m, [prompts[1]] * 4, meta, use_graph=False)
+    assert torch.isfinite(a).all()
+    assert torch.equal(a, b)
+    for i in range(4):
+        r = rel_l2(a[i].cpu().numpy(), g['latent'][0])
+        record(f'smp_xl x4 row {i}: final-latent rel-L2 {r:.3e}')
+        assert r < 2e-2
+        assert torch.equal(a[i], a[0])
+
+
+def _is_smp_xl_prompt(meta4, meta1):
+    """Prompt 1 of sampler_smp_xl_p4 is smp_xl's prompt (tests/test_oracle.py checks the latents agree bit for bit)."""
+    pr = meta4['prompts'][1]
+    return (pr['seed_in'] == meta1['seed_in'] and pr['cond_keys'] == [(0, 12)] and pr['uncond_keys'] == [(0, 1)] and not pr['neg_text']
+            and all(meta4[k] == meta1[k] for k in ('size', 'L', 'Lc', 'steps', 'seed_w', 'guidance_scale', 'guidance_rescale', 'eta')))
 
 
 def test_context_with_another_single_key_pattern_drops_the_captured_step(lib, dev):

@@ -703,72 +703,172 @@ def test_blind_statistics_loads_of_the_layernorm_algebra_consumers_are_not_touch
     assert checked >= 4, checked
 
 
+# Wait states an XDL MFMA's destination needs before a VALU / VMEM / LDS / FLAT instruction reads or overwrites it (RAW + WAW), by the MFMA's pass count:
+# AMD "Instinct MI300" (CDNA3) ISA reference guide, section 7.6 "Dependency Resolution: Required Independent Instructions", row "XDL write VGPR -> VALU read /
+# VM, L/GDS, FLAT and export read (RAW + WAW)": 2 / 4 / 8 / 16 passes -> 5 / 7 / 11 / 19; gfx950 needs one more (LLVM GCNHazardRecognizer.cpp,
+# GFX940_XDL_N_PassWriteVgprVALUWawWaitStates = NumPasses + 3 + IsGFX950).  Pass counts from the CDNA4 ISA guide's MFMA table: the gfx950
+# double-K bf16 forms keep the pass counts of the CDNA3 shapes they extend (16x16x16 -> 16x16x32: 8, 32x32x8 -> 32x32x16: 16).
+MFMA_PASSES = {'v_mfma_f32_16x16x32_bf16': 8, 'v_mfma_f32_32x32x16_bf16': 16}
+
+
+def _mfma_read_wait_states(op):
+    return MFMA_PASSES[op] + 3 + 1
+
+
+def _mfma_result_touches(f, reg):
+    """[(kernel instruction, issue slots since the MFMA that wrote the register it names, wait states that MFMA's shape needs)] for the FIRST non-MFMA instruction
+    that names a register some MFMA wrote (reg 'a': AGPR accumulators, 'v': VGPR accumulators), per register and along every path: a label takes, per register,
+    the minimum distance over its fall-through and every branch to it, iterated to a fixed point (loop back-edges come textually after their header).  Per register,
+    not per chain: k_attn's VGPRs are reused for other values between its MFMA chains, so only the MFMA that wrote THAT register starts its clock; another MFMA
+    writing it (the next link of a chain taking it as C) restarts it.  v_accvgpr_write (hipcc parking a spilled VGPR in an AGPR) writes without a matrix-pipe hazard.
+    Distances saturate at CAP (beyond every table entry), which keeps the fixed point a few passes away."""
+    import re
+    CAP = 64
+    lines = [l.strip() for l in f.splitlines() if (l.startswith('\t') or re.match(r'\.LBB\d+_\d+:', l)) and not l.strip().startswith((';', '.p2align', '.long', '.byte'))]
+
+    def named(ops):
+        regs = {int(x) for x in re.findall(r'\b%s(\d+)\b' % reg, ops)}
+        for x, y in re.findall(r'\b%s\[(\d+):(\d+)\]' % reg, ops):
+            regs |= set(range(int(x), int(y) + 1))
+        return regs
+
+    def merge(dst, src):
+        for r, (d, need) in src.items():
+            d0, n0 = dst.get(r, (d, need))
+            dst[r] = (min(d0, d), max(n0, need))
+
+    label_in = {}
+    for _ in range(40):
+        live, new_in, touches = {}, {}, []     # live: register -> (slots since the MFMA that wrote it, wait states it needs)
+        for ins in lines:
+            m = re.match(r'(\.LBB\d+_\d+):', ins)
+            if m:
+                live = dict(live)
+                merge(live, label_in.get(m.group(1), {}))
+                continue
+            op = ins.split()[0]
+            opnds = ins.split(None, 1)[1] if ' ' in ins else ''
+            if op.startswith('v_mfma'):
+                live = {r: (min(d + 1, CAP), need) for r, (d, need) in live.items()}
+                mm = re.match(r'%s\[(\d+):(\d+)\]' % reg, opnds)
+                if mm:
+                    for r in range(int(mm.group(1)), int(mm.group(2)) + 1):
+                        live[r] = (0, _mfma_read_wait_states(op))
+                continue
+            if op == 's_branch' or op.startswith('s_cbranch'):
+                live = {r: (min(d + 1, CAP), need) for r, (d, need) in live.items()}
+                merge(new_in.setdefault(ins.split()[-1], {}), live)
+                if op == 's_branch':
+                    live = {}
+                continue
+            if op == 's_endpgm':
+                live = {}
+                continue
+            hit = set()
+            if op.startswith(('v_', 'ds_', 'global_', 'buffer_')) and not op.startswith('v_accvgpr_write'):
+                hit = named(opnds) & set(live)
+            if hit:
+                touches.append((ins, min(live[r][0] for r in hit), max(live[r][1] for r in hit)))
+                for r in hit:
+                    del live[r]
+            m2 = re.match(r's_nop (\d+)', ins)
+            k = int(m2.group(1)) + 1 if m2 else 1
+            live = {r: (min(d + k, CAP), need) for r, (d, need) in live.items()}
+        if new_in == label_in:
+            return touches
+        label_in = new_in
+    raise AssertionError('no fixed point')
+
+
 def test_inline_asm_mfma_results_are_read_behind_their_wait_states():
-    """k_gemm_pp, k_gemm_ks and k_attn issue their MFMAs from inline asm, so hipcc's hazard recogniser neither sees them nor pads behind them
-    (round-3 ADVICE): the wait states between the LAST MFMA of an accumulation chain and the first non-MFMA read of its accumulator are
-    hand-placed `s_nop`s.  This test disassembles the gfx950 code hipcc generates for those sources and checks, per kernel, that every
-    instruction which reads an accumulator register (AGPR operand of a v_accvgpr_read / ds_write / global_store / VALU instruction, or the
-    VGPR accumulators of k_attn) sits at least 18 issue slots (s_nop N counts N + 1) behind the textually preceding MFMA -- a refactor or a
-    compiler upgrade that moves a reader up fails here instead of corrupting tiles silently."""
+    """k_gemm_pp, k_gemm_ks, k_gemm_co and k_attn issue their MFMAs from inline asm, so hipcc's hazard recogniser neither sees them nor pads behind them
+    (round-3 ADVICE): the wait states between an MFMA and the first non-MFMA instruction that touches its result are hand-placed `s_nop`s.  This test
+    compiles those sources for gfx950 and checks the generated code, per instantiation:
+    (1) k_gemm_pp / k_gemm_ks (AGPR accumulators): every instruction which reads an accumulator (AGPR operand of a v_accvgpr_read / ds_write / global_store /
+    VALU instruction) sits at least 18 issue slots (s_nop N counts N + 1) behind the textually preceding MFMA of any chain (the rule since round 3);
+    (2) all four kernels, per register (`_mfma_result_touches`: AGPR accumulators of the GEMMs, the VGPR accumulators `v[a:b]` of k_attn's score and
+    output MFMAs): the first VALU / LDS / VMEM instruction that names an MFMA's destination sits at least the ISA table's wait states for that MFMA's
+    shape behind it (MFMA_PASSES: 12 for 16x16x32, 20 for 32x32x16).
+    Each kernel -- and each instantiation of k_gemm_co and k_attn -- must contribute checked reads, so a kernel that drops out of the scan fails here too.
+    A refactor or a compiler upgrade that moves a reader up fails here instead of corrupting tiles silently."""
     import re
     INF = 10 ** 9
-    for src, kernels in (('gemm.hip', ('k_gemm_pp', 'k_gemm_ks')),):
-        funcs = _gfx950_isa(src)
-        checked = 0
-        for name, f in funcs.items():
-            if not any(k in name for k in kernels) or 'v_mfma' not in f:
-                continue
-            lines = [l.strip() for l in f.splitlines() if (l.startswith('\t') or re.match(r'\.LBB\d+_\d+:', l)) and not l.strip().startswith((';', '.p2align', '.long', '.byte'))]
-            # the accumulators = the AGPRs some MFMA of this kernel writes; hipcc also parks spilled VGPRs in the AGPRs above them (v_accvgpr_write / _read around the loops:
-            # no matrix-pipe hazard on those)
-            acc_regs = set()
-            for ins in lines:
-                mm = re.match(r'v_mfma\S* a\[(\d+):(\d+)\]', ins)
-                if mm:
-                    acc_regs |= set(range(int(mm.group(1)), int(mm.group(2)) + 1))
+    funcs = _gfx950_isa('gemm.hip')
+    checked = {'k_gemm_pp': 0, 'k_gemm_ks': 0}
+    for name, f in funcs.items():
+        kern = next((k for k in checked if re.search(r'\d%sI' % k, name)), None)
+        if kern is None or 'v_mfma' not in f:
+            continue
+        lines = [l.strip() for l in f.splitlines() if (l.startswith('\t') or re.match(r'\.LBB\d+_\d+:', l)) and not l.strip().startswith((';', '.p2align', '.long', '.byte'))]
+        # the accumulators = the AGPRs some MFMA of this kernel writes; hipcc also parks spilled VGPRs in the AGPRs above them (v_accvgpr_write / _read around the loops:
+        # no matrix-pipe hazard on those)
+        acc_regs = set()
+        for ins in lines:
+            mm = re.match(r'v_mfma\S* a\[(\d+):(\d+)\]', ins)
+            if mm:
+                acc_regs |= set(range(int(mm.group(1)), int(mm.group(2)) + 1))
 
-            def names_acc(ops):
-                named = {int(x) for x in re.findall(r'\ba(\d+)\b', ops)}
-                for x, y in re.findall(r'\ba\[(\d+):(\d+)\]', ops):
-                    named |= set(range(int(x), int(y) + 1))
-                return bool(named & acc_regs)
-            # dist = issue slots since the last MFMA on ANY path into this point: a label takes the minimum over its fall-through and every branch that
-            # targets it (round 5: the register allocator put accumulator copies on a loop-exit EDGE, which a purely textual scan -- whose predecessor
-            # was an unrelated block -- did not see); iterated to a fixed point because loop back-edges come textually after their header
-            label_in = {}
-            for _ in range(6):
-                dist, new_in, reads = INF, {}, []
-                for ins in lines:
-                    m = re.match(r'(\.LBB\d+_\d+):', ins)
-                    if m:
-                        dist = min(dist, label_in.get(m.group(1), INF))
-                        continue
-                    op = ins.split()[0]
-                    if op.startswith('v_mfma'):
-                        m2 = re.match(r's_nop (\d+)', '')
-                        dist = 0
-                        continue
-                    if op in ('s_branch',) or op.startswith('s_cbranch'):
-                        tgt = ins.split()[-1]
-                        new_in[tgt] = min(new_in.get(tgt, INF), dist + 1)
-                        dist = INF if op == 's_branch' else dist + 1
-                        continue
-                    opnds = ins.split(None, 1)[1] if ' ' in ins else ''
-                    if op in ('v_accvgpr_read_b32', 'v_accvgpr_mov_b32'):
-                        reads_acc = names_acc(opnds.split(',', 1)[1] if ',' in opnds else opnds)   # (the source operand)
-                    else:
-                        reads_acc = op.startswith(('ds_write', 'global_store', 'v_')) and not op.startswith('v_accvgpr_write') and names_acc(opnds)
-                    if reads_acc and dist < INF:
-                        reads.append((ins, dist))
-                        dist = INF          # chain consumed; the next MFMA re-arms the check
-                        continue
-                    m2 = re.match(r's_nop (\d+)', ins)
-                    if dist < INF:
-                        dist += int(m2.group(1)) + 1 if m2 else 1
-                if new_in == label_in:
-                    break
-                label_in = new_in
-            for ins, d in reads:
-                assert d >= 18, (name, ins, d)
-            checked += len(reads)
-        assert checked >= 10, checked
+        def names_acc(ops):
+            named = {int(x) for x in re.findall(r'\ba(\d+)\b', ops)}
+            for x, y in re.findall(r'\ba\[(\d+):(\d+)\]', ops):
+                named |= set(range(int(x), int(y) + 1))
+            return bool(named & acc_regs)
+        # dist = issue slots since the last MFMA on ANY path into this point: a label takes the minimum over its fall-through and every branch that
+        # targets it (round 5: the register allocator put accumulator copies on a loop-exit EDGE, which a purely textual scan -- whose predecessor
+        # was an unrelated block -- did not see); iterated to a fixed point because loop back-edges come textually after their header
+        label_in = {}
+        for _ in range(6):
+            dist, new_in, reads = INF, {}, []
+            for ins in lines:
+                m = re.match(r'(\.LBB\d+_\d+):', ins)
+                if m:
+                    dist = min(dist, label_in.get(m.group(1), INF))
+                    continue
+                op = ins.split()[0]
+                if op.startswith('v_mfma'):
+                    m2 = re.match(r's_nop (\d+)', '')
+                    dist = 0
+                    continue
+                if op in ('s_branch',) or op.startswith('s_cbranch'):
+                    tgt = ins.split()[-1]
+                    new_in[tgt] = min(new_in.get(tgt, INF), dist + 1)
+                    dist = INF if op == 's_branch' else dist + 1
+                    continue
+                opnds = ins.split(None, 1)[1] if ' ' in ins else ''
+                if op in ('v_accvgpr_read_b32', 'v_accvgpr_mov_b32'):
+                    reads_acc = names_acc(opnds.split(',', 1)[1] if ',' in opnds else opnds)   # (the source operand)
+                else:
+                    reads_acc = op.startswith(('ds_write', 'global_store', 'v_')) and not op.startswith('v_accvgpr_write') and names_acc(opnds)
+                if reads_acc and dist < INF:
+                    reads.append((ins, dist))
+                    dist = INF          # chain consumed; the next MFMA re-arms the check
+                    continue
+                m2 = re.match(r's_nop (\d+)', ins)
+                if dist < INF:
+                    dist += int(m2.group(1)) + 1 if m2 else 1
+            if new_in == label_in:
+                break
+            label_in = new_in
+        for ins, d in reads:
+            assert d >= 18, (name, ins, d)
+        checked[kern] += len(reads)
+    assert min(checked.values()) >= 10, checked
+
+    touches = {}   # kernel -> {instantiation: number of checked first touches}
+    for src, kern, reg in (('gemm.hip', 'k_gemm_pp', 'a'), ('gemm.hip', 'k_gemm_ks', 'a'), ('gemm.hip', 'k_gemm_co', 'a'), ('attn.hip', 'k_attn', 'v')):
+        touches[kern] = {}
+        for name, f in _gfx950_isa(src).items():
+            if not re.search(r'\d%sI' % kern, name) or 'v_mfma' not in f:
+                continue
+            shapes = set(re.findall(r'^\s*(v_mfma\S*)', f, re.M))
+            assert shapes <= set(MFMA_PASSES), (name, shapes - set(MFMA_PASSES))   # a new shape needs its row of the table first
+            found = _mfma_result_touches(f, reg)
+            for ins, d, need in found:
+                assert d >= need, (name, ins, d, need)
+            touches[kern][name] = len(found)
+    print({k: sum(v.values()) for k, v in touches.items()})
+    assert len(touches['k_gemm_co']) >= 8 and len(touches['k_attn']) >= 8, {k: len(v) for k, v in touches.items()}
+    for kern in ('k_gemm_co', 'k_attn'):
+        assert min(touches[kern].values()) > 0, (kern, touches[kern])
+    for kern, per in touches.items():
+        assert sum(per.values()) >= 10, (kern, per)

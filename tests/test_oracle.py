@@ -169,3 +169,40 @@ def test_skip_connection_layernorm_is_the_algebra_the_skip_path_runs():
     Gp, Cp = g @ W.T, c @ W.T + b
     got = r[:, None] * (A @ W.T - mu[:, None] * Gp) + Cp
     np.testing.assert_allclose(got, want, rtol=0, atol=1e-10)
+
+
+def test_four_prompt_sampler_fixture_is_the_one_prompt_job_per_prompt():
+    """sampler_smp_xl_p4 (mint_sampler_prompts) holds four independent runs of the reference's inference(), one per prompt.  Its prompt 1 is smp_xl's prompt
+    (seed 21, 12 cond keys, the empty uncond prompt): its latent must be smp_xl's latent bit for bit -- both were minted by the same unmodified reference loop
+    on the same inputs, and a re-mint of the new job on the same machine reproduced the committed smp_xl file exactly.  The mask patterns are the batch-level
+    edges of ezdit_prepare_context the GPU tests rely on: a single-key cond row whose key is not key 0 next to a 5-key negative prompt, smp_xl's layout, every
+    key valid, and a ragged 37-key tile.  The per-prompt inputs the GPU tests rebuild (tests/util.py sampler_prompts_case) are the ones stored."""
+    from oracle.mint_golden import sampler_prompt_inputs
+    from tests.util import load_golden
+    g4, meta4 = load_golden('sampler_smp_xl_p4')
+    g1, meta1 = load_golden('sampler_smp_xl')
+    assert g4['latent'].shape == (4, 128, 500) and g4['latent'].dtype == np.float32
+    assert np.array_equal(g4['latent'][1], g1['latent'][0])
+    for k in ('size', 'L', 'Lc', 'steps', 'seed_w', 'guidance_scale', 'guidance_rescale', 'eta'):
+        assert meta4[k] == meta1[k], k
+    assert meta4['prompts'][1]['seed_in'] == meta1['seed_in']
+    cm, um = g4['cond_mask'], g4['uncond_mask']
+    assert [list(np.flatnonzero(m)) for m in cm] == [[7], list(range(12)), list(range(100)), list(range(37))]
+    assert [list(np.flatnonzero(m)) for m in um] == [list(range(5)), [0], [0], [0]]
+    assert [p['neg_text'] for p in meta4['prompts']] == [True, False, False, False]
+    assert len({p['seed_in'] for p in meta4['prompts']}) == 4                    # every prompt its own context and noises
+    assert all(rel_l2(g4['latent'][i], g4['latent'][j]) > 0.1 for i in range(4) for j in range(i))
+    # the inputs the loader rebuilds: masks as stored, and prompt 1's are smp_xl's (tests/util.py sampler_case)
+    cfg = model_config(meta4['size'])
+    C, L, Lc, steps = cfg['out_chans'], meta4['L'], meta4['Lc'], meta4['steps']
+    for p, pr in enumerate(meta4['prompts']):
+        ctx, mask, init, noises = sampler_prompt_inputs(cfg, L, Lc, steps, pr)
+        assert np.array_equal(mask[0], cm[p]) and np.array_equal(mask[1], um[p])
+        assert ctx.shape == (2, Lc, cfg['context_dim']) and init.shape == (1, C, L) and len(noises) == steps
+    from oracle.weights import make_inputs
+    ctx, mask, init, noises = sampler_prompt_inputs(cfg, L, Lc, steps, meta4['prompts'][1])
+    inp = make_inputs(cfg, B=2, L=L, Lc=Lc, seed=meta1['seed_in'])
+    s3 = np.float32(np.sqrt(3.0))
+    assert np.array_equal(ctx, inp['ctx']) and np.array_equal(mask, inp['ctx_mask'])
+    assert np.array_equal(init, (uniform_pm1('smp.init', C * L, meta1['seed_in']) * s3).reshape(1, C, L))
+    assert np.array_equal(noises[-1], (uniform_pm1(f'smp.z{steps - 1}', C * L, meta1['seed_in']) * s3).reshape(1, C, L))

@@ -74,6 +74,20 @@ def sampler_case(name):
     return cfg, sd, inp, init, noises, g, meta
 
 
+def sampler_prompts_case(name):
+    """(cfg, per-prompt inputs, golden arrays, meta) of a multi-prompt sampler fixture (oracle/mint_golden.py mint_sampler_prompts): prompt p's inputs are
+    dict(ctx [2, Lc, Dc] = (text, negative text), mask [2, Lc], init [1, C, L], noises = steps x [1, C, L]), its golden latent g['latent'][p].  (No state
+    dict: the GPU tests' model cache builds its own, and at XL width one costs tens of seconds of CPU.)"""
+    from oracle.mint_golden import sampler_prompt_inputs
+    g, meta = load_golden('sampler_' + name)
+    cfg = model_config(meta['size'])
+    prompts = []
+    for pr in meta['prompts']:
+        ctx, mask, init, noises = sampler_prompt_inputs(cfg, meta['L'], meta['Lc'], meta['steps'], pr)
+        prompts.append(dict(ctx=ctx, mask=mask, init=init, noises=noises))
+    return cfg, prompts, g, meta
+
+
 DIFF = dict(num_train_timesteps=1000, beta_schedule='scaled_linear', beta_start=0.00085, beta_end=0.012,
             prediction_type='v_prediction', rescale_betas_zero_snr=True, timestep_spacing='trailing',
             clip_sample=False)
