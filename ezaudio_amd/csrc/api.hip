@@ -1538,6 +1538,92 @@ int ezdit_test_resid_skip(int tile, const void* A, int lda, const void* W, int l
     return EZDIT_OK;
 }
 
+// the DUAL form of the same launch (GemmArgs.zd; the attention-out projection when single-key batch elements skip cross-attention), stand-alone: the rows OUTSIDE
+// [act_row0, act_row1) get  h_out = h_in + gate * (A . W^T + bias) + zd[row / rows_per_b]  and  zu = bf16(h_out * zg2); the rows inside it no zd and the gain zg
+int ezdit_test_resid_dual(int tile, const void* A, int lda, const void* W, int ldw, const float* bias, const float* h_in, const float* gate, const float* zg,
+                          float* h_out, void* zu, int ld_zu, void* zstat, int M, int N, int K,
+                          const float* zd, long zd_stride, const float* zg2, int act_row0, int act_row1, int rows_per_b, ezdit_stream stream) {
+    if (K % 64) return fail(EZDIT_E_INVALID, "K=%d must be a multiple of 64", K);
+    if (!zd || rows_per_b <= 0) return fail(EZDIT_E_INVALID, "the DUAL form needs zd and rows_per_b");
+    GemmArgs g;
+    memset(&g, 0, sizeof g);
+    g.A = (const bf16_t*)A; g.lda = lda; g.W = (const bf16_t*)W; g.ldw = ldw; g.wrows = (int)rup(N, 128); g.bias = bias;
+    g.out = h_out; g.ldo = N; g.M = M; g.N = N; g.K = K; g.splitk = 1; g.epi = EPI_RESID; g.tile = tile; g.xcd_map = 1;
+    g.resid = h_in; g.ldr = N; g.gate = gate; g.rows_per_b = rows_per_b;
+    g.zu = (bf16_t*)zu; g.ld_zu = ld_zu; g.zg = zg; g.zstat_out = (float2*)zstat; g.zs_stride = M;
+    g.zd = zd; g.zd_stride = zd_stride; g.zg2 = zg2; g.act_row0 = act_row0; g.act_row1 = act_row1;
+    (void)hipGetLastError();
+    if (launch_gemm(g, (hipStream_t)stream)) return fail(EZDIT_E_UNSUPPORTED, "residual GEMM configuration not supported");
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of the residual GEMM failed: %s", hipGetErrorString(e));
+    return EZDIT_OK;
+}
+
+// consumer side of the LayerNorm algebra, stand-alone (GemmArgs.z*: what gemm() above fills from Ctx.zG / zC / zstat): epi = EPI_GEGLU (out bf16 [M][ldo]) or EPI_QKV
+// (nothing goes to `out`; q / k / v in the attention layouts, HeadNormArgs) with  acc := r (acc - mu zG[slot][col]) + zC[slot][col]  in the epilogue, (mu, r) merged from the
+// part-major partial statistics zstat_in [zparts][zs_stride], slot = *cur_step + row_slot[row / rows_per_b] (NULL = 0 each).  EPI_QKV: perm = 1 with RoPE tables is the fused
+// q | k | v projection (N = 3 H dh, W rows packed by EZDIT_T_QKROPE), perm = 0 with k = v = NULL and no tables the q-only projection of batched prompts (N = H dh)
+int ezdit_test_consumer(int tile, int epi, int epi_lds, const void* A, int lda, const void* W, int ldw, int wrows, const float* bias, void* out, int ldo, int M, int N, int K,
+                        const void* zstat_in, long zs_stride, int zparts, int zD, int zw, const float* zG, const float* zC, long zt_slot_stride, float zeps,
+                        const int* cur_step, const int* row_slot, int rows_per_b,
+                        const float* qn_w, const float* qn_b, const float* kn_w, const float* kn_b, const float* rope_cos, const float* rope_sin,
+                        void* q, void* k, void* v, int B, int H, int L, int Lp, int dh, int perm, ezdit_stream stream) {
+    if (K % 64) return fail(EZDIT_E_INVALID, "K=%d must be a multiple of 64", K);
+    if (epi != EPI_GEGLU && epi != EPI_QKV) return fail(EZDIT_E_INVALID, "epi %d is no LayerNorm-algebra consumer", epi);
+    if (!zstat_in || rows_per_b <= 0) return fail(EZDIT_E_INVALID, "the consumer form needs zstat_in and rows_per_b");
+    GemmArgs g;
+    memset(&g, 0, sizeof g);
+    g.A = (const bf16_t*)A; g.lda = lda; g.W = (const bf16_t*)W; g.ldw = ldw; g.wrows = wrows; g.bias = bias; g.out = out; g.ldo = ldo;
+    g.M = M; g.N = N; g.K = K; g.splitk = 1; g.epi = epi; g.tile = tile; g.xcd_map = 1; g.epi_lds = epi_lds;
+    g.zstat_in = (const float2*)zstat_in; g.zs_stride = zs_stride; g.zparts = zparts; g.zD = zD; g.zw = zw; g.zG = zG; g.zC = zC; g.zt_slot_stride = zt_slot_stride; g.zeps = zeps;
+    g.cur_step = cur_step; g.row_slot = row_slot; g.rows_per_b = rows_per_b;
+    if (epi == EPI_QKV) {
+        if (M != B * L) return fail(EZDIT_E_INVALID, "M=%d != B L = %d", M, B * L);
+        HeadNormArgs& hn = g.hn;
+        hn.q_col = 0; hn.k_col = k ? H * dh : -1; hn.v_col = v ? 2 * H * dh : -1;
+        hn.qn_w = qn_w; hn.qn_b = qn_b; hn.kn_w = kn_w; hn.kn_b = kn_b; hn.rope_cos = rope_cos; hn.rope_sin = rope_sin;
+        hn.q = (bf16_t*)q; hn.k = (bf16_t*)k; hn.v = (bf16_t*)v;
+        hn.B = B; hn.H = H; hn.L = L; hn.Lp = Lp; hn.dh = dh; hn.perm = perm;
+    }
+    (void)hipGetLastError();
+    if (launch_gemm(g, (hipStream_t)stream)) return fail(EZDIT_E_UNSUPPORTED, "consumer GEMM configuration not supported");
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of the consumer GEMM failed: %s", hipGetErrorString(e));
+    return EZDIT_OK;
+}
+
+// the RoPE tables as ezdit_bind_workspace fills them: cos / sin fp32 [max_len][dh / 2]
+int ezdit_test_rope_table(float* cosT, float* sinT, int max_len, int dh, ezdit_stream stream) {
+    if (!cosT || !sinT || max_len <= 0 || dh <= 0 || dh % 2) return fail(EZDIT_E_INVALID, "bad RoPE table request");
+    (void)hipGetLastError();
+    launch_rope_table(cosT, sinT, max_len, dh, (hipStream_t)stream);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of k_rope_table failed: %s", hipGetErrorString(e));
+    return EZDIT_OK;
+}
+
+// cross-attention with its own q projection and the LayerNorm algebra, stand-alone (the AttnArgs forward_impl builds for fuse_q2): q = LN_head(r (xu . xw_h^T - mu zG) + zC),
+// then softmax(q k^T / sqrt(dh) + mask) v over the batch elements [b0, b0 + B) of the buffers (all pointers are given for batch element 0)
+int ezdit_test_cross_attention(const void* xu, int ldu, const void* xw, int ldw, int xw_rows, int xK, const float* qn_w, const float* qn_b,
+                               const void* k, const void* v, const uint8_t* kmask, void* out, int ldo, int B, int b0, int H, int dh, int Lq, int Lk, int Lqp, int Lkp,
+                               const void* zstat_in, long zs_stride, int zparts, int zD, int zw, const float* zG, const float* zC, float zeps,
+                               int xk2, int qtile, int xcd_map, ezdit_stream stream) {
+    if (!xu || !xw || xK <= 0 || xK % 64) return fail(EZDIT_E_INVALID, "the fused projection needs xu, xw and xK a multiple of 64");
+    AttnArgs a;
+    memset(&a, 0, sizeof a);
+    a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.kmask = kmask;
+    a.out = (bf16_t*)out; a.ldo = ldo;
+    a.B = B; a.b0 = b0; a.H = H; a.Lq = Lq; a.Lk = Lk; a.Lqp = Lqp; a.Lkp = Lkp; a.dh = dh;
+    a.xu = (const bf16_t*)xu; a.ldu = ldu; a.xw = (const bf16_t*)xw; a.ldw = ldw; a.xw_rows = xw_rows; a.xK = xK;
+    a.qn_w = qn_w; a.qn_b = qn_b; a.nkh = 4; a.xk2 = xk2; a.qtile = qtile; a.xcd_map = xcd_map;
+    a.zstat_in = (const float2*)zstat_in; a.zs_stride = zs_stride; a.zparts = zparts; a.zD = zD; a.zw = zw; a.zG = zG; a.zC = zC; a.zeps = zeps;
+    (void)hipGetLastError();
+    if (launch_attention(a, (hipStream_t)stream)) return fail(EZDIT_E_UNSUPPORTED, "attention configuration not supported");
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of k_attn failed: %s", hipGetErrorString(e));
+    return EZDIT_OK;
+}
+
 int ezdit_test_attention(ezdit_handle* h, const void* q, const void* k, const void* v, const uint8_t* kmask, void* out, int B,
                          int Lq, int Lk, int Lqp, int Lkp, ezdit_stream stream) {
     if (!h) return fail(EZDIT_E_INVALID, "null handle");

@@ -218,6 +218,37 @@ int ezdit_test_resid_skip(int tile, const void* dev_a_bf16, int lda, const void*
                           const float* dev_gate, const float* dev_zg, float* dev_h_out, void* dev_zu_bf16, int ld_zu, void* dev_zstat,
                           int M, int N, int K, const float* dev_zg2, void* dev_zu2_bf16, int ld_zu2, const void* dev_zstat_in, const void* dev_zstat_in2,
                           int zparts, int zD, const float* dev_zG, ezdit_stream stream);
+/* ... and of its DUAL form (csrc/common.h GemmArgs.zd; tiles 70 and 61; gate and h_in required): the rows OUTSIDE [act_row0, act_row1) additionally get
+ * dev_zd[row / rows_per_b] (fp32 [batch elements][zd_stride]) in h_out and the gain dev_zg2 instead of dev_zg in zu; zstat covers h_out as stored. */
+int ezdit_test_resid_dual(int tile, const void* dev_a_bf16, int lda, const void* dev_w_bf16, int ldw, const float* dev_bias, const float* dev_h_in,
+                          const float* dev_gate, const float* dev_zg, float* dev_h_out, void* dev_zu_bf16, int ld_zu, void* dev_zstat,
+                          int M, int N, int K, const float* dev_zd, long zd_stride, const float* dev_zg2, int act_row0, int act_row1, int rows_per_b,
+                          ezdit_stream stream);
+/* unit-test hook of the LayerNorm algebra's CONSUMER side (csrc/common.h GemmArgs.z*; tiles 60, 61, 66): epi 2 (GEGLU: dev_out bf16 [M][ldo], ldo >= N / 2, W rows and the
+ * tables in the interleaved 8 value / 8 gate order) or epi 3 (fused QKV: dev_out unused).  The operand is A' = bf16(x g); the epilogue applies
+ * acc := r (acc - mu zG[slot][col]) + zC[slot][col] with (mu, r) of row m merged from dev_zstat_in -- float pairs (sum, sum of squares) [zparts][zs_stride], PART-MAJOR,
+ * part p = the columns [p zw, min((p + 1) zw, zD)) of x -- and slot = *dev_cur_step + dev_row_slot[m / rows_per_b] (either NULL = 0); zG, zC fp32 [slots][zt_slot_stride].
+ * dev_bias is what the forward passes along (C' already holds it: the consumer form must not add it again).  epi 3: M = B L token rows; q, k bf16 [B][H][Lp][DQK], v bf16
+ * [B][H][Lp][DV] (DQK / DV = 64 / 64 or 80 / 96 for head_dim 64 / 72; only rows < L and columns < dh are written); qn / kn: the per-head LayerNorm affine [dh]; rope
+ * cos / sin fp32 [>= L][dh / 2] or NULL.  perm 1: N = 3 H dh, W rows packed by EZDIT_T_QKROPE, q and k leave in that column order (two heads per tile); perm 0 with
+ * dev_k = dev_v = NULL and no tables: the q-only projection of batched prompts (tile 61, N = H dh, natural order). */
+int ezdit_test_consumer(int tile, int epi, int epi_lds, const void* dev_a_bf16, int lda, const void* dev_w_bf16, int ldw, int w_rows, const float* dev_bias,
+                        void* dev_out, int ldo, int M, int N, int K,
+                        const void* dev_zstat_in, long zs_stride, int zparts, int zD, int zw, const float* dev_zG, const float* dev_zC, long zt_slot_stride, float zeps,
+                        const int* dev_cur_step, const int* dev_row_slot, int rows_per_b,
+                        const float* dev_qn_w, const float* dev_qn_b, const float* dev_kn_w, const float* dev_kn_b, const float* dev_rope_cos, const float* dev_rope_sin,
+                        void* dev_q, void* dev_k, void* dev_v, int B, int H, int L, int Lp, int dh, int perm, ezdit_stream stream);
+/* the RoPE tables of the fused QKV epilogue as ezdit_bind_workspace fills them: cos / sin fp32 [max_len][dh / 2] */
+int ezdit_test_rope_table(float* dev_cos, float* dev_sin, int max_len, int dh, ezdit_stream stream);
+/* unit-test hook of cross-attention with its own q projection (csrc/attn.hip k_attn<.., ZQ, 32 | 64>; Lkp % 128 == 0): q = LN_head(r (xu . xw_h^T - mu zG) + zC) per head
+ * (xu bf16 [batch elements x Lq][ldu] = bf16(x g), xw bf16 [xw_rows][ldw] in nn.Linear layout, xK % 64 == 0, qn affine [dh], zG / zC fp32 [H dh], statistics as above with
+ * row = b Lq + query), then softmax(q k^T / sqrt(dh) + mask) v -> dev_out bf16 [batch elements x Lq][ldo].  k bf16 [.][H][Lkp][DQK], v bf16 [.][H][Lkp][DV], kmask [.][Lk].
+ * The launch covers the batch elements [b0, b0 + B); every pointer is given for batch element 0.  qtile 32 | 64 | 0 (auto), xk2 0 / 1, xcd_map 0 / 1 as the options. */
+int ezdit_test_cross_attention(const void* dev_xu, int ldu, const void* dev_xw, int ldw, int xw_rows, int xK, const float* dev_qn_w, const float* dev_qn_b,
+                               const void* dev_k, const void* dev_v, const uint8_t* dev_kmask, void* dev_out, int ldo, int B, int b0, int H, int dh,
+                               int Lq, int Lk, int Lqp, int Lkp,
+                               const void* dev_zstat_in, long zs_stride, int zparts, int zD, int zw, const float* dev_zG, const float* dev_zC, float zeps,
+                               int xk2, int qtile, int xcd_map, ezdit_stream stream);
 /* test hook: launches of k_gemm_pp / k_gemm_ks / k_attn record, per workgroup, eight 64-bit shader-clock stamps (kernel start, K-loop
  * start, K-loop end, kernel end, then epilogue internals) into dev_buf ([capacity_workgroups][8] uint64; NULL switches it off).  A launch
  * whose grid exceeds capacity_workgroups writes no stamps.  Un-register (NULL) before freeing the buffer. */

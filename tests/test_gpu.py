@@ -14,6 +14,7 @@ import torch
 from oracle.dit import DiTOracle
 from oracle.sampler import sample as oracle_sample
 from oracle.weights import make_inputs, make_state_dict, model_config, uniform_pm1
+from tests import kernel_emul as KE
 from tests.util import DIFF, golden_case, record, rel_l2, sampler_case, sampler_prompts_case
 
 pytestmark = pytest.mark.gpu
@@ -301,6 +302,240 @@ def test_gemm_geglu_epilogue(lib, dev, tile):
     assert rc == 0
     torch.cuda.synchronize()
     assert rel_l2(out.float().cpu().numpy(), ref.numpy()) < 4e-3  # one bf16 rounding of the output
+
+
+# ---- LayerNorm-algebra consumers and the DUAL producer, one kernel at a time against fp64 (inputs, references, emulated floors and gates: tests/kernel_emul.py) ----
+def _dev_consumer_tables(c, dev, G, C):
+    """device copies of what every consumer launch reads: statistics (NaN outside [zparts][M]), G' / C' [slots][N], step counter and per-batch-element slot offsets"""
+    d = dict(stats=c.stats.to(dev), G=G.contiguous().to(dev), C=C.contiguous().to(dev), cur=torch.tensor([c.cur_step], dtype=torch.int32, device=dev),
+             rs=c.row_slot.to(dev) if c.row_slot is not None else None)
+    d['rs_ptr'] = d['rs'].data_ptr() if d['rs'] is not None else None
+    return d
+
+
+def _assert_bf16_bits(got_bf16, emul, ref_a, what):
+    """bf16 outputs against reference (a): every element within one bf16 ulp of bf16(reference) -- the ulp taken at max(|reference|, 2^-10 rms(reference)): below that the
+    fp32 epilogue's own absolute error, ~1e-7 of terms of the size of the rms, is no longer small against a bf16 ulp of the value -- and the share of elements that are not
+    bit-equal at most twice what the CPU emulation of the same case shows.  Such flips are rare independent events (an fp32 value within ~1e-7 of a bf16 rounding boundary), so
+    their number scatters like a Poisson variable: the cap on the count is 2 n + 3 sqrt(2 n) + 3 for n flips in the emulation -- twice the emulated share plus three standard
+    deviations of a count of that mean, which matters for outputs of a few ten thousand elements where n is 0 .. 3."""
+    want = ref_a.float().to(torch.bfloat16).float()
+    floor = float(ref_a.pow(2).mean().sqrt()) * 2.0 ** -10
+    ulp = torch.exp2(torch.floor(torch.log2(ref_a.abs().float().clamp_min(floor))) - 7)
+    d = (got_bf16.float() - want).abs()
+    worst = float((d / ulp).max())
+    share = float((got_bf16.float() != want).double().mean())
+    n_e = int((emul != want).sum())
+    share_e = n_e / want.numel()
+    cap = (KE.ULP_SHARE_CAP * n_e + 3 * (KE.ULP_SHARE_CAP * n_e) ** 0.5 + 3) / want.numel()
+    record(f'{what}: worst distance {worst:.2f} bf16 ulp, not bit-equal {share:.2e} (emulation {share_e:.2e}, cap {cap:.2e})')
+    assert worst <= 1.0, worst
+    assert share <= cap, (share, cap)
+
+
+def _geglu_consumer(lib, dev, tile, case, per_row, mean_scale, gate_b):
+    M, D, zw, inner = case
+    c = KE.geglu_case(M, D, zw, inner, per_row, mean_scale)
+    W, G, C, bias = KE.geglu_device_order(c)
+    N, K = 2 * inner, (D + 63) // 64 * 64
+    wrows = (N + 127) // 128 * 128
+    A = torch.zeros(M, K, dtype=torch.bfloat16); A[:, :D] = c.A
+    Wp = torch.zeros(wrows, K, dtype=torch.bfloat16); Wp[:N, :D] = W
+    t = _dev_consumer_tables(c, dev, G, C)
+    Ad, Wd, bd = A.to(dev), Wp.to(dev), bias.to(dev)
+    out = torch.full((M, inner), float('nan'), dtype=torch.bfloat16, device=dev)
+    rc = lib.ezdit_test_consumer(tile % 1000, 2, 1 if tile >= 2000 else 0, Ad.data_ptr(), K, Wd.data_ptr(), K, wrows, bd.data_ptr(), out.data_ptr(), inner, M, N, K,
+                                 t['stats'].data_ptr(), c.rows_alloc, c.zparts, D, zw, t['G'].data_ptr(), t['C'].data_ptr(), N, 1e-5,
+                                 t['cur'].data_ptr(), t['rs_ptr'], c.rows_per_b, None, None, None, None, None, None, None, None, None, 0, 0, 0, 0, 0, 0, None)
+    assert rc == 0, lib.ezdit_last_error()
+    torch.cuda.synchronize()
+    got = out.cpu()
+    assert torch.isfinite(got.float()).all()      # a NaN here = a statistics row >= M or a part >= zparts was merged
+    ra, rb = KE.geglu(c.ref_a()), KE.geglu(c.ref_b())
+    ea, eb = KE.rel_l2(got, ra), KE.rel_l2(got, rb)
+    what = f'consumer GEGLU tile {tile} M={M} D={D} zw={zw} inner={inner} per_row={int(per_row)} mean x{mean_scale:g}'
+    record(f'{what}: rel-L2 same operand {ea:.3e} (gate {KE.GATE_GEGLU_A:.1e}), true LayerNorm {eb:.3e} (gate {gate_b:.1e})')
+    assert ea < KE.GATE_GEGLU_A
+    assert eb < gate_b
+    _assert_bf16_bits(got, KE.bf16r(KE.geglu(c.emul())), ra, what)
+
+
+@pytest.mark.parametrize('per_row', [False, True])     # one modulation slot for the launch (G' | C' parked in LDS) / a slot per batch element (read per row)
+@pytest.mark.parametrize('tile', [60, 66, 2060, 2066])   # ping-pong 128 x 288, co-resident 128 x 144; + 2000: LDS-staged store as the forward launches them
+@pytest.mark.parametrize('case', KE.GEGLU_CASES)
+def test_consumer_geglu_gemm_finishes_the_layernorm_of_its_operand(lib, dev, case, tile, per_row):
+    """GEGLU GEMM as LayerNorm-algebra consumer, alone: out = geglu(r (A' W^T - mu G'[slot]) + C'[slot]) with (mu, r) of each row merged from 12, 8, 6, 2, 11 or 12 partial
+    statistics (1024 leaves a ragged 64-column last part, 160 has fewer parts than the four lanes that fetch them, the last case is one row).  Every row has its own mean and
+    spread, rows >= M and parts >= zparts of the table are NaN, G' and C' differ per slot, the step counter is 2 and the batch elements sit in different slots.
+    Gates (tests/kernel_emul.py): same operand 3.6e-3 = 2 x the emulated 1.8e-3, true LayerNorm 5e-3 (emulated 3.3e-3; capped by the ZIN gate)."""
+    _geglu_consumer(lib, dev, tile, case, per_row, 1.0, KE.GATE_GEGLU_B)
+
+
+@pytest.mark.parametrize('tile', [60, 66])
+def test_consumer_geglu_gemm_survives_row_means_at_five_times_the_spread(lib, dev, tile):
+    """As above with row means up to five times the spread (what test_residual_gemm_statistics_survive_a_row_mean_far_above_the_spread does for the producers).  Against the
+    same operand the gate is unchanged.  Against the true LayerNorm the bf16 rounding of x g grows with |mean| / sigma: the emulation shows 7.4e-3, gate 1.5e-2 -- the 5e-3
+    cap of the other cases belongs to rows with |mean| <= sigma."""
+    _geglu_consumer(lib, dev, tile, KE.GEGLU_FAR_MEAN, True, 5.0, KE.GATE_GEGLU_B_FAR)
+
+
+def _qkv_launch(lib, dev, c, tile):
+    """one EPI_QKV consumer launch of a tests/kernel_emul.py QkvCase; returns (q, k, v) as stored (zero-initialised buffers, like the workspace) and the RoPE tables the launch read"""
+    cc, H, dh, B, L, Lp, D = c.c, c.H, c.dh, c.B, c.L, c.Lp, c.D
+    M, N = B * L, c.nparts * D
+    K = (D + 63) // 64 * 64
+    W, G, C = c.device_weights()
+    wrows = (N + 127) // 128 * 128
+    A = torch.zeros(M, K, dtype=torch.bfloat16); A[:, :D] = cc.A
+    Wp = torch.zeros(wrows, K, dtype=torch.bfloat16); Wp[:N, :D] = W
+    t = _dev_consumer_tables(cc, dev, G, C)
+    Ad, Wd = A.to(dev), Wp.to(dev)
+    aff = [x.to(dev) for x in (c.qn_w, c.qn_b, c.kn_w, c.kn_b)]
+    cos = torch.zeros(L, dh // 2, device=dev); sin = torch.zeros(L, dh // 2, device=dev)
+    if not c.q_only:
+        assert lib.ezdit_test_rope_table(cos.data_ptr(), sin.data_ptr(), L, dh, None) == 0
+    q = torch.zeros(B, H, Lp, c.DQK, dtype=torch.bfloat16, device=dev)
+    k = torch.zeros(B, H, Lp, c.DQK, dtype=torch.bfloat16, device=dev)
+    v = torch.zeros(B, H, Lp, c.DV, dtype=torch.bfloat16, device=dev)
+    rc = lib.ezdit_test_consumer(tile, 3, 0, Ad.data_ptr(), K, Wd.data_ptr(), K, wrows, None, None, 0, M, N, K,
+                                 t['stats'].data_ptr(), cc.rows_alloc, cc.zparts, D, 96, t['G'].data_ptr(), t['C'].data_ptr(), N, 1e-5,
+                                 t['cur'].data_ptr(), t['rs_ptr'], L, aff[0].data_ptr(), aff[1].data_ptr(), aff[2].data_ptr(), aff[3].data_ptr(),
+                                 None if c.q_only else cos.data_ptr(), None if c.q_only else sin.data_ptr(),
+                                 q.data_ptr(), None if c.q_only else k.data_ptr(), None if c.q_only else v.data_ptr(), B, H, L, Lp, dh, 0 if c.q_only else 1, None)
+    assert rc == 0, lib.ezdit_last_error()
+    torch.cuda.synchronize()
+    return [x.cpu() for x in ((q,) if c.q_only else (q, k, v))], cos.cpu(), sin.cpu()
+
+
+def _qkv_check(c, got, cos, sin, what):
+    L, dh = c.L, c.dh
+    for name, t in zip('qkv', got):
+        # what k_attn relies on in the padding (attn.hip): QK^T contracts over all DQK columns of q and k, so the columns [dh, DQK) must be zero in both; P . V runs over whole
+        # 64- / 128-key tiles with P = 0 for the keys >= Lk, so the rows [L, Lp) of v must be finite (0 x NaN = NaN); the workspace is zeroed once at bind time and this
+        # launch must leave every padding element as it found it
+        assert (t[:, :, L:] == 0).all(), f'{name}: rows [L, Lp) written'
+        assert (t[:, :, :, dh:] == 0).all(), f'{name}: columns [dh, ..) written'
+    if not c.q_only:
+        rc64, rs64 = KE.rope_tables64(L, dh)
+        assert (cos.double() - rc64.double()).abs().max() < 1e-4 and (sin.double() - rs64.double()).abs().max() < 1e-4     # fp32 angles up to 500 rad: 500 x 2^-24 = 3e-5
+    val = [t[:, :, :L, :dh] for t in got]
+    nat = [c.unpermute(val[0])] + ([c.unpermute(val[1]), val[2]] if not c.q_only else [])
+    ra = c.ref_a(None if c.q_only else cos, None if c.q_only else sin)      # same operand: the tables the launch read
+    rb = c.ref_b()
+    em = c.emul(None, None if c.q_only else cos, None if c.q_only else sin)
+    for name, g_, a_, b_, e_ in zip('qkv', nat, ra, rb, em):
+        assert torch.isfinite(g_.float()).all()
+        ea, eb = KE.per_head_rel(g_, a_), KE.per_head_rel(g_, b_)
+        record(f'{what} {name}: worst head rel-L2 same operand {ea:.3e} (gate {KE.GATE_QKV_A:.1e}), true LayerNorm {eb:.3e} (gate {KE.GATE_QKV_B:.1e})')
+        assert ea < KE.GATE_QKV_A
+        assert eb < KE.GATE_QKV_B
+        _assert_bf16_bits(g_.contiguous(), e_, a_, f'{what} {name}')
+    if not c.q_only:    # order-free: the stored column order of q and k against each other
+        e = KE.qkt_err(val[0], val[1], ra[0], ra[1])
+        record(f'{what} q.k^T: worst head error / (|q| |k|) {e:.3e} (gate {KE.GATE_QKT:.1e})')
+        assert e < KE.GATE_QKT
+
+
+@pytest.mark.parametrize('tile', [61, 66])     # ping-pong kernel (k-split schedule) and co-resident kernel: two heads per tile, epilogue in registers
+@pytest.mark.parametrize('B,L', KE.QKV_BL)
+@pytest.mark.parametrize('H,dh', KE.QKV_HEADS)
+def test_fused_qkv_gemm_consumer_against_fp64(lib, dev, H, dh, B, L, tile):
+    """EPI_QKV with hn.perm = 1, alone: consumer finish -> heads -> LayerNorm per head (shared [dh] affine, eps 1e-5) -> RoPE (oracle/dit.py apply_rope) -> q, k, v in
+    [B][H][Lp][DQK | DV].  Batch boundaries fall inside a 128-row tile (the RoPE position restarts mid-tile), L = 77, 131 and 1 leave Lp padding.  q and k are compared after
+    mapping the stored column order back through qkrope_col; q . k^T per head needs no mapping.  The batch elements sit in different modulation slots.
+    Gates per head (tests/kernel_emul.py): same operand 4e-3 (emulated 2.02e-3), true LayerNorm 5e-3 (emulated 2.9e-3; capped), q . k^T 1.1e-3 of |q| |k| (emulated 5.3e-4)."""
+    c = KE.qkv_case(H, dh, B, L, True)
+    got, cos, sin = _qkv_launch(lib, dev, c, tile)
+    _qkv_check(c, got, cos, sin, f'fused QKV tile {tile} H={H} dh={dh} B={B} L={L}')
+
+
+@pytest.mark.parametrize('per_row', [False, True])
+@pytest.mark.parametrize('B,L', [(8, 500), (3, 131)])
+@pytest.mark.parametrize('H,dh', KE.QKV_HEADS)
+def test_q_only_projection_of_batched_prompts_against_fp64(lib, dev, H, dh, B, L, per_row):
+    """The q2_pp form: EPI_QKV restricted to q (k_col = v_col = -1, natural weight order, no RoPE; tile 61, the fp32-park epilogue), as consumer."""
+    c = KE.qkv_case(H, dh, B, L, per_row, True)
+    got, cos, sin = _qkv_launch(lib, dev, c, 61)
+    _qkv_check(c, got, cos, sin, f'q-only projection H={H} dh={dh} B={B} L={L} per_row={int(per_row)}')
+
+
+@pytest.mark.parametrize('xk2', [0, 1])
+@pytest.mark.parametrize('qtile', [32, 64])
+@pytest.mark.parametrize('n_valid', KE.XATTN_VALID)
+@pytest.mark.parametrize('Lq', KE.XATTN_LQ)
+@pytest.mark.parametrize('B,b0,Btot', KE.XATTN_B)
+@pytest.mark.parametrize('H,dh', KE.XATTN_WIDTHS)
+def test_cross_attention_with_its_own_q_projection_against_fp64(lib, dev, H, dh, B, b0, Btot, Lq, n_valid, qtile, xk2):
+    """k_attn<.., ZQ, 32 | 64>, alone: q = LN_head(r (xu W_h^T - mu G') + C') -> softmax over the valid keys -> P . V, for the batch elements [b0, b0 + B) of buffers that hold
+    Btot.  Lk = 100 (Lkp = 128) with 100, 12 or 2 valid keys per batch element (the even ones at the front, the odd ones at the end), the spiked key of
+    test_attention_against_softmax_reference, and V = 30 in every row no query may see (masked keys, padding rows).  Rows of the other batch elements keep their sentinel.
+    Gates (tests/kernel_emul.py): same operand 5.8e-3 (emulated 2.87e-3), true LayerNorm 8.3e-3 (emulated 4.14e-3), max-abs 0.06 (emulated 0.039)."""
+    c = KE.xattn_case(H, dh, Btot, Lq, n_valid)
+    cc, D, Lk, Lkp, Lqp = c.c, c.D, c.Lk, c.Lkp, c.Lqp
+    M = Btot * Lq
+    K = (D + 63) // 64 * 64
+    wrows = (D + 127) // 128 * 128
+    A = torch.zeros(M, K, dtype=torch.bfloat16); A[:, :D] = cc.A
+    Wp = torch.zeros(wrows, K, dtype=torch.bfloat16); Wp[:D, :D] = cc.W
+    kp = torch.zeros(Btot, H, Lkp, c.DQK, dtype=torch.bfloat16); kp[..., :dh] = c.k
+    vp = torch.zeros(Btot, H, Lkp, c.DV, dtype=torch.bfloat16); vp[..., :dh] = c.v
+    SENT = -7.0
+    out = torch.full((M, K), SENT, dtype=torch.bfloat16, device=dev)
+    dv = [t.to(dev) for t in (A, Wp, c.qn_w, c.qn_b, kp, vp, c.mask.to(torch.uint8), cc.stats, cc.G[cc.cur_step].contiguous(), cc.C[cc.cur_step].contiguous())]
+    rc = lib.ezdit_test_cross_attention(dv[0].data_ptr(), K, dv[1].data_ptr(), K, wrows, K, dv[2].data_ptr(), dv[3].data_ptr(), dv[4].data_ptr(), dv[5].data_ptr(),
+                                        dv[6].data_ptr(), out.data_ptr(), K, B, b0, H, dh, Lq, Lk, Lqp, Lkp,
+                                        dv[7].data_ptr(), cc.rows_alloc, cc.zparts, D, 96, dv[8].data_ptr(), dv[9].data_ptr(), 1e-5, xk2, qtile, 1, None)
+    assert rc == 0, lib.ezdit_last_error()
+    torch.cuda.synchronize()
+    got = out.cpu().float()
+    rows = slice(b0 * Lq, (b0 + B) * Lq)
+    keep = torch.ones(M, dtype=torch.bool); keep[rows] = False
+    assert (got[keep] == SENT).all() and (got[:, D:] == SENT).all()      # nothing outside the sub-range, nothing beyond the model width
+    g_ = got[rows, :D]
+    assert torch.isfinite(g_).all()
+    ra, rb = c.ref_a()[rows], c.ref_b()[rows]
+    ea, eb, eabs = KE.rel_l2(g_, ra), KE.rel_l2(g_, rb), float((g_.double() - rb).abs().max())
+    record(f'cross-attention H={H} dh={dh} B={B} b0={b0} of {Btot} Lq={Lq} valid={n_valid} qtile={qtile} xk2={xk2}: rel-L2 same operand {ea:.3e} (gate {KE.GATE_XATTN_A:.1e}), '
+           f'true LayerNorm {eb:.3e} (gate {KE.GATE_XATTN_B:.1e}), max-abs {eabs:.3f}')
+    assert ea < KE.GATE_XATTN_A
+    assert eb < KE.GATE_XATTN_B
+    assert eabs < KE.GATE_XATTN_ABS
+
+
+@pytest.mark.parametrize('form', ['empty', 'whole', 'middle'])
+@pytest.mark.parametrize('tile', [70, 61])
+@pytest.mark.parametrize('M,D', KE.DUAL_SHAPES)
+def test_dual_form_of_the_attention_out_projection(lib, dev, M, D, tile, form):
+    """EPI_RESID with GemmArgs.zd: inside [act_row0, act_row1) h = h_in + gate (A W^T + b) and zu = bf16(h zg); outside it h additionally gets zd[batch element] and zu the
+    gain zg2.  The range is empty, everything, or a middle piece whose ends are on no tile boundary; four batch elements.  fp32 stream 1e-5 (emulated 1.1e-7), zu 3e-3 (one
+    bf16 rounding, emulated 1.7e-3), statistics as the producer tests."""
+    c = KE.dual_case(M, D)
+    r0, r1 = KE.dual_ranges(M)[form]
+    cw = ZW[tile]
+    parts = (D + cw - 1) // cw
+    ld, Np, K = (D + 63) // 64 * 64, (D + 127) // 128 * 128, (D + 63) // 64 * 64
+    A = torch.zeros(M, K, dtype=torch.bfloat16); A[:, :D] = c.A
+    W = torch.zeros(Np, K, dtype=torch.bfloat16); W[:D, :D] = c.W
+    dv = [t.to(dev) for t in (A, W, c.bias, c.h_in, c.gate, c.zg, c.zd, c.zg2)]
+    h_out = torch.full((M, D), float('nan'), device=dev)
+    zu = torch.zeros(M, ld, dtype=torch.bfloat16, device=dev)
+    zs = torch.zeros(parts, M, 2, device=dev)
+    rc = lib.ezdit_test_resid_dual(tile, dv[0].data_ptr(), K, dv[1].data_ptr(), K, dv[2].data_ptr(), dv[3].data_ptr(), dv[4].data_ptr(), dv[5].data_ptr(),
+                                   h_out.data_ptr(), zu.data_ptr(), ld, zs.data_ptr(), M, D, K, dv[6].data_ptr(), D, dv[7].data_ptr(), r0, r1, c.rows_per_b, None)
+    assert rc == 0, lib.ezdit_last_error()
+    torch.cuda.synchronize()
+    h64, z64 = c.forms(r0, r1, torch.float64)
+    got = h_out.cpu().double()
+    eh = KE.rel_l2(got, h64)
+    ez = KE.rel_l2(zu.cpu()[:, :D], z64)
+    record(f'DUAL tile {tile} M={M} D={D} rows [{r0}, {r1}): fp32 stream rel-L2 {eh:.3e} (gate {KE.GATE_DUAL_H:.1e}), zu {ez:.3e} (gate {KE.GATE_DUAL_ZU:.1e})')
+    assert eh < KE.GATE_DUAL_H
+    assert ez < KE.GATE_DUAL_ZU
+    assert (zu.float().cpu()[:, D:] == 0).all()
+    st = zs.cpu().double().permute(1, 0, 2)
+    mean = st[:, :, 0].sum(1) / D
+    np.testing.assert_allclose(mean.numpy(), h64.mean(1).numpy(), rtol=0, atol=2e-5)
+    np.testing.assert_allclose((st[:, :, 1].sum(1) / D - mean ** 2).numpy(), h64.var(1, unbiased=False).numpy(), rtol=1e-4)
 
 
 @pytest.mark.parametrize('nkh', [2, 4])   # 64-key tiles / 4 waves and 128-key tiles / 8 waves

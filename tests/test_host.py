@@ -872,3 +872,87 @@ def test_inline_asm_mfma_results_are_read_behind_their_wait_states():
         assert min(touches[kern].values()) > 0, (kern, touches[kern])
     for kern, per in touches.items():
         assert sum(per.values()) >= 10, (kern, per)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the gates of the kernel-level consumer tests (tests/test_gpu.py) against the CPU emulation of tests/kernel_emul.py:
+# the emulation itself stays within half of every gate, and every deliberate mistake exceeds the gate meant to catch it three times over
+# ---------------------------------------------------------------------------------------------------
+STAT_MUTATIONS = ('row+1', 'drop_last_part', 'part_twice', 'G_neighbour_slot')
+
+
+def _geglu_cases():
+    from tests import kernel_emul as KE
+    return [(c, 1.0) for c in KE.GEGLU_CASES] + [(KE.GEGLU_FAR_MEAN, 5.0)]
+
+
+@pytest.mark.parametrize('case,mean_scale', _geglu_cases())
+def test_consumer_geglu_gates_hold_the_emulation_and_catch_every_statistics_mistake(case, mean_scale):
+    """rel-L2 of the emulated kernel against reference (a) <= gate / 2 (the gate is twice the emulated floor or the older, tighter cap), against (b) below the gate;
+    statistics of row r + 1, last part dropped, one part counted twice, G' of the neighbouring slot: each >= 3 x the gate.  (One row has no row r + 1.)"""
+    import torch
+    from tests import kernel_emul as KE
+    for per_row in (False, True):
+        c = KE.geglu_case(*case, per_row, mean_scale)
+        ra, rb = KE.geglu(c.ref_a()), KE.geglu(c.ref_b())
+        em = KE.bf16r(KE.geglu(c.emul()))
+        gate_b = KE.GATE_GEGLU_B_FAR if mean_scale > 1 else KE.GATE_GEGLU_B
+        assert KE.rel_l2(em, ra) <= KE.GATE_GEGLU_A / 2 * 1.001 and KE.rel_l2(em, rb) <= max(gate_b / 2, 3.4e-3)   # (3.3e-3 emulated under the 5e-3 cap)
+        assert not torch.isnan(em).any()
+        for mut in STAT_MUTATIONS:
+            if mut == 'row+1' and c.M == 1:
+                continue
+            bad = KE.bf16r(KE.geglu(c.emul(mut)))
+            assert KE.rel_l2(bad, ra) >= 3 * KE.GATE_GEGLU_A, (mut, per_row, KE.rel_l2(bad, ra))
+            assert KE.rel_l2(bad, rb) >= 3 * gate_b, (mut, per_row, KE.rel_l2(bad, rb))
+
+
+@pytest.mark.parametrize('B,L', [(2, 500), (2, 77), (8, 500), (3, 131), (2, 1)])
+@pytest.mark.parametrize('H,dh', [(16, 72), (2, 72), (16, 64), (4, 64)])
+def test_fused_qkv_gates_hold_the_emulation_and_catch_every_mistake(H, dh, B, L):
+    """As above for the fused QKV test (worst head of q, k, v), plus: one head's RoPE pair (c, c + dh / 2) swapped, RoPE position not reset at a batch boundary, head
+    LayerNorm over DQK instead of dh columns (head_dim 72 only: at 64, DQK = dh and there is no such mistake to make)."""
+    from tests import kernel_emul as KE
+    c = KE.qkv_case(H, dh, B, L, True)
+    ra, rb, em = c.ref_a(), c.ref_b(), c.emul()
+    assert max(KE.per_head_rel(e, a) for e, a in zip(em, ra)) <= 2.05e-3 and max(KE.per_head_rel(e, b) for e, b in zip(em, rb)) <= 2.9e-3   # the emulated floors (the gates 4e-3 / 5e-3 are the older caps, just under twice these)
+    assert KE.qkt_err(em[0], em[1], ra[0], ra[1]) <= KE.GATE_QKT / 2
+    muts = STAT_MUTATIONS + ('rope_pair_swapped', 'rope_no_reset') + (('ln_over_dqk',) if dh == 72 else ())
+    for mut in muts:
+        bad = c.emul(mut)
+        wa = max(KE.per_head_rel(x, a) for x, a in zip(bad, ra))
+        wb = max(KE.per_head_rel(x, b) for x, b in zip(bad, rb))
+        assert wa >= 3 * KE.GATE_QKV_A and wb >= 3 * KE.GATE_QKV_B, (mut, wa, wb)
+    bad = c.emul('rope_pair_swapped')      # (swapped in q only: the order-free check sees it too)
+    assert KE.qkt_err(bad[0], bad[1], ra[0], ra[1]) >= 3 * KE.GATE_QKT
+
+
+@pytest.mark.parametrize('n_valid', [100, 12, 2])
+@pytest.mark.parametrize('Lq', [500, 77, 1])
+@pytest.mark.parametrize('H,dh,Btot', [(16, 72, 2), (16, 72, 4), (6, 64, 2), (6, 64, 4)])
+def test_cross_attention_gates_hold_the_emulation_and_catch_every_mistake(H, dh, Btot, Lq, n_valid):
+    """... and for cross-attention with its own q projection: the statistics mistakes, and one key beyond the mask admitted."""
+    from tests import kernel_emul as KE
+    c = KE.xattn_case(H, dh, Btot, Lq, n_valid)
+    ra, rb, em = c.ref_a(), c.ref_b(), c.emul()
+    assert KE.rel_l2(em, ra) <= KE.GATE_XATTN_A / 2 and KE.rel_l2(em, rb) <= KE.GATE_XATTN_B / 2 and float((em.double() - rb).abs().max()) <= 0.04
+    for mut in ('row+1', 'drop_last_part', 'part_twice', 'one_key_beyond_mask'):
+        if mut == 'row+1' and Btot * Lq == 1:
+            continue
+        bad = c.emul(mut)
+        assert KE.rel_l2(bad, ra) >= 3 * KE.GATE_XATTN_A and KE.rel_l2(bad, rb) >= 3 * KE.GATE_XATTN_B, (mut, KE.rel_l2(bad, ra), KE.rel_l2(bad, rb))
+
+
+@pytest.mark.parametrize('M,D', [(1000, 1152), (300, 576), (77, 160)])
+def test_dual_form_gates_catch_zd_added_inside_the_active_range(M, D):
+    import torch
+    from tests import kernel_emul as KE
+    c = KE.dual_case(M, D)
+    for form, (r0, r1) in KE.dual_ranges(M).items():
+        h64, z64 = c.forms(r0, r1, torch.float64)
+        h32, z32 = c.forms(r0, r1, torch.float32)
+        assert KE.rel_l2(h32, h64) <= 1.1e-7 and KE.rel_l2(KE.bf16r(z32), z64) <= 1.7e-3
+        if form == 'empty':       # no active range: nothing to add zd inside of
+            continue
+        hm, zm = c.forms(r0, r1, torch.float32, 'zd_inside')
+        assert KE.rel_l2(hm, h64) >= 3 * KE.GATE_DUAL_H and KE.rel_l2(KE.bf16r(zm), z64) >= 3 * KE.GATE_DUAL_ZU
