@@ -49,6 +49,7 @@ PROTOTYPES = {
     'ezdit_prepare_context': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'ezdit_prepare_timesteps': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p]),
     'ezdit_set_step': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    'ezdit_set_lengths': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p]),
     'ezdit_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                 C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p]),
     'ezdit_prepare_condition': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -90,6 +91,10 @@ PROTOTYPES = {
                                              C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'ezdit_test_attention': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    'ezdit_test_attention_varlen': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'ezdit_test_final_conv': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                        C.c_void_p, C.c_void_p]),
     'ezdit_debug_buffer': (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     'ezdit_last_launch_count': (C.c_int, [C.c_void_p]),
     'ezdit_debug_stop_after': (C.c_int, [C.c_void_p, C.c_int]),

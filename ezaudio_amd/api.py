@@ -78,9 +78,17 @@ class EzAudio:
     def generate_audio(self, text, length=10, guidance_scale=5, guidance_rescale=0.75, ddim_steps=100, eta=1,
                        random_seed=None, randomize_seed=False):
         """api/ezaudio.py:101-130.  `text` may also be a list of prompts (batched extension): the result is then
-        an array [N, T]."""
+        an array [N, T].  With a list of prompts `length` may be a list too, one duration in seconds per prompt (mixed-length
+        batch, one call): the result is then (sr, [one 1-D array per prompt]), each trimmed to its own duration."""
         neg_text = None
-        length = length * self.params['autoencoder']['latent_sr']
+        latent_sr = self.params['autoencoder']['latent_sr']
+        per_prompt = isinstance(length, (list, tuple))
+        if per_prompt:
+            if isinstance(text, str) or len(length) != len(text):
+                raise ValueError('a list of lengths needs a list of prompts of the same size')
+            length = [int(round(v * latent_sr)) for v in length]
+        else:
+            length = length * latent_sr
         gt, gt_mask = None, None
         if text == '':
             guidance_scale = None
@@ -91,6 +99,9 @@ class EzAudio:
                          self.noise_scheduler, text, neg_text, length, guidance_scale, guidance_rescale, ddim_steps,
                          eta, random_seed, self.device)
         pred = pred.cpu().numpy()
+        if per_prompt:
+            ratio = self.params['autoencoder']['sr'] // latent_sr
+            return self.params['autoencoder']['sr'], [pred[i, 0, :n * ratio] for i, n in enumerate(length)]
         pred = pred.squeeze(0).squeeze(0) if isinstance(text, str) or len(text) == 1 else pred.squeeze(1)
         return self.params['autoencoder']['sr'], pred
 

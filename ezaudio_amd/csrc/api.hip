@@ -57,6 +57,7 @@ struct WsPtrs {  // workspace regions used on the per-step path, resolved once a
     float *cembed, *cnres; bf16_t* skipbf;   // ControlNet only
     float2* zstat; float *zt_qkv, *zt_geglu, *zt_q2;   // LayerNorm algebra: partial row statistics, G' / C' tables
     float2* zstat_skip; float* zt_skip; bf16_t* ucat_z;              // ... of the out-blocks' LN_2D([x | skip]) -> skip_linear: the skips' statistics (kept from the in-block to its out-block), static tables
+    int* lens;   // [B] per-batch-element valid frames (ezdit_set_lengths); read by the kernels only while ezdit_handle::lens_on
     float* zd;   // [nblk][B][D] constant cross-attention-out vectors of the single-key batch elements (opt_xkey1)
 };
 
@@ -94,6 +95,12 @@ struct ezdit_handle {
     float gscale = 0.f, grescale = 0.f;
     hipGraphExec_t graph_exec = nullptr;
     hipGraph_t graph = nullptr;
+
+    // padded batch (ezdit_set_lengths): batch element b is valid on frames [0, lens[b]).  The kernels read the device table at run time, so a captured step serves every
+    // set of lengths; only switching the feature on or off changes kernel arguments (null <-> table) and drops the graph
+    bool lens_on = false;
+    std::vector<int> lens;       // host mirror, expanded to B entries (the source of the asynchronous upload: must outlive it)
+    const int* lens_dev() const { return lens_on ? p.lens : nullptr; }
 
     int launches = 0;
     bool is_cn = false;          // ControlNet variant (cfg.controlnet)
@@ -438,6 +445,7 @@ size_t carve(const ezdit_handle* h, int B, int L, int Lc, int n_slots, std::map<
         add("ucat_z", (size_t)((!h->is_cn && h->nhalf > 0) ? h->nhalf : 1) * Mp * h->ld2D * 2);
         add("zstat_skip", (size_t)(h->nhalf > 0 ? h->nhalf : 1) * Z_MAXP * Mp * 8);
         add("zt_skip", (size_t)(h->nhalf > 0 ? h->nhalf : 1) * 2 * D * 4);
+        add("lens", 256 * sizeof(int));   // per-batch-element valid frames of a padded batch (B <= 240), behind everything else for the same reason
     }
     return off;
 }
@@ -581,7 +589,7 @@ void resolve_workspace(ezdit_handle* h) {
     p.ao = h->buf<bf16_t>("ao"); p.act = h->buf<bf16_t>("act"); p.part = h->buf<float>("part"); p.y = h->buf<float>("y");
     p.pred = h->buf<float>("pred"); p.kmask = h->buf<uint8_t>("kmask"); p.kc = h->buf<bf16_t>("kc"); p.vc = h->buf<bf16_t>("vc");
     p.mod = h->buf<float>("mod"); p.modf = h->buf<float>("modf");
-    p.zd = h->buf<float>("zd");
+    p.zd = h->buf<float>("zd"); p.lens = h->buf<int>("lens");
     p.zstat = h->buf<float2>("zstat"); p.zt_qkv = h->buf<float>("zt_qkv"); p.zt_geglu = h->buf<float>("zt_geglu"); p.zt_q2 = h->buf<float>("zt_q2");
     p.zstat_skip = h->buf<float2>("zstat_skip"); p.zt_skip = h->buf<float>("zt_skip"); p.ucat_z = h->buf<bf16_t>("ucat_z");
     if (h->is_cn) { p.cembed = h->buf<float>("cembed"); p.cnres = h->buf<float>("cnres"); p.skipbf = h->buf<bf16_t>("skipbf"); }
@@ -704,6 +712,7 @@ int ezdit_bind_workspace(ezdit_handle* h, void* ws, size_t bytes, int B, int L, 
     resolve_workspace(h);
     h->steps_done = 0;
     h->ctx_ready = h->ts_ready = h->cond_ready = false;
+    h->lens_on = false; h->lens.clear();
     drop_graph(h);
     for (ezdit_handle* u : h->cn_users) drop_graph(u);   // a graph captured with this ControlNet attached points at its old buffers
     // zero everything once: all padding rows / columns / keys stay zero for the lifetime of the binding
@@ -914,6 +923,34 @@ int ezdit_set_step(ezdit_handle* h, int step, ezdit_stream stream) {
     return EZDIT_OK;
 }
 
+int ezdit_set_lengths(ezdit_handle* h, const int32_t* lengths, int n, ezdit_stream stream) {
+    if (!h) return fail(EZDIT_E_INVALID, "null handle");
+    if (!h->ws) return fail(EZDIT_E_STATE, "bind workspace first");
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    if (cs != hipStreamCaptureStatusNone) return fail(EZDIT_E_STATE, "ezdit_set_lengths inside a stream capture (it uploads from host memory and waits)");
+    if (!lengths || n == 0) {
+        if (h->lens_on) drop_graph(h);
+        h->lens_on = false; h->lens.clear();
+        return EZDIT_OK;
+    }
+    if (h->is_cn) return fail(EZDIT_E_UNSUPPORTED, "per-sample lengths on a ControlNet handle (its condition embed has a convolution boundary of its own)");
+    if (h->cn) return fail(EZDIT_E_UNSUPPORTED, "per-sample lengths with a ControlNet attached");
+    if (n < 0 || n > h->B || h->B % n) return fail(EZDIT_E_INVALID, "%d lengths do not divide B = %d", n, h->B);
+    for (int i = 0; i < n; ++i)
+        if (lengths[i] < 1 || lengths[i] > h->L) return fail(EZDIT_E_INVALID, "lengths[%d] = %d outside [1, L = %d]", i, (int)lengths[i], h->L);
+    std::vector<int> v((size_t)h->B);
+    for (int b = 0; b < h->B; ++b) v[b] = lengths[b % n];   // the rule by which batch row b reads latent row b % x_rows
+    HIPCHK(hipStreamSynchronize(st));   // an earlier upload may still be reading the host mirror
+    h->lens = v;
+    HIPCHK(hipMemcpyAsync(h->p.lens, h->lens.data(), (size_t)h->B * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (!h->lens_on) drop_graph(h);
+    h->lens_on = true;
+    return EZDIT_OK;
+}
+
 // ------------------------------------------------------------------------------------------------------
 // cn_scale multiplies the ControlNet residuals `cn` (conditioning_scale, controlnet.py:313): the fused sampler passes the
 // attached ControlNet's scale, ezdit_forward passes 1 (the caller's residuals are already scaled, as DiTControlNet.forward returns them)
@@ -948,7 +985,7 @@ static int forward_impl(ezdit_handle* h, const float* x, int in_ch, int x_rows, 
     as.x = x; as.x_rows = x_rows; as.in_ch = in_ch;
     as.gt = gt; as.gt_mask = gt_mask; as.mask_embed = cn_mode ? h->ext_mask_embed : h->w_mask_embed;
     as.out = p.ape; as.ldo = h->ldPE;
-    as.B = h->B; as.C = h->C; as.L = h->L;
+    as.B = h->B; as.C = h->C; as.L = h->L; as.lens = h->lens_dev();
     STOPCHK();
     launch_assemble(as, st);
     c.launched("k_assemble");
@@ -1106,6 +1143,7 @@ static int forward_impl(ezdit_handle* h, const float* x, int in_ch, int x_rows, 
         at.nkh = h->opt_attn_nkh; at.xcd_map = h->opt_attn_xcd; at.wt = h->wt();
         at.out = p.ao; at.ldo = h->ldD;
         at.B = h->B; at.H = h->H; at.Lq = h->L; at.Lk = h->L; at.Lqp = h->Lp; at.Lkp = h->Lp; at.dh = h->dh;
+        at.klen = h->lens_dev();   // the reference's x_mask: keys beyond a sample's length do not exist
         STOPCHK();
         at.ts = c.stamps(); at.ts_cap = g_gemm_ts_cap;
         c.launched("k_attn (self)", launch_attention(at, st));
@@ -1162,7 +1200,7 @@ static int forward_impl(ezdit_handle* h, const float* x, int in_ch, int x_rows, 
             at.q = p.q;
             at.k = p.kc + (size_t)b * h->B * h->H * h->Lcp * h->DQK;
             at.v = p.vc + (size_t)b * h->B * h->H * h->Lcp * h->DV;
-            at.kmask = p.kmask;
+            at.kmask = p.kmask; at.klen = nullptr;   // (the key lengths are self-attention's: context keys have their own mask)
             at.Lk = h->Lc; at.Lkp = h->Lcp;
             STOPCHK();
             at.ts = c.stamps(); at.ts_cap = g_gemm_ts_cap;
@@ -1226,7 +1264,7 @@ static int forward_impl(ezdit_handle* h, const float* x, int in_ch, int x_rows, 
     FinalConvArgs fc;
     fc.y = p.y; fc.ldy = h->C;
     fc.w = h->w_fin_cw; fc.b = h->w_fin_cb;
-    fc.out = out; fc.B = h->B; fc.C = h->C; fc.L = h->L;
+    fc.out = out; fc.B = h->B; fc.C = h->C; fc.L = h->L; fc.lens = h->lens_dev();
     STOPCHK();
     launch_final_conv(fc, st);
     c.launched("k_final_conv");
@@ -1244,6 +1282,7 @@ int ezdit_forward(ezdit_handle* h, const float* x, int in_ch, int x_rows, const 
     if (in_ch == h->C && (x_rows <= 0 || h->B % x_rows)) return fail(EZDIT_E_INVALID, "x_rows %d does not divide B %d", x_rows, h->B);
     if ((gt == nullptr) != (gt_mask == nullptr)) return fail(EZDIT_E_INVALID, "gt and gt_mask must be given together");
     if (n_cn != 0 && n_cn != h->nhalf) return fail(EZDIT_E_INVALID, "n_cn %d: expected 0 or %d", n_cn, h->nhalf);
+    if (n_cn != 0 && h->lens_on) return fail(EZDIT_E_UNSUPPORTED, "ControlNet residuals with per-sample lengths (ezdit_set_lengths)");
     // the caller's residuals are already multiplied by conditioning_scale (DiTControlNet.forward returns them scaled,
     // controlnet.py:313); a scale left on the handle by the fused sampler must not be applied a second time
     return forward_impl(h, x, in_ch, x_rows, gt, gt_mask, cn_skips, n_cn, h->fwd_cn_scale, out, (hipStream_t)stream);
@@ -1338,6 +1377,9 @@ int ezdit_sampler_begin(ezdit_handle* h, float* latents, int P, const float* noi
     const int needB = guidance_scale > 0.f ? 2 * P : P;
     if (P <= 0 || needB != h->B) return fail(EZDIT_E_INVALID, "P=%d with guidance %g needs B=%d, workspace has B=%d", P, (double)guidance_scale, needB, h->B);
     if ((gt == nullptr) != (gt_mask == nullptr)) return fail(EZDIT_E_INVALID, "gt and gt_mask must be given together");
+    if (h->lens_on && needB == 2 * P)
+        for (int p = 0; p < P; ++p)
+            if (h->lens[p] != h->lens[P + p]) return fail(EZDIT_E_INVALID, "lengths of the CFG pair of sample %d differ (%d, %d)", p, h->lens[p], h->lens[P + p]);
     hipStream_t st = (hipStream_t)stream;
     std::vector<float> cf((size_t)n_steps * 8, 0.f);
     for (int i = 0; i < n_steps; ++i) {
@@ -1361,6 +1403,7 @@ static int sampler_step(ezdit_handle* h, hipStream_t st) {
     const float* cnp[64];
     int n_cn = 0;
     hipEvent_t cn_ready = nullptr;
+    if (h->cn && h->lens_on) return fail(EZDIT_E_UNSUPPORTED, "per-sample lengths with a ControlNet attached");
     if (h->cn) {  // src/inference_controlnet.py:89-99: ControlNet on the same assembled input, then the backbone with its skips
         ezdit_handle* cn = h->cn;
         if (cn->B != h->B || cn->L != h->L || cn->nhalf != h->nhalf || cn->D != h->D || !cn->ctx_ready || !cn->ts_ready || !cn->cond_ready)
@@ -1396,6 +1439,7 @@ static int sampler_step(ezdit_handle* h, hipStream_t st) {
     a.guidance_scale = h->gscale; a.guidance_rescale = h->grescale;
     a.P = h->P; a.n = h->C * h->L;
     a.step_inc = h->p.ints; a.done = reinterpret_cast<unsigned*>(h->p.ints + 8);
+    a.lens = h->lens_dev(); a.L = h->L;
     launch_cfg_ddim(a, h->p.cfgpart, st);   // its last kernel also advances the device step counter
     h->launches += (h->gscale > 0.f && h->grescale > 0.f) ? 2 : 1;
     const hipError_t e = hipGetLastError();
@@ -1415,6 +1459,7 @@ int ezdit_cfg_ddim_step(const float* pred, float* latents, const float* noise, c
     a.guidance_scale = guidance_scale; a.guidance_rescale = guidance_rescale;
     a.P = P; a.n = n;
     a.step_inc = nullptr; a.done = nullptr;
+    a.lens = nullptr; a.L = n;
     launch_cfg_ddim(a, scratch, (hipStream_t)stream);
     return EZDIT_OK;
 }
@@ -1638,6 +1683,54 @@ int ezdit_test_attention(ezdit_handle* h, const void* q, const void* k, const vo
     if (launch_attention(a, (hipStream_t)stream)) return fail(EZDIT_E_UNSUPPORTED, "attention configuration not supported");
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of k_attn failed: %s", hipGetErrorString(e));
+    return EZDIT_OK;
+}
+
+int ezdit_test_attention_varlen(ezdit_handle* h, const void* q, const void* k, const void* v, const uint8_t* kmask, void* out, int B,
+                                int Lq, int Lk, int Lqp, int Lkp, const int32_t* dev_klen, ezdit_stream stream) {
+    if (!h) return fail(EZDIT_E_INVALID, "null handle");
+    if (B <= 0 || Lq <= 0 || Lk <= 0 || Lqp < Lq || Lkp < Lk) return fail(EZDIT_E_INVALID, "bad shape");
+    if (dev_klen) {   // a test hook may wait: the lengths bound what the kernel reads and which rows it zeroes
+        if (Lq != Lk) return fail(EZDIT_E_INVALID, "per-batch-element lengths are a self-attention form: Lq %d != Lk %d", Lq, Lk);
+        std::vector<int> kl((size_t)B);
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+        HIPCHK(hipMemcpy(kl.data(), dev_klen, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; ++b)
+            if (kl[b] < 1 || kl[b] > Lk) return fail(EZDIT_E_INVALID, "klen[%d] = %d outside [1, Lk = %d]", b, kl[b], Lk);
+    }
+    AttnArgs a;
+    memset(&a, 0, sizeof a);
+    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.kmask = kmask;
+    a.nkh = h->opt_attn_nkh; a.xcd_map = h->opt_attn_xcd;
+    a.out = (bf16_t*)out; a.ldo = h->ldD;
+    a.B = B; a.H = h->H; a.Lq = Lq; a.Lk = Lk; a.Lqp = Lqp; a.Lkp = Lkp; a.dh = h->dh;
+    a.klen = dev_klen;
+    (void)hipGetLastError();
+    if (launch_attention(a, (hipStream_t)stream)) return fail(EZDIT_E_UNSUPPORTED, "attention configuration not supported");
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of k_attn failed: %s", hipGetErrorString(e));
+    return EZDIT_OK;
+}
+
+int ezdit_test_final_conv(const float* y, int ldy, const float* w, const float* b, float* out, int B, int C, int L, const int32_t* dev_lens,
+                          ezdit_stream stream) {
+    if (!y || !w || !b || !out) return fail(EZDIT_E_INVALID, "null argument");
+    if (B <= 0 || L <= 0 || C <= 0 || ldy < C) return fail(EZDIT_E_INVALID, "bad shape B=%d C=%d L=%d ldy=%d", B, C, L, ldy);
+    // (the kernel's two-halves walk of a weight row needs C % 8 == 0; every shipped model has C = 128)
+    if (C % 8) return fail(EZDIT_E_UNSUPPORTED, "C = %d is not a multiple of 8", C);
+    if (dev_lens) {
+        std::vector<int> ln((size_t)B);
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+        HIPCHK(hipMemcpy(ln.data(), dev_lens, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
+        for (int i = 0; i < B; ++i)
+            if (ln[i] < 1 || ln[i] > L) return fail(EZDIT_E_INVALID, "lens[%d] = %d outside [1, L = %d]", i, ln[i], L);
+    }
+    FinalConvArgs fc;
+    fc.y = y; fc.ldy = ldy; fc.w = w; fc.b = b; fc.out = out; fc.B = B; fc.C = C; fc.L = L; fc.lens = dev_lens;
+    (void)hipGetLastError();
+    launch_final_conv(fc, (hipStream_t)stream);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of k_final_conv failed: %s", hipGetErrorString(e));
     return EZDIT_OK;
 }
 

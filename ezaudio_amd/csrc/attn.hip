@@ -97,7 +97,7 @@ __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
     int Lq_ = a.Lq;
     asm("" : "+s"(Lq_) : "s"(a.q), "s"(a.k), "s"(a.v), "s"(a.kmask), "s"(a.out), "s"(a.ldo), "s"(a.B), "s"(a.H), "s"(a.Lk), "s"(a.Lqp), "s"(a.Lkp), "s"(a.xu), "s"(a.ldu),
         "s"(a.xw), "s"(a.ldw), "s"(a.xw_rows), "s"(a.xK), "s"(a.xcd_map), "s"(a.nq), "s"(a.ppx), "s"(a.mnq), "s"(a.mH), "s"(a.q_raw), "s"(a.ts), "s"(a.xk2), "s"(a.zstat_in),
-        "s"(a.zs_stride), "s"(a.zparts));
+        "s"(a.zs_stride), "s"(a.zparts), "s"(a.klen));
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
@@ -120,6 +120,23 @@ __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
     }
     const int q0 = qt * QT + qs * 32;
     const long bh = (long)b * a.H + h;
+    // keys (and, in self-attention over a padded batch, queries) of this batch element: AttnArgs.klen, one scalar load, wave-uniform
+    int Lk = a.Lk;
+    if constexpr (!ZQ) {
+        if (a.klen) {
+            Lk = __builtin_amdgcn_readfirstlane(a.klen[b]);
+            if (qt * QT >= Lk) {
+                // the whole query tile lies beyond this batch element's length: its rows are padding.  They must still be FINITE for everything downstream
+                // (a masked key goes through the next block's P . V with P = 0, and 0 * NaN = NaN): store zeros, then leave -- the whole workgroup, before any barrier
+                for (int i = tid; i < QT * (DH / 4); i += NT) {
+                    const int r = i / (DH / 4), g = i - r * (DH / 4);
+                    if (qt * QT + r < a.Lq)
+                        *reinterpret_cast<uint2*>(a.out + ((long)b * a.Lq + qt * QT + r) * a.ldo + h * DH + 4 * g) = make_uint2(0u, 0u);
+                }
+                return;
+            }
+        }
+    }
     unsigned long long* ts = (a.ts && tid < 64) ? a.ts + 8 * (long)blockIdx.x : nullptr;
     if (ts && lane == 0) { ts[0] = __builtin_readcyclecounter(); ts[6] = ez_stamp_start(); }   // [6], [7]: 100 MHz device-wide clock
 
@@ -493,7 +510,7 @@ __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
     // step for it evens the pair out (MI355X_MICROARCH.md "Two waves per SIMD").  The guard must be provably wave-uniform: s_setprio
     // ignores EXEC.
     if (NKH == 4 && __builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
-    const int ntiles = (a.Lk + TK - 1) / TK;
+    const int ntiles = (Lk + TK - 1) / TK;
     LOAD_TILE(0);
     WRITE_TILE(0);
     __syncthreads();
@@ -504,11 +521,11 @@ __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
         const char* vb = kb + KBYTES;
         const char* vtr = vb + (32 * kh + 4 * hi + ((lane & 15) >> 2)) * VSTR + ((lane & 16) + 4 * (lane & 3)) * 2;   // this lane's corner of the transposing reads
         const int key0 = t * TK + kh * 32;
-        if (active && key0 < a.Lk) {  // wave-uniform: the whole 32-key sub-tile may lie beyond Lk (32-query tiles: waves 4 - 7 only stage)
+        if (active && key0 < Lk) {  // wave-uniform: the whole 32-key sub-tile may lie beyond Lk (32-query tiles: waves 4 - 7 only stage)
             // validity of this wave's 32 keys as one bit mask (bit j <-> key0 + j), built BEFORE the MFMAs
             const int kidx = key0 + r32;
-            bool kv = kidx < a.Lk;
-            if (km) kv = kv && (km[kidx < a.Lk ? kidx : 0] != 0);
+            bool kv = kidx < Lk;
+            if (km) kv = kv && (km[kidx < Lk ? kidx : 0] != 0);
             const uint32_t ball = (uint32_t)__ballot(kv);               // lanes 0..31 fill bits 0..31
             const uint32_t tmask = ball >> (4 * hi);
             // wave-uniform: no key of this sub-tile is masked or beyond Lk (every self-attention tile but the last).  The loop is bound
@@ -661,6 +678,9 @@ __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
                 uint2 v;
                 v.x = pack_bf2(acc.x, acc.y);
                 v.y = pack_bf2(acc.z, acc.w);
+                if constexpr (!ZQ) {
+                    if (a.klen && qrow >= Lk) v = make_uint2(0u, 0u);   // a padding query row of a tile that straddles the length
+                }
                 if (a.wt) st8_wt(orow + 8 * G, v); else *reinterpret_cast<uint2*>(orow + 8 * G) = v;
             }
         }
@@ -686,6 +706,7 @@ int launch_attention(const AttnArgs& a0, hipStream_t st) {
         if (a.q_raw) a.q_raw += b0 * a.Lq * a.ld_qraw;
         if (a.xu) a.xu += b0 * a.Lq * a.ldu;
         if (a.zstat_in) a.zstat_in += b0 * a.Lq;
+        if (a.klen) a.klen += b0;
         a.b0 = 0;
     }
     const long nwg64 = (long)((a.Lq + 63) / 64) * a.H * a.B;
@@ -694,6 +715,7 @@ int launch_attention(const AttnArgs& a0, hipStream_t st) {
     if (a.Lkp % 128) nkh = 2;
     if (a.xu && nkh != 4) return 1;   // the fused projection exists in the 8-wave form only (needs Lkp % 128 == 0)
     if (a.dh != 64 && a.dh != 72) return 1;
+    if (a.klen && (a.xu || a.q_raw || a.Lq != a.Lk)) return 1;   // per-batch-element lengths: plain self-attention only
     const bool zq = a.xu && a.zstat_in;
     if (zq && !(a.zG && a.zC && a.zparts > 0 && a.zparts <= Z_MAXP && a.zs_stride > 0 && a.zw > 0)) return 1;
     // 32-query tiles (fused projection with the LayerNorm algebra, an even number of K tiles): when the 64-row grid leaves half the CUs without a workgroup

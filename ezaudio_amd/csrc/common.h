@@ -297,6 +297,11 @@ struct AttnArgs {
     // advanced by the launcher).  Cross-attention of a CFG step runs over the conditional rows only: an uncond row's mask has ONE valid key, its
     // output is a constant that the attention-out projection adds (GemmArgs.zd)
     int b0;
+    // self-attention over a padded batch (null = every batch element has Lk keys and Lq queries): klen [B] (device), 1 <= klen[b] <= Lk.  Batch element b has the
+    // keys AND queries [0, klen[b]): its workgroups run ceil(klen[b] / tile) key tiles, query rows >= klen[b] are stored as zeros (a query tile wholly beyond
+    // klen[b] stores zeros and leaves).  Read at run time: one captured graph serves every set of lengths.  Not for the forms with a query prologue (q_raw, xu).
+    // At the END of the struct: the offsets of everything above stay what they were
+    const int* klen;
 };
 int launch_attention(const AttnArgs& a, hipStream_t st);   // 0 = launched, nonzero = configuration not supported
 
@@ -309,6 +314,7 @@ struct AssembleArgs {
     const float* gt; const uint8_t* gt_mask; const float* mask_embed;
     bf16_t* out; int ldo;  // [B*L][ldo], zero padded
     int B, C, L;
+    const int* lens;       // nullable [B] (device): frames >= lens[b] of batch element b are assembled as zero rows whatever x / gt / gt_mask hold there
 };
 void launch_assemble(const AssembleArgs& a, hipStream_t st);
 
@@ -317,6 +323,8 @@ struct FinalConvArgs {
     const float* w; const float* b;  // [C][C][3], [C]
     float* out;               // [B][C][L]
     int B, C, L;
+    const int* lens;          // nullable [B] (device): batch element b ends at frame lens[b] -- inputs at frames >= lens[b] read as zero (the convolution's own
+                              // zero padding moves there), outputs at frames >= lens[b] are written as zero
 };
 void launch_final_conv(const FinalConvArgs& a, hipStream_t st);
 
@@ -355,6 +363,9 @@ struct CfgDdimArgs {
     // fused sampler: the LAST workgroup to finish (arrival counter `done`, zero between launches) advances the device step
     // counter, so the step needs no separate single-thread launch.  Both null: stand-alone operator.
     int* step_inc; unsigned* done;
+    // padded batch (null lens = every sample has n elements): sample p is valid on frames [0, lens[p]) of its L (n = C * L): the rescale statistics run over
+    // the C * lens[p] valid elements, frames >= lens[p] of the latents are written as zero whatever pred / noise / latents hold there
+    const int* lens; int L;
 };
 void launch_cfg_ddim(const CfgDdimArgs& a, float* partial /* [P][64][4] scratch */, hipStream_t st);
 void launch_set_int(int* p, int v, int add, hipStream_t st);  // *p = add ? *p + v : v

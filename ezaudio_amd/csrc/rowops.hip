@@ -257,7 +257,9 @@ __global__ __launch_bounds__(256) void k_assemble(AssembleArgs a) {
     const int b = m / a.L, l = m % a.L;
     const int C = a.C;
     float v = 0.f;
-    if (a.in_ch == C) {
+    if (a.lens && l >= a.lens[b]) {
+        // a padded frame of this batch element: a zero row, whatever the caller left there (nothing non-finite may enter the step)
+    } else if (a.in_ch == C) {
         const int xb = b % a.x_rows;
         if (c < C) {
             v = a.x[((long)xb * C + c) * a.L + l];
@@ -290,13 +292,22 @@ __global__ __launch_bounds__(256) void k_final_conv(FinalConvArgs a) {
     const int ltiles = (a.L + TL - 1) / TL;
     const int b = blockIdx.x / ltiles;
     const int l0 = (blockIdx.x % ltiles) * TL;
+    // frames of this batch element (FinalConvArgs.lens; wave-uniform): the convolution's zero padding starts at Lb, outputs from Lb on are zero
+    const int Lb = a.lens ? __builtin_amdgcn_readfirstlane(a.lens[b]) : a.L;
+    if (l0 >= Lb) {   // (only with lens) a tile of padding: zeros, the whole workgroup leaves before any barrier
+        for (int i = threadIdx.x; i < C * TL; i += 256) {
+            const int co = i / TL, l = l0 + i % TL;
+            if (l < a.L) a.out[((long)b * C + co) * a.L + l] = 0.f;
+        }
+        return;
+    }
     bool staged = false;
     auto stage = [&]() {   // the TL + 2 input rows of this tile -> LDS.  Called BEHIND the first weight block's requests: one round trip instead of two in front of the first FMA
         if (staged) return;
         for (int i = threadIdx.x; i < (TL + 2) * C; i += 256) {
             const int r = i / C, ci = i % C;
             const int l = l0 + r - 1;
-            sy[r * C + ci] = (l >= 0 && l < a.L) ? a.y[((long)b * a.L + l) * a.ldy + ci] : 0.f;
+            sy[r * C + ci] = (l >= 0 && l < Lb) ? a.y[((long)b * a.L + l) * a.ldy + ci] : 0.f;
         }
         __syncthreads();
         staged = true;
@@ -356,7 +367,12 @@ __global__ __launch_bounds__(256) void k_final_conv(FinalConvArgs a) {
         if (half == 0 && co_ok) {
             const float4 o = *reinterpret_cast<const float4*>(red + co * TL);
             const float bb = a.b[co];
-            const float4 v = make_float4((acc[0] + o.x) + bb, (acc[1] + o.y) + bb, (acc[2] + o.z) + bb, (acc[3] + o.w) + bb);
+            float4 v = make_float4((acc[0] + o.x) + bb, (acc[1] + o.y) + bb, (acc[2] + o.z) + bb, (acc[3] + o.w) + bb);
+            if (l0 + TL > Lb) {   // (only with lens: Lb <= L, and the stores below are bounded by L) the tile straddles the end of the sample
+                if (l0 + 1 >= Lb) v.y = 0.f;
+                if (l0 + 2 >= Lb) v.z = 0.f;
+                if (l0 + 3 >= Lb) v.w = 0.f;
+            }
             float* dst = a.out + ((long)b * C + co) * a.L + l0;
             if (l0 + TL <= a.L && (a.L & 3) == 0) {
                 *reinterpret_cast<float4*>(dst) = v;
@@ -466,7 +482,9 @@ __global__ __launch_bounds__(256) void k_cfg_stats(CfgDdimArgs a, float* partial
     const float* pu = a.pred + (long)(a.P + p) * n;
     const float gs = a.guidance_scale;
     float s1 = 0.f, q1 = 0.f, s2 = 0.f, q2 = 0.f;
+    const int len = a.lens ? a.lens[p] : 0;
     for (int i = blk * 256 + threadIdx.x; i < n; i += CFG_NB * 256) {
+        if (a.lens && i % a.L >= len) continue;   // padded frame: not part of the sample
         const float c = pc[i], u = pu[i];
         const float g = u + gs * (c - u);
         s1 += c; q1 += c * c; s2 += g; q2 += g * g;
@@ -499,8 +517,10 @@ __global__ __launch_bounds__(256) void k_cfg_apply(CfgDdimArgs a, const float* p
             const float4 o = part_l[i];
             s1 += o.x; q1 += o.y; s2 += o.z; q2 += o.w;
         }
-        const double v1 = (q1 - s1 * s1 / n) / (n - 1);  // torch.std default: unbiased
-        const double v2 = (q2 - s2 * s2 / n) / (n - 1);
+        // elements of the sample: all n, or the C * lens[p] valid ones of a padded batch (n = C L)
+        const int nv = a.lens ? (n / a.L) * a.lens[p] : n;
+        const double v1 = (q1 - s1 * s1 / nv) / (nv - 1);  // torch.std default: unbiased
+        const double v2 = (q2 - s2 * s2 / nv) / (nv - 1);
         ratio = (float)(sqrt(v1) / sqrt(v2));
     }
     const float* pc = a.pred + (long)p * n;
@@ -508,7 +528,9 @@ __global__ __launch_bounds__(256) void k_cfg_apply(CfgDdimArgs a, const float* p
     float* lat = a.latents + (long)p * n;
     const float* z = a.noise ? a.noise + ((long)step * a.P + p) * n : nullptr;
     const float gs = a.guidance_scale, phi = a.guidance_rescale;
+    const int len = a.lens ? a.lens[p] : 0;
     for (int i = blk * 256 + threadIdx.x; i < n; i += CFG_NB * 256) {
+        if (a.lens && i % a.L >= len) { lat[i] = 0.f; continue; }   // padded frame: zero, whatever pred / noise / the latents hold there
         float v = pc[i];
         if (cfg) {
             const float u = pu[i];

@@ -23,6 +23,12 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+_X_MASK_MSG = ('x_mask is not implemented: a prefix mask (sample b valid on the frames [0, len_b) of a padded batch) is spelled '
+               'x_lens=[len_0, ...].  It differs from the reference\'s x_mask (the self-attention key mask, src/models/blocks.py:143) '
+               'by the boundary of the final Conv1d, which sees a zero at frame len_b -- each sample comes out as if run alone at its '
+               'own length.  General (non-prefix) masks are out of scope')
+
+
 class _UDiTView:
     """``unet.model(x=x257, timesteps=..., context=..., context_mask=..., cls_token=None, controlnet_skips=...)``
     as called by src/inference_controlnet.py:97-99."""
@@ -31,6 +37,8 @@ class _UDiTView:
         self._o = owner
 
     def __call__(self, x, timesteps, context, x_mask=None, context_mask=None, cls_token=None, controlnet_skips=None):
+        if x_mask is not None:
+            raise NotImplementedError(_X_MASK_MSG)
         return self._o._run(x, timesteps, context, context_mask, None, None, controlnet_skips, in_ch=x.shape[1])
 
 
@@ -106,6 +114,17 @@ class MaskDiT:
         mask = None if context_mask is None else context_mask.to(self.device).to(torch.uint8).contiguous()
         _lib.check(self.lib.ezdit_prepare_context(self._h, _ptr(context), _ptr(mask), _stream()))
 
+    def set_lengths(self, lengths, stream=None):
+        """Per-sample valid frames of the padded batch bound last (ezdit_set_lengths): a list / int tensor whose size divides B, row b uses
+        lengths[b % n].  None clears.  The binding is cached across calls, so every caller sets or clears explicitly."""
+        st = _stream() if stream is None else stream
+        if lengths is None:
+            _lib.check(self.lib.ezdit_set_lengths(self._h, None, 0, st))
+            return
+        vals = [int(v) for v in (lengths.reshape(-1).tolist() if torch.is_tensor(lengths) else lengths)]
+        arr = (C.c_int32 * len(vals))(*vals)
+        _lib.check(self.lib.ezdit_set_lengths(self._h, arr, len(vals), st))
+
     def prepare_timesteps(self, ts, per_row):
         arr = (C.c_int32 * len(ts))(*[int(t) for t in ts])
         _lib.check(self.lib.ezdit_prepare_timesteps(self._h, arr, len(ts), 1 if per_row else 0, _stream()))
@@ -119,7 +138,7 @@ class MaskDiT:
         return t if shape is None else t[:int(np.prod(shape))].reshape(shape)
 
     # -- forward ------------------------------------------------------------------------------------
-    def _run(self, x, timesteps, context, context_mask, gt, gt_mask, controlnet_skips, in_ch):
+    def _run(self, x, timesteps, context, context_mask, gt, gt_mask, controlnet_skips, in_ch, x_lens=None):
         B, _, L = x.shape
         Lc = context.shape[1]
         if context.shape[0] != B:
@@ -132,6 +151,7 @@ class MaskDiT:
         self.bind(B, L, Lc, max(len(t_list), 1))
         self.prepare_context(context, context_mask)
         self.prepare_timesteps(t_list, per_row)
+        self.set_lengths(x_lens)
         x = x.to(self.device, torch.float32).contiguous()
         gt_d = None if gt is None else gt.to(self.device, torch.float32).contiguous()
         gm_d = None if gt_mask is None else gt_mask.to(self.device).expand(B, self.C, L).to(torch.uint8).contiguous()
@@ -147,9 +167,14 @@ class MaskDiT:
         return out
 
     def forward(self, x, timesteps, context, x_mask=None, context_mask=None, cls_token=None, gt=None,
-                mae_mask_infer=None, forward_model=True):
-        if x_mask is not None or cls_token is not None:
-            raise NotImplementedError('x_mask / cls_token are not used by the shipped configs')
+                mae_mask_infer=None, forward_model=True, x_lens=None):
+        """``x_lens`` (list / int tensor [B]): x, gt and mae_mask_infer are padded to L = max(x_lens) frames, row b is valid on [0, x_lens[b]); its
+        valid output frames are what a call with that row alone computes, output frames beyond are exactly 0, and whatever the padded
+        region of the inputs holds is ignored (include/ezdit.h ezdit_set_lengths)."""
+        if x_mask is not None:
+            raise NotImplementedError(_X_MASK_MSG)
+        if cls_token is not None:
+            raise NotImplementedError('cls_token is not used by the shipped configs')
         if gt is not None and mae_mask_infer is None:
             raise NotImplementedError('training-time random span masking is out of scope (pass mae_mask_infer)')
         mae_mask = torch.ones_like(x) if gt is None else mae_mask_infer.expand_as(gt).type_as(gt)
@@ -157,7 +182,7 @@ class MaskDiT:
             me = self._mask_embed.view(1, -1, 1).to(x.device).expand_as(x)
             g = me if gt is None else torch.where(mae_mask_infer.expand_as(gt), me, gt)
             return torch.cat([x, g, mae_mask[:, 0:1, :]], dim=1), mae_mask
-        pred = self._run(x, timesteps, context, context_mask, gt, mae_mask_infer, None, in_ch=self.C)
+        pred = self._run(x, timesteps, context, context_mask, gt, mae_mask_infer, None, in_ch=self.C, x_lens=x_lens)
         return pred, mae_mask
 
     __call__ = forward

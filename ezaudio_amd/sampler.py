@@ -30,10 +30,19 @@ class LatentSampler:
 
     def prepare(self, text, text_mask, uncond_text, uncond_mask, init_noise, step_noises, guidance_scale,
                 guidance_rescale, ddim_steps, eta, gt=None, gt_mask=None, controlnet=None, condition=None,
-                conditioning_scale=1.0):
+                conditioning_scale=1.0, lengths=None):
+        """``lengths`` (list of P ints): init_noise / step_noises / gt / gt_mask are padded to L = max(lengths) frames and sample p is valid on
+        [0, lengths[p]) -- its final latent is what a call with that sample alone at its own length gives, zero beyond (include/ezdit.h
+        ezdit_set_lengths).  Not with a ControlNet."""
         u = self.unet
         dev = u.device
         P, Cc, L = init_noise.shape
+        if lengths is not None:
+            lengths = [int(v) for v in lengths]
+            if len(lengths) != P:
+                raise ValueError(f'{len(lengths)} lengths for P={P} samples')
+            if controlnet is not None:
+                raise NotImplementedError('per-sample lengths with a ControlNet are not implemented')
         self.scheduler.set_timesteps(ddim_steps)
         ts = [int(t) for t in self.scheduler.timesteps]
         coefs = self.scheduler.ddim_coefficients(eta)
@@ -72,6 +81,7 @@ class LatentSampler:
             _lib.check(u.lib.ezdit_sampler_attach_controlnet(u._h, controlnet._h if controlnet is not None else None,
                                                              float(conditioning_scale)))
             self.controlnet = controlnet
+            u.set_lengths(lengths, C.c_void_p(self.stream.cuda_stream))   # (always: the binding is cached, None clears an earlier call's)
             arr = (_lib.EzditDdimCoef * ddim_steps)(*[_lib.EzditDdimCoef(*c) for c in coefs])
             _lib.check(u.lib.ezdit_sampler_begin(u._h, _ptr(self.latents), P, _ptr(self.noise), arr, ddim_steps,
                                                  float(guidance_scale or 0.0), float(guidance_rescale or 0.0),
@@ -104,11 +114,37 @@ class LatentSampler:
         return self.latents
 
 
+def _frames_list(audio_frames, n_prompts):
+    """audio_frames as one length per prompt, or None for the scalar form."""
+    if isinstance(audio_frames, (list, tuple)) or (torch.is_tensor(audio_frames) and audio_frames.dim() > 0):
+        lens = [int(v) for v in audio_frames]
+        if len(lens) != n_prompts:
+            raise ValueError(f'{len(lens)} lengths for {n_prompts} prompts')
+        if min(lens) < 1:
+            raise ValueError(f'lengths must be positive: {lens}')
+        return lens
+    return None
+
+
 def draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n_prompts=1, first_index=0):
     """Init noise + per-step DDIM noise in the order the reference draws them from ONE generator
     (src/inference.py:58-67 then one randn per scheduler.step, diffusers `randn_tensor`).  For several
     prompts each sample gets its own generator seeded seed + index, so results do not depend on how
-    prompts are sharded over GPUs."""
+    prompts are sharded over GPUs.
+
+    ``audio_frames`` may be a list with one length per prompt: sample i then draws (1, C, len_i) tensors -- the numbers a call with
+    that sample alone draws -- which are placed into zero-padded [.., max(lengths)] tensors."""
+    lens = _frames_list(audio_frames, n_prompts)
+    if lens is not None:
+        Lmax = max(lens)
+        init = torch.zeros((n_prompts, codec_dim, Lmax), device=device)
+        step = torch.zeros((ddim_steps, n_prompts, codec_dim, Lmax), device=device) if eta > 0 else None
+        for i, li in enumerate(lens):
+            ini, st = draw_noises(codec_dim, li, ddim_steps, eta, random_seed, device, 1, first_index + i)
+            init[i:i + 1, :, :li] = ini
+            if st is not None:
+                step[:, i:i + 1, :, :li] = st
+        return init, step
     inits, steps = [], []
     for i in range(n_prompts):
         g = torch.Generator(device=device)
@@ -144,25 +180,43 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
     """Same signature and semantics as the reference's ``inference`` (src/inference.py:26-107).
 
     Extension: with ``torch.distributed`` initialised and several prompts, every rank samples AND
-    VAE-decodes its own contiguous shard of the prompts and the waveforms are all-gathered once (RCCL)."""
+    VAE-decodes its own contiguous shard of the prompts and the waveforms are all-gathered once (RCCL).
+
+    Extension: ``audio_frames`` may be a list with one latent length per prompt (mixed-length batch).  gt / gt_mask are then padded to
+    max(audio_frames) frames; a prompt WITHOUT a reference clip in a batch that has some carries gt_mask all ones (that is the
+    reference's no-gt input, src/models/conditioners.py:173-176).  The VAE decodes every sample at its own length (its convolutions have
+    boundaries too); the result is [N, 1, Tmax], zero beyond each sample's own duration."""
     if neg_text is None:
         neg_text = [""]
     if isinstance(text_raw, str):
         text_raw = [text_raw]
     import torch.distributed as dist
+    frames = _frames_list(audio_frames, len(text_raw))
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and len(text_raw) > 1 and first_index is None:
         from .dist import sample_sharded
         n_all = len(text_raw)
+        ratio_ = params['autoencoder']['sr'] // params['autoencoder']['latent_sr']
+        t_all = (max(frames) if frames is not None else audio_frames) * ratio_   # every shard is gathered at the GLOBAL duration
         neg_all = list(neg_text) * n_all if len(neg_text) == 1 else list(neg_text)
 
         def local(s, e):
             if e == s:   # more ranks than prompts: contribute an empty shard of the common shape
                 ratio = params['autoencoder']['sr'] // params['autoencoder']['latent_sr']
-                return torch.zeros(0, 1, audio_frames * ratio, device=device)
+                return torch.zeros(0, 1, t_all if frames is not None else audio_frames * ratio, device=device)
             sl = lambda t: t if t is None or t.shape[0] == 1 else t[s:e]   # noqa: E731  per-prompt tensors are sliced
-            return inference(autoencoder, unet, sl(gt), sl(gt_mask), tokenizer, text_encoder, params, noise_scheduler,
-                             list(text_raw[s:e]), neg_all[s:e], audio_frames, guidance_scale, guidance_rescale, ddim_steps, eta,
-                             random_seed, device, use_graph, controlnet, sl(condition), conditioning_scale, first_index=s)
+            if frames is None:
+                return inference(autoencoder, unet, sl(gt), sl(gt_mask), tokenizer, text_encoder, params, noise_scheduler,
+                                 list(text_raw[s:e]), neg_all[s:e], audio_frames, guidance_scale, guidance_rescale, ddim_steps, eta,
+                                 random_seed, device, use_graph, controlnet, sl(condition), conditioning_scale, first_index=s)
+            # mixed lengths: the lengths are sliced with the prompts, per-prompt tensors additionally cut to the shard's own padded length
+            lmax = max(frames[s:e])
+            cut = lambda t: t if t is None else sl(t)[..., :lmax]   # noqa: E731
+            wav = inference(autoencoder, unet, cut(gt), cut(gt_mask), tokenizer, text_encoder, params, noise_scheduler,
+                            list(text_raw[s:e]), neg_all[s:e], frames[s:e], guidance_scale, guidance_rescale, ddim_steps, eta,
+                            random_seed, device, use_graph, controlnet, sl(condition), conditioning_scale, first_index=s)
+            out = torch.zeros(wav.shape[0], wav.shape[1], t_all, dtype=wav.dtype, device=wav.device)
+            out[..., :wav.shape[-1]] = wav
+            return out
         return sample_sharded(local, n_all)
     first_index = first_index or 0
     n_prompts = len(text_raw)
@@ -181,13 +235,22 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
     unet.eval()
     init, step_noises = draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n_prompts, first_index)
     smp = LatentSampler(unet, noise_scheduler)
+    # equal lengths are the unpadded batch (the same bits; include/ezdit.h ezdit_set_lengths): the length table is for ragged batches only
+    ragged = frames is not None and len(set(frames)) > 1
+    kw = dict(lengths=frames) if ragged else {}
     smp.prepare(text.float(), text_mask, uncond_text.float(), uncond_mask, init, step_noises, guidance_scale,
                 guidance_rescale, ddim_steps, eta, gt=gt, gt_mask=gt_mask, controlnet=controlnet, condition=condition,
-                conditioning_scale=conditioning_scale)
+                conditioning_scale=conditioning_scale, **kw)
     smp.run(use_graph=use_graph)
     latents = smp.finish()
     pred = scale_shift_re(latents, params['autoencoder']['scale'], params['autoencoder']['shift'])
     if gt is not None:   # src/inference.py:103-104, with a shared [1, C, L] reference broadcast over the prompts
         keep = ~gt_mask.to(pred.device).expand_as(pred)
         pred = torch.where(keep, gt.to(pred.device, pred.dtype).expand_as(pred), pred)
-    return autoencoder(embedding=pred)
+    if not ragged:
+        return autoencoder(embedding=pred)
+    wavs = [autoencoder(embedding=pred[i:i + 1, :, :li]) for i, li in enumerate(frames)]   # each sample at its own length
+    out = torch.zeros(n_prompts, wavs[0].shape[1], max(w.shape[-1] for w in wavs), dtype=wavs[0].dtype, device=wavs[0].device)
+    for i, w in enumerate(wavs):
+        out[i:i + 1, :, :w.shape[-1]] = w
+    return out

@@ -124,6 +124,25 @@ int ezdit_prepare_context(ezdit_handle* h, const float* dev_ctx, const uint8_t* 
 int ezdit_prepare_timesteps(ezdit_handle* h, const int32_t* timesteps, int n, int per_row, ezdit_stream stream);
 int ezdit_set_step(ezdit_handle* h, int step, ezdit_stream stream);
 
+/* ---- mixed-length batches: per-sample valid lengths of a PADDED batch -------------------------- */
+/* The batch is stored padded to L frames (x / gt / gt_mask / noise / latents [.., C, L], token rows B * L); batch row b is valid on
+ * the frames [0, lengths[b % n]) -- the rule by which row b reads latent row b % x_rows, so n = P serves a CFG batch of 2 P rows.
+ * `lengths` is a HOST array, 1 <= lengths[i] <= L, n divides B; NULL or n = 0 clears (every row has L frames again, bit for bit the
+ * behaviour without this call; all lengths equal to L give those bits as well).  With lengths set, the valid frames of a row are what
+ * a call with that row alone at its own length computes (up to rounding): self-attention sees the keys [0, len) only (the
+ * reference's `x_mask`, src/models/blocks.py:143), the FinalBlock's Conv1d sees a zero at frame len (which `x_mask` does NOT give),
+ * `rescale_noise_cfg` takes mean / std over the C * len valid elements, and the input assembly substitutes zeros for padded frames:
+ * what the caller leaves there -- NaN included -- is ignored.  Frames >= len of ezdit_forward's output and of the sampler's latents
+ * are written as exactly 0.  Padded token rows are still computed (and discarded) by the per-row kernels.
+ * The table lives in the workspace and is read by the kernels at run time: a captured step graph serves every set of lengths of the
+ * bound (B, L).  A set-up entry point like ezdit_prepare_* / ezdit_sampler_begin: it uploads from host memory and waits for `stream`;
+ * refused with EZDIT_E_STATE inside a stream capture and before a workspace is bound.  ezdit_bind_workspace clears the lengths.
+ * EZDIT_E_INVALID: a length outside [1, L], n not dividing B.  EZDIT_E_UNSUPPORTED: a ControlNet handle, a backbone with a ControlNet
+ * attached; ezdit_forward with cn_skips and ezdit_sampler_run with an attached ControlNet refuse likewise while lengths are set (the
+ * condition embed's stride-2 convolutions have a boundary of their own).  ezdit_sampler_begin checks that both rows of a CFG pair
+ * have the same length. */
+int ezdit_set_lengths(ezdit_handle* h, const int32_t* lengths, int n, ezdit_stream stream);
+
 /* ---- the denoiser operator: MaskDiT.forward / UDiT.forward ----------------------------------- */
 /* src/models/conditioners.py:156-183 (in_ch = C: x [x_rows,C,L], optional gt/gt_mask [x_rows,C,L];
  * batch row b reads latent row b % x_rows, which is how the CFG pair shares one latent,
@@ -257,6 +276,15 @@ int ezdit_debug_gemm_timestamps(void* dev_buf, long capacity_workgroups);
 int ezdit_test_attention(ezdit_handle* h, const void* dev_q, const void* dev_k, const void* dev_v,
                          const uint8_t* dev_kmask, void* dev_out, int B, int Lq, int Lk, int Lqp, int Lkp,
                          ezdit_stream stream);
+/* ezdit_test_attention over a padded batch (csrc/common.h AttnArgs.klen; Lq == Lk): dev_klen int32 [B] on the DEVICE, 1 <= klen[b] <= Lk (checked: the hook
+ * waits for `stream` and reads it back), NULL = ezdit_test_attention.  Batch element b attends to the keys [0, klen[b]); its query rows >= klen[b] come back as zeros. */
+int ezdit_test_attention_varlen(ezdit_handle* h, const void* dev_q, const void* dev_k, const void* dev_v,
+                                const uint8_t* dev_kmask, void* dev_out, int B, int Lq, int Lk, int Lqp, int Lkp,
+                                const int32_t* dev_klen, ezdit_stream stream);
+/* unit-test hook of the FinalBlock's Conv1d(C, C, 3, pad 1) (k_final_conv; C % 8 == 0): y fp32 [B * L][ldy] token-major, w fp32 [C][C][3], b fp32 [C] -> out fp32 [B][C][L].
+ * dev_lens int32 [B] on the DEVICE or NULL: inputs at frames >= lens[b] read as zero, outputs at frames >= lens[b] are written as zero (checked as above). */
+int ezdit_test_final_conv(const float* dev_y, int ldy, const float* dev_w, const float* dev_b, float* dev_out, int B, int C, int L,
+                          const int32_t* dev_lens, ezdit_stream stream);
 /* copy an internal fp32/bf16 buffer (by name, e.g. "h", "u", "q", "k", "v", "mod") for debugging. */
 int ezdit_debug_buffer(ezdit_handle* h, const char* name, void** dev_ptr, size_t* bytes);
 /* number of kernel launches issued by the last ezdit_forward (host counter). */
