@@ -103,9 +103,33 @@ int launch_status(const char* what) {   // a failed launch must surface as an er
 extern "C" {
 
 // out fp32 [M][ldo] = A . W^T (+ bias) (+ resid); conv_cpb / conv_tap_bytes as in GemmArgs.  N multiple of 4.
+// Everything that cannot be computed is refused HERE, before any HIP call (include/ezdit.h lists the rules): the tile id is the caller's, and only the
+// lockstep k_gemm reads conv_cpb / conv_tap_bytes -- the ping-pong, co-resident and K-split kernels would run a plain GEMM over K * 2 bytes of each row.
 int ezvae_gemm(const void* A, int lda, const void* W, int ldw, int wrows, const float* bias, const float* resid, int ldr,
                float* out, int ldo, int M, int N, int K, int conv_cpb, long conv_tap_bytes, int tile, ezdit_stream stream) {
-    if (K % 64 || N % 4) return ez_fail(EZDIT_E_INVALID, "ezvae_gemm: K=%d must be a multiple of 64 and N=%d of 4", K, N);
+    if (M <= 0 || N <= 0) return ez_fail(EZDIT_E_INVALID, "ezvae_gemm: M=%d and N=%d must be positive", M, N);
+    if (K <= 0 || K % 64 || N % 4) return ez_fail(EZDIT_E_INVALID, "ezvae_gemm: K=%d must be a positive multiple of 64 and N=%d of 4", K, N);
+    if (lda < 0 || ldw < 0 || wrows <= 0 || conv_cpb < 0)
+        return ez_fail(EZDIT_E_INVALID, "ezvae_gemm: lda=%d, ldw=%d, conv_cpb=%d must not be negative and wrows=%d must be positive", lda, ldw, conv_cpb, wrows);
+    const bool lockstep = tile == 6 || tile == 9 || tile == 13 || tile == 25;       // k_gemm: conv addressing, resid
+    const bool pp_co = tile == 60 || tile == 61 || tile == 62 || tile == 66;         // k_gemm_pp / k_gemm_co: resid (pp_store_direct), no conv addressing
+    const bool ks = tile == 70 || tile == 72 || tile == 73;                          // k_gemm_ks: neither
+    if (!lockstep && !pp_co && !ks) return ez_fail(EZDIT_E_UNSUPPORTED, "ezvae_gemm: tile %d is not a GEMM configuration", tile);
+    if (conv_cpb != 0 && !lockstep)
+        return ez_fail(EZDIT_E_UNSUPPORTED, "ezvae_gemm: tile %d does not implement conv addressing (conv_cpb=%d); tiles 6, 9, 13, 25 do", tile, conv_cpb);
+    if (resid && ks) return ez_fail(EZDIT_E_UNSUPPORTED, "ezvae_gemm: tile %d does not add a residual to an fp32 output", tile);
+    if (conv_cpb != 0 && conv_tap_bytes % 16) return ez_fail(EZDIT_E_INVALID, "ezvae_gemm: conv_tap_bytes=%ld must be a multiple of 16", conv_tap_bytes);
+    {   // the staging offsets of A and W are 32-bit (stage_offsets, common.h): the furthest element a launch may name stays below 2^31
+        const long nkt = K / 64;
+        long reach = K;
+        if (conv_cpb != 0) {
+            const long far_tap = (nkt - 1) / conv_cpb * (conv_tap_bytes / 2);
+            reach = (far_tap > 0 ? far_tap : 0) + (nkt < conv_cpb ? nkt : (long)conv_cpb) * 64;
+        }
+        const long a_reach = (long)(M - 1) * lda + reach, w_reach = (long)(wrows - 1) * ldw + K;
+        if (a_reach >= (1L << 31) || w_reach >= (1L << 31))
+            return ez_fail(EZDIT_E_INVALID, "ezvae_gemm: operand reach A=%ld / W=%ld elements does not fit the 32-bit staging offset (< 2^31)", a_reach, w_reach);
+    }
     GemmArgs g;
     memset(&g, 0, sizeof g);
     g.A = (const bf16_t*)A; g.lda = lda; g.W = (const bf16_t*)W; g.ldw = ldw; g.wrows = wrows; g.bias = bias;
@@ -119,7 +143,7 @@ int ezvae_gemm(const void* A, int lda, const void* W, int ldw, int wrows, const 
 
 int ezvae_snake_bf16(const float* x, int ldx, const float* alpha, const float* inv_beta, void* out, int ldo, long L, int C,
                      ezdit_stream stream) {
-    if (C % 4) return ez_fail(EZDIT_E_INVALID, "C=%d must be a multiple of 4", C);
+    if (L <= 0 || C <= 0 || C % 4) return ez_fail(EZDIT_E_INVALID, "ezvae_snake_bf16: L=%ld must be positive and C=%d a positive multiple of 4", L, C);
     const long total = L * (C / 4);
     hipLaunchKernelGGL(k_snake_bf16, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, ldx, alpha, inv_beta,
                        (bf16_t*)out, ldo, L, C);
@@ -127,19 +151,21 @@ int ezvae_snake_bf16(const float* x, int ldx, const float* alpha, const float* i
 }
 
 int ezvae_conv_out1(const void* xb, int ldx, const float* w, float* out, long L, int C, ezdit_stream stream) {
-    if (C % 8) return ez_fail(EZDIT_E_INVALID, "C=%d must be a multiple of 8", C);
+    if (L <= 0 || C <= 0 || C % 8) return ez_fail(EZDIT_E_INVALID, "ezvae_conv_out1: L=%ld must be positive and C=%d a positive multiple of 8", L, C);
     hipLaunchKernelGGL(k_conv_out1, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)xb, ldx, w, out, L, C);
     return launch_status("k_conv_out1");
 }
 
 int ezvae_conv_in1(const float* wav, const float* w, const float* bias, float* out, long T, int C, ezdit_stream stream) {
-    if (C % 4) return ez_fail(EZDIT_E_INVALID, "C=%d must be a multiple of 4", C);
+    if (T <= 0 || C <= 0 || C % 4) return ez_fail(EZDIT_E_INVALID, "ezvae_conv_in1: T=%ld must be positive and C=%d a positive multiple of 4", T, C);
     const long total = T * (C / 4);
     hipLaunchKernelGGL(k_conv_in1, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, wav, w, bias, out, T, C);
     return launch_status("k_conv_in1");
 }
 
 int ezvae_sample(const float* enc, const float* noise, float* z, int L, int latent_dim, ezdit_stream stream) {
+    if (L <= 0 || latent_dim <= 0 || (long)L * latent_dim >= (1L << 31))
+        return ez_fail(EZDIT_E_INVALID, "ezvae_sample: L=%d and latent_dim=%d must be positive, with L * latent_dim < 2^31", L, latent_dim);
     const int total = L * latent_dim;
     hipLaunchKernelGGL(k_vae_sample, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, enc, noise, z, L, latent_dim);
     return launch_status("k_vae_sample");

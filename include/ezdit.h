@@ -204,7 +204,15 @@ int ezdit_sampler_run(ezdit_handle* h, int n, int use_graph, ezdit_stream stream
  * Stateless ops on caller-owned device buffers; the layer sequence is host code (ezaudio_amd/vae.py), run once per call.
  * Activations are token-major [L][C] with zero halo rows so that convolutions are GEMMs over shifted rows. */
 /* out fp32 [M][ldo] = A[M][K] . W[N][K]^T (+ bias[N]) (+ resid[M][ldr]); K tile t (64 wide) of A is read at byte offset
- * (t / conv_cpb) * conv_tap_bytes + (t % conv_cpb) * 128 (conv_cpb = 0: plain GEMM).  A, W bf16. */
+ * (t / conv_cpb) * conv_tap_bytes + (t % conv_cpb) * 128 (conv_cpb = 0: plain GEMM).  A, W bf16.  `tile` is a configuration id of csrc/gemm.hip.
+ * Refused before anything is read or launched (the message of ezdit_last_error names the argument):
+ *   EZDIT_E_UNSUPPORTED  a tile id that is no configuration; conv_cpb != 0 on a tile other than 6, 9, 13, 25 (only the lockstep kernel implements the
+ *                        conv addressing: 60, 61, 62, 66, 70, 72, 73 would run a plain GEMM over K * 2 bytes of each row); dev_resid on tile 70, 72, 73
+ *                        (the K-split kernel's fp32 epilogue adds none; 6, 9, 13, 25, 60, 61, 62, 66 do)
+ *   EZDIT_E_INVALID      M or N <= 0; K not a positive multiple of 64; N not a multiple of 4; lda, ldw or conv_cpb < 0; wrows <= 0; conv_tap_bytes not a
+ *                        multiple of 16; (M - 1) lda plus the furthest tap's reach (conv_cpb = 0: plus K), or (wrows - 1) ldw + K, at or above 2^31
+ *                        elements -- the kernels stage A and W through 32-bit offsets
+ * The other four ops return EZDIT_E_INVALID for L, T, C or latent_dim <= 0 (and C not a multiple of 4; 8 for ezvae_conv_out1). */
 int ezvae_gemm(const void* dev_a, int lda, const void* dev_w, int ldw, int wrows, const float* dev_bias, const float* dev_resid,
                int ldr, float* dev_out, int ldo, int M, int N, int K, int conv_cpb, long conv_tap_bytes, int tile,
                ezdit_stream stream);

@@ -155,7 +155,7 @@ def conv1d(x, w, b=None, stride=1, padding=0, dilation=1):
     Co, _, K = w.shape
     xp = np.pad(x, ((0, 0), (0, 0), (padding, padding)))
     Lout = (L + 2 * padding - dilation * (K - 1) - 1) // stride + 1
-    out = np.zeros((B, Co, Lout), dtype=np.float32)
+    out = np.zeros((B, Co, Lout), dtype=np.result_type(x.dtype, w.dtype, np.float32))   # float64 operands: a float64 reference (tests/vae_emul.py)
     for k in range(K):
         seg = xp[:, :, k * dilation:k * dilation + stride * (Lout - 1) + 1:stride]
         wk = np.ascontiguousarray(w[:, :, k])
@@ -170,7 +170,7 @@ def conv_transpose1d(x, w, b=None, stride=1, padding=0):
     """nn.ConvTranspose1d: x [B,Ci,L], w [Ci,Co,K] -> [B,Co,(L-1)*stride - 2*padding + K]."""
     B, Ci, L = x.shape
     _, Co, K = w.shape
-    full = np.zeros((B, Co, (L - 1) * stride + K), dtype=np.float32)
+    full = np.zeros((B, Co, (L - 1) * stride + K), dtype=np.result_type(x.dtype, w.dtype, np.float32))
     for k in range(K):
         wk = np.ascontiguousarray(w[:, :, k].T)
         for bi in range(B):

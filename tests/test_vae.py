@@ -130,6 +130,195 @@ def test_decoder_rejects_unbuilt_recipes():
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# the gates of the kernel-level VAE tests (tests/test_vae_kernels.py) against the numpy emulations of tests/vae_emul.py: the emulation of each op (fp32 arithmetic on
+# the test's own inputs) passes its gate, and every deliberate mistake exceeds it at least three times over (`excess` = worst error / bound; infinity = a value that
+# is not finite, or the sentinel touched outside the region the op owns)
+# ----------------------------------------------------------------------------------------------------------------------
+def _margin(what, mut, ex):
+    print(f'{what} [{mut}]: {ex:.3g} x the gate')
+    return ex
+
+
+def _conv_specs():
+    from tests import vae_emul as E
+    dil = [('conv', dict(C=C, d=d, L=L)) for C in (64, 128) for d in (1, 3, 9) for L in (1, 5, 127, 129)]
+    return dil + [E.GEMM_FAMILIES['decoder_conv_in'][1]] + E.GEMM_FAMILIES['encoder_conv_out_k3'][3:]
+
+
+@pytest.mark.parametrize('spec', _conv_specs(), ids=lambda s: '-'.join(f'{k}{v}' for k, v in s[1].items()))
+def test_vae_conv_gemm_gates_hold_the_emulation_and_catch_every_tap_mistake(spec):
+    """Every tap one row further; tap order reversed; the halo one row short (the last valid row where a zero belongs).  Two of them cannot be seen everywhere, and the
+    test says where: with L <= dilation only the centre tap meets the sequence, so reversing the order changes nothing; the short halo's row is read by output row
+    L - j d (j = 1 .. k // 2) only, which needs L >= d.  L = 5 with d = 3 is the case in which EVERY row reads the halo and both mistakes still show."""
+    from tests import vae_emul as E
+    c = E.build(spec)
+    L, d = spec[1]['L'], spec[1]['d']
+    assert _margin(c.name, 'emulation', c.excess(c.emulate())) <= 1.0
+    assert _margin(c.name, 'tap_shift+1', c.excess(c.emulate(mut='tap_shift+1'))) >= 3.0
+    rev = _margin(c.name, 'tap_reversed', c.excess(c.emulate(mut='tap_reversed')))
+    assert rev >= 3.0 if L > d else rev <= 1.0
+    short = _margin(c.name, 'halo_short', c.excess(E.build(spec, mut='halo_short').emulate()))
+    assert short >= 3.0 if L >= d else short <= 1.0
+    if L >= 127 and short >= 3.0:       # ... and only within 3 d rows of the end: the per-element bound is what sees it, an average over the rows would not
+        bad = E.build(spec, mut='halo_short').emulate().reshape(-1, c.ldo)[E.GUARD:E.GUARD + L, :c.N]
+        err = np.abs(bad - c.full_ref) / c.full_bound
+        assert err[:L - 3 * d].max() <= 1.0 and E.rel_l2(bad.astype(np.float64), c.full_ref) < 0.2
+
+
+def _convt_specs():
+    from tests import vae_emul as E
+    return [('convt', dict(ci=ci, co=co, s=s, L=L)) for ci, co, s in E.CONVT_PAIRS for L in (1, 37)]
+
+
+@pytest.mark.parametrize('spec', _convt_specs(), ids=lambda s: '-'.join(f'{k}{v}' for k, v in s[1].items()))
+def test_vae_transposed_conv_gates_hold_the_emulation_and_catch_every_mistake(spec):
+    """The sign of the negative tap step flipped (x[q + 1] where x[q - 1] belongs: row L reads the NaN guard, the reason the guards are there); the tap step off by one
+    row; the halo one row short; the bias on phase 0 only; the read-back offset ceil(s / 2) -+ 1, for every stride."""
+    from tests import vae_emul as E
+    c = E.build(spec)
+    good = c.emulate()
+    assert _margin(c.name, 'emulation', c.excess(good)) <= 1.0
+    for mut in ('tap_sign', 'tap_shift+1'):
+        assert _margin(c.name, mut, c.excess(c.emulate(mut=mut))) >= 3.0
+    for mut in ('halo_short', 'bias_once'):
+        assert _margin(c.name, mut, c.excess(E.build(spec, mut=mut).emulate())) >= 3.0
+    for shift in (-1, 1):
+        assert _margin(c.name, f'read-back offset {shift:+d}', c.excess(good, shift=shift)) >= 3.0
+
+
+@pytest.mark.parametrize('s', [2, 4, 6, 10])
+def test_vae_strided_conv_gates_catch_a_ceiling_where_the_floor_belongs(s):
+    """Lo = ceil(T / s): one more output row, seen as a touched sentinel row -- for the T of the GPU test, none a multiple of s.  At T = 4 s floor and ceiling agree and the
+    mistake cannot be seen: the reason no T of the test is a multiple of its stride."""
+    from tests import vae_emul as E
+    for T in E.strided_T(s) + (4 * s,):
+        spec = ('strided', dict(C=64, Co=128, s=s, T=T))
+        c = E.build(spec)
+        assert c.M == T // s and (T % s != 0 or T == 4 * s)
+        assert _margin(c.name, 'emulation', c.excess(c.emulate())) <= 1.0
+        ex = _margin(c.name, 'ceil', c.excess(E.build(spec, mut='ceil').emulate(like=c)))
+        assert ex >= 3.0 if T % s else ex <= 1.0
+    assert E.strided_T(s)[0] // s == 1
+
+
+def test_vae_pointwise_and_plain_gemm_gates_hold_the_emulation():
+    from tests import vae_emul as E
+    for spec in E.GEMM_FAMILIES['pointwise_resid'] + E.GEMM_FAMILIES['no_bias_ldo'] + E.GEMM_FAMILIES['strided']:
+        c = E.build(spec)
+        assert _margin(c.name, 'emulation', c.excess(c.emulate())) <= 1.0
+        # the residual's guard columns and rows are NaN: one column or one row off is not finite
+        if c.r is not None:
+            for off in (-1, 1, -c.ldr, c.ldr):
+                c.r0 += off
+                bad = c.excess(c.emulate())
+                c.r0 -= off
+                assert _margin(c.name, f'resid pointer {off:+d}', bad) >= 3.0
+    assert set(E.GEMM_TILE25) == set(E.GEMM_FAMILIES)
+    for fam, spec in E.GEMM_TILE25.items():
+        assert spec in E.GEMM_FAMILIES[fam]
+
+
+def test_vae_conv_in1_and_conv_out1_gates_catch_clamping_where_zero_padding_belongs():
+    """... at the first and last 3 samples only, so T = 1 .. 7 matter; conv_in1 padding by READING is invisible between zero guards and not finite between NaN guards."""
+    from tests import vae_emul as E
+    for C, L in E.CONV_OUT1:
+        c = E.ConvOut1Case(C, L)
+        what = f'conv_out1 C{C} L{L}'
+        assert _margin(what, 'emulation', c.excess(c.emulate())) <= 1.0
+        for mut in ('clamp', 'tap_shift+1') + (('tap_reversed',) if L > 1 else ()):        # (one row meets the centre tap only)
+            assert _margin(what, mut, c.excess(c.emulate(mut))) >= 3.0
+    for C, T in E.CONV_IN1:
+        c = E.ConvIn1Case(C, T)
+        what = f'conv_in1 C{C} T{T}'
+        assert _margin(what, 'emulation', c.excess(c.emulate())) <= 1.0
+        for mut in ('clamp', 'pad_by_reading') + (('tap_reversed',) if T > 1 else ()):     # (one sample meets the centre tap only)
+            assert _margin(what, mut, c.excess(c.emulate(mut))) >= 3.0
+        z = E.ConvIn1Case(C, T, zero_guards=True)
+        assert z.excess(z.emulate('pad_by_reading')) <= 1.0
+
+
+def test_vae_sample_gates_catch_swapped_halves_swapped_indices_and_a_missing_threshold():
+    from tests import vae_emul as E
+    for with_noise in (True, False):
+        for lat, L in E.SAMPLE_SHAPES:
+            assert lat != L
+            c = E.SampleCase(lat, L, with_noise)
+            what = f'sample lat {lat} L{L} noise {with_noise}'
+            assert _margin(what, 'emulation', c.excess(c.emulate())) <= 1.0
+            for mut in ('halves_swapped', 'index_swapped', 'no_threshold'):     # (no_threshold: scale = 100 is among the inputs, expf overflows)
+                assert _margin(what, mut, c.excess(c.emulate(mut))) >= 3.0
+            assert (c.enc[:, lat:] == 100.0).any() and (c.enc[:, lat:] == -100.0).any()
+        sq = E.SampleCase(*E.SAMPLE_SQUARE, with_noise)
+        assert sq.excess(sq.emulate('index_swapped')) <= 1.0                     # L == latent: invisible, hence L != latent above
+    assert any(lat * L % 256 for lat, L in E.SAMPLE_SHAPES)
+
+
+def test_vae_snake_gates_hold_float32_numpy_and_catch_sin_for_sin_squared_and_beta_for_its_inverse():
+    """The cap on the share of elements not bit-equal to bf16(reference), 0.5 %, is a condition: the same formula in numpy float32 on the same inputs stays under a
+    third of it.  The cast's reference rounding (integer arithmetic on the bits) agrees with torch's on every special value."""
+    import torch
+    from tests import vae_emul as E
+    assert any(L * C // 4 % 256 for C, L in E.SNAKE_SHAPES)
+    for C, L in E.SNAKE_SHAPES:
+        c = E.SnakeCase(C, L, True)
+        what = f'snake C{C} L{L}'
+        ex, share = c.measure(c.emulate())
+        print(f'{what}: float32 numpy not bit-equal {share:.2e} (cap {E.SNAKE_SHARE_CAP:.1e})')
+        assert _margin(what, 'emulation', ex) <= 1.0 and share <= E.SNAKE_SHARE_CAP / 3
+        assert np.abs(c.alpha[None, :] * c.x).max() > 200
+        for mut in ('sin_not_squared', 'beta_not_inverted'):
+            assert _margin(what, mut, c.measure(c.emulate(mut))[0]) >= 3.0
+        k = E.SnakeCase(C, L, False)
+        assert k.measure(k.emulate())[0] == 0.0
+        want = torch.from_numpy(k.x).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
+        assert np.array_equal(E.bf16_bits(k.x), want)
+        flip = k.emulate()
+        flip[E.GUARD + E.SNAKE_HALO, 0] ^= 1                                       # one ulp on one element of the cast: not bitwise
+        assert k.measure(flip)[0] >= 3.0
+        touched = k.emulate()
+        touched[E.GUARD + E.SNAKE_HALO - 1, 0] = 0                                  # a halo row written
+        assert k.measure(touched)[0] >= 3.0
+    v = np.array([1.00390625, 1.01171875, -1.00390625, 3.0e-5, 257.0], np.float64)  # ties at 8 significant bits: to even
+    assert np.array_equal(E.bf16_rne64(v), E.bf16_val(E.bf16_bits(v.astype(np.float32))).astype(np.float64))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the public ezvae_* entry points refuse what they cannot compute -- before anything is dereferenced or launched: the pointers below name nothing
+# ----------------------------------------------------------------------------------------------------------------------
+def test_vae_entry_points_refuse_what_cannot_be_computed(lib):
+    INVALID, UNSUPPORTED = -1, -2
+    P = 4096         # never dereferenced
+
+    def gemm(M=128, N=64, K=64, lda=64, ldw=64, wrows=64, resid=None, cpb=0, tap=0, tile=6):
+        rc = lib.ezvae_gemm(P, lda, P, ldw, wrows, None, resid, N, P, N, M, N, K, cpb, tap, tile, None)
+        return rc, lib.ezdit_last_error().decode()
+
+    for tile in (60, 61, 62, 66, 70, 72, 73):          # conv addressing lives in the lockstep kernel only
+        rc, msg = gemm(K=448, cpb=1, tap=128, tile=tile)
+        assert rc == UNSUPPORTED and f'tile {tile}' in msg and 'conv' in msg, (tile, rc, msg)
+    for tile in (70, 72, 73):                          # fp32 output of the K-split kernel: no residual
+        rc, msg = gemm(resid=P, tile=tile)
+        assert rc == UNSUPPORTED and f'tile {tile}' in msg and 'resid' in msg, (tile, rc, msg)
+    for tile in (0, 2, 5, 7, 8, 4, 99, -1):            # retired or unknown ids
+        rc, msg = gemm(tile=tile)
+        assert rc == UNSUPPORTED and f'tile {tile}' in msg, (tile, rc, msg)
+    for kw in (dict(M=0), dict(M=-5), dict(N=0), dict(N=-4), dict(K=0), dict(K=100), dict(N=6), dict(cpb=-1), dict(wrows=0),
+               dict(K=448, cpb=1, tap=136), dict(K=448, cpb=1, tap=-8),                        # tap step not a multiple of 16 bytes
+               dict(M=2 ** 21 + 1, lda=1024), dict(M=120000, lda=17896),                        # (M - 1) lda + K reach >= 2^31 elements
+               dict(M=2 ** 20, lda=2040, K=448, cpb=1, tap=2 ** 24),                            # ... through the furthest tap
+               dict(wrows=2 ** 21 + 1, ldw=1024)):
+        rc, msg = gemm(**kw)
+        assert rc == INVALID and msg, (kw, rc, msg)
+    assert gemm(M=2 ** 21, lda=1024, K=1024)[0] == INVALID and (2 ** 21 - 1) * 1024 + 1024 == 2 ** 31      # the boundary itself
+    for L, C in ((0, 64), (-1, 64), (5, 0), (5, -64), (5, 6)):
+        assert lib.ezvae_snake_bf16(P, C, None, None, P, C, L, C, None) == INVALID and lib.ezdit_last_error()
+        assert lib.ezvae_conv_out1(P, C, P, P, L, C, None) == INVALID
+        assert lib.ezvae_conv_in1(P, P, P, P, L, C, None) == INVALID
+    for L, lat in ((0, 64), (-3, 64), (5, 0), (5, -1), (2 ** 16, 2 ** 15)):
+        assert lib.ezvae_sample(P, None, P, L, lat, None) == INVALID
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # GPU: the HIP decoder through the C ABI
 # ----------------------------------------------------------------------------------------------------------------------
 def _hip_decoder(cfg, sd):

@@ -27,7 +27,7 @@ def timeit(fn, n=10):
     return (time.perf_counter() - t) / n * 1e3
 
 
-for tile in (2, 5, 6, 7, 8, 9, 0, 4):
+for tile in (6, 9, 13, 25):   # the ids that address convolutions (csrc/gemm.hip: the lockstep kernel); ezvae_gemm refuses every other
     dec.tile = enc.tile = tile
     try:
         td = timeit(lambda: dec(z))
