@@ -134,7 +134,7 @@ struct ezdit_handle {
     // 14 split-K GEMMs + 14 row-kernel launches of an XL step become 14 un-split launches (225 launches instead of 239).  The ping-pong producer (M > kZBigM rows) has the same forms.
     // ControlNet residuals change the skips (skip + scale * residual) and take the row-kernel path.
     int opt_skip_z = 1;
-    bool skip_z_usable() const { return opt_skip_z && !is_cn && nhalf > 0 && (D + zwidth() - 1) / zwidth() <= (ztile() == kZTile ? 16 : 8); }   // (statistics parts a lane group of the consumer covers)
+    bool skip_z_usable() const { return opt_skip_z && !is_cn && nhalf > 0 && zparts() <= (ztile() == kZTile ? 16 : 8); }   // (statistics parts a lane group of the consumer covers)
     // GEGLU GEMM on the co-resident kernel (k_gemm_co, gemm_co.h: 4-wave workgroups with a 128 x 144 tile, TWO per CU, so that a workgroup's prologue and
     // epilogue run under its neighbour's K loop): 0 = never, 1 = above kCoM rows (batched prompts: the ping-pong kernel runs 4 rounds of workgroups there), 2 = always
     int opt_geglu_co = 0;
@@ -167,10 +167,27 @@ struct ezdit_handle {
     // the LayerNorm-algebra path can run for the bound shape under the current options (its tables are built by ezdit_prepare_timesteps only then)
     bool zfuse_usable() const {
         // the cross-attention q projection must be one of the two LayerNorm-algebra consumers: fused into k_attn (small grids) or the ping-pong GEMM with the q epilogue
-        return opt_zfuse && (D + zwidth() - 1) / zwidth() <= Z_MAXP && (opt_gemm_pp & 1) && qkv_mode() == 2 && (q2_fused(B) || opt_q2_pp);
+        return opt_zfuse && zparts() <= Z_MAXP && (opt_gemm_pp & 1) && qkv_mode() == 2 && (q2_fused(B) || opt_q2_pp);
     }
     int ztile() const { return (M > kZBigM && !per_row) ? 61 : kZTile; }   // producer of the LayerNorm algebra for the bound shape (the ping-pong producer shares one modulation slot per launch)
     int zwidth() const { return ztile() == 61 ? 144 : 96; }   // statistics part = the producer's tile width
+    int zparts() const { return (D + zwidth() - 1) / zwidth(); }   // statistics parts of a D-wide producer
+    // ---- layouts of the LayerNorm-algebra buffers.  carve (sizes), ezdit_prepare_timesteps (fill), forward_impl (use) and the EZ_DIAG blocks all go through these ----
+    // G' / C' tables of one consumer: [slot][item][G' | C'][N] floats, item = block (out-block for zt_skip); the static tables (norm2 -> to_q, skip_norm -> skip_linear) have one slot
+    struct ZTab { float *G, *C; long slot_stride; };
+    static long ztab_floats(int items, long N) { return (long)items * 2 * N; }
+    static ZTab ztab(float* base, int item, long N, long slot_stride) { float* G = base + ztab_floats(item, N); return {G, G + N, slot_stride}; }
+    ZTab zt_qkv_of(int b) const { return ztab(p.zt_qkv, b, 3L * D, ztab_floats(nblk, 3L * D)); }
+    ZTab zt_geglu_of(int b) const { return ztab(p.zt_geglu, b, 2L * I, ztab_floats(nblk, 2L * I)); }
+    ZTab zt_q2_of(int b) const { return ztab(p.zt_q2, b, D, 0); }
+    ZTab zt_skip_of(int j) const { return ztab(p.zt_skip, j, D, 0); }
+    // partial statistics are part-major [part][Mp] float pairs in ranges of Z_MAXP parts: `zstat` holds two ranges (the second one: the x half in front of an
+    // out-block, written by the MLP-out projection and read by skip_linear), `zstat_skip` one range per skip (kept from the in-block to its out-block)
+    static size_t zrange(long Mp_) { return (size_t)Z_MAXP * Mp_; }
+    float2* zstat_xhalf() const { return p.zstat + zrange(Mp); }
+    float2* zstat_skip_of(int i) const { return p.zstat_skip + (size_t)i * zrange(Mp); }
+    size_t ucat_elems(long Mp_) const { return (size_t)Mp_ * ld2D; }
+    bf16_t* ucat_of(int j) const { return p.ucat_z + (size_t)j * ucat_elems(Mp); }   // operand [x | skip] of out-block j
     int opt_wt = 2;   // write-through (sc1) output stores: 0 off, 1 on, 2 = on while B L <= 2048.  The end-of-kernel write-back then has nothing left to flush: -3.5 % step time
                       // for one prompt (4.19 -> 4.04 ms), +1.4 % for four (the step is throughput-bound there and the stores compete with the loads)
     int wt() const { return opt_wt == 2 ? (B * L <= 2048) : opt_wt; }
@@ -429,22 +446,23 @@ size_t carve(const ezdit_handle* h, int B, int L, int Lc, int n_slots, std::map<
     // LayerNorm algebra: partial row statistics (chunks of 64 columns, up to the 2D-wide concat), G' / C' tables per modulation slot
     {
         const long I2 = 2L * h->I, N3 = 3L * D, nmax = I2 > N3 ? I2 : N3;
-        add("zstat", (size_t)Mp * (((2 * D + 63) / 64) > 2 * Z_MAXP ? ((2 * D + 63) / 64) : 2 * Z_MAXP) * 8);   // two part ranges of Z_MAXP: the second one holds the statistics of the x half in front of an out-block (skip_z)
-        add("zt_qkv", (size_t)ns * nblk * 2 * N3 * 4);
-        add("zt_geglu", (size_t)ns * nblk * 2 * I2 * 4);
-        add("zt_q2", (size_t)nblk * 2 * D * 4);
+        const size_t zr = ezdit_handle::zrange(Mp), z64 = (size_t)Mp * ((2 * D + 63) / 64), nskip = h->nhalf > 0 ? h->nhalf : 1;
+        add("zstat", (z64 > 2 * zr ? z64 : 2 * zr) * 8);   // two part ranges of Z_MAXP: the second one holds the statistics of the x half in front of an out-block (skip_z)
+        add("zt_qkv", (size_t)ns * ezdit_handle::ztab_floats(nblk, N3) * 4);
+        add("zt_geglu", (size_t)ns * ezdit_handle::ztab_floats(nblk, I2) * 4);
+        add("zt_q2", (size_t)ezdit_handle::ztab_floats(nblk, D) * 4);
         add("zd", (size_t)nblk * B * D * 4);
         add("zA", (size_t)rup(4 * ns, 128) * h->ldD * 2);
         add("ztmp", (size_t)rup(4 * ns, 128) * nmax * 4);
 #ifdef EZ_DIAG
-        add("zneutral", (size_t)Z_MAXP * Mp * 8);
+        add("zneutral", zr * 8);
         add("zzeros", (size_t)nmax * 4);
 #endif
         // skip path by the LayerNorm algebra (opt_skip_z), BEHIND everything else: the buffers above keep the offsets -- the relative placement in the HBM channels -- the
         // round's measurements were made with.  One [x | skip] operand per out-block (the in-block fills the right half long before the out-block runs), the skips' statistics, static tables
-        add("ucat_z", (size_t)((!h->is_cn && h->nhalf > 0) ? h->nhalf : 1) * Mp * h->ld2D * 2);
-        add("zstat_skip", (size_t)(h->nhalf > 0 ? h->nhalf : 1) * Z_MAXP * Mp * 8);
-        add("zt_skip", (size_t)(h->nhalf > 0 ? h->nhalf : 1) * 2 * D * 4);
+        add("ucat_z", (h->is_cn ? 1 : nskip) * h->ucat_elems(Mp) * 2);
+        add("zstat_skip", nskip * zr * 8);
+        add("zt_skip", (size_t)ezdit_handle::ztab_floats((int)nskip, D) * 4);
         add("lens", 256 * sizeof(int));   // per-batch-element valid frames of a padded batch (B <= 240), behind everything else for the same reason
     }
     return off;
@@ -456,11 +474,6 @@ size_t carve(const ezdit_handle* h, int B, int L, int Lc, int n_slots, std::map<
 struct Ctx {
     ezdit_handle* h;
     hipStream_t st;
-    const HeadNormArgs* hn = nullptr;   // one-shot: EPI_QKV epilogue arguments
-    bool panel = false;                 // one-shot: panel placement of a split-K GEMM (GemmArgs.xcd_panel)
-    const float* zG = nullptr; const float* zC = nullptr; long zt_stride = 0;   // one-shot: LayerNorm algebra in the consumer's epilogue
-    const float2* zstat = nullptr;      // one-shot: ... its partial statistics when they are not in the shared buffer (null = WsPtrs.zstat)
-    int zrow0 = 0, zb0 = 0;   // one-shot: the launch covers a row sub-range that starts at row zrow0 = batch element zb0 (statistics table / per-row slot offsets)
     const int* cur = nullptr; const int* row_slot = nullptr;   // modulation slot of this forward (a ControlNet attached to the fused sampler reads the BACKBONE's step counter)
     // first launch failure of this call (hipGetLastError after EVERY launch: a rejected launch -- LDS limit, bad grid,
     // unsupported fused configuration -- must surface as an error code, never as stale numbers)
@@ -484,8 +497,17 @@ struct Ctx {
     }
 };
 
+// LayerNorm-algebra input of a consumer GEMM (EPI_QKV, EPI_GEGLU): the operand is A' = bf16(x g) and the epilogue finishes the LayerNorm from the tables `t` and the
+// partial statistics `stat` (null = plain GEMM on a finished LayerNorm).  A launch over a row sub-range starts at row row0 = batch element b0 (statistics / per-row slot offsets)
+struct ZIn {
+    ezdit_handle::ZTab t{};
+    const float2* stat = nullptr;
+    int row0 = 0, b0 = 0;
+};
+
+// hn: EPI_QKV epilogue arguments; panel: panel placement of a split-K GEMM (GemmArgs.xcd_panel)
 void gemm(Ctx& c, const bf16_t* A, int lda, const WRef& w, const float* bias, void* out, int ldo, int M, int N,
-          int epi, int tile, int splitk = 1, long slab = 0) {
+          int epi, int tile, const HeadNormArgs* hn = nullptr, const ZIn& z = ZIn{}, int splitk = 1, long slab = 0, bool panel = false) {
     ezdit_handle* h = c.h;
     GemmArgs g;
     memset(&g, 0, sizeof g);
@@ -509,21 +531,19 @@ void gemm(Ctx& c, const bf16_t* A, int lda, const WRef& w, const float* bias, vo
     g.wt = h->wt();
     g.epi_lds = h->opt_epi_lds;
     g.rows_per_b = 1;
-    if (c.hn) { g.hn = *c.hn; c.hn = nullptr; }
-    if (c.panel) { g.xcd_panel = 1; c.panel = false; }
+    if (hn) g.hn = *hn;
+    g.xcd_panel = panel ? 1 : 0;
 #ifdef EZ_DIAG
-    if (!c.zG && h->opt_zfake && (epi == EPI_QKV || epi == EPI_GEGLU) && (tile == 60 || tile == 61 || tile == 66) && (h->D + h->zwidth() - 1) / h->zwidth() <= Z_MAXP) {
-        g.zw = h->zwidth(); g.zstat_in = h->buf<float2>("zneutral"); g.zs_stride = h->Mp; g.zparts = (h->D + g.zw - 1) / g.zw; g.zD = h->D;
+    if (!z.stat && h->opt_zfake && (epi == EPI_QKV || epi == EPI_GEGLU) && (tile == 60 || tile == 61 || tile == 66) && h->zparts() <= Z_MAXP) {
+        g.zw = h->zwidth(); g.zstat_in = h->buf<float2>("zneutral"); g.zs_stride = h->Mp; g.zparts = h->zparts(); g.zD = h->D;
         g.zG = h->buf<float>("zzeros"); g.zC = bias ? bias : g.zG; g.zt_slot_stride = 0; g.zeps = 1e-5f; g.rows_per_b = h->L;
     }
 #endif
-    if (c.zG) {
-        g.zw = h->zwidth(); g.zstat_in = (c.zstat ? c.zstat : h->p.zstat) + c.zrow0; g.zs_stride = h->Mp; g.zparts = (h->D + g.zw - 1) / g.zw; g.zD = h->D; g.zG = c.zG; g.zC = c.zC; g.zt_slot_stride = c.zt_stride; g.zeps = 1e-5f;
+    if (z.stat) {
+        g.zw = h->zwidth(); g.zstat_in = z.stat + z.row0; g.zs_stride = h->Mp; g.zparts = h->zparts(); g.zD = h->D; g.zG = z.t.G; g.zC = z.t.C; g.zt_slot_stride = z.t.slot_stride; g.zeps = 1e-5f;
         g.cur_step = c.cur ? c.cur : h->p.ints; g.row_slot = c.cur ? c.row_slot : (h->per_row ? h->p.ints + 16 : nullptr); g.rows_per_b = h->L;
-        if (g.row_slot) g.row_slot += c.zb0;
-        c.zG = nullptr; c.zstat = nullptr;
+        if (g.row_slot) g.row_slot += z.b0;
     }
-    c.zrow0 = 0; c.zb0 = 0;
     g.ts = c.stamps(); g.ts_cap = g_gemm_ts_cap;
     c.launched(epi == EPI_GEGLU ? "k_gemm (GEGLU)" : epi == EPI_QKV ? "k_gemm (QKV)" : epi == EPI_PARTIAL ? "k_gemm (split-K slabs)" : "k_gemm", launch_gemm(g, c.st));
 }
@@ -548,10 +568,45 @@ int gemm_partial(Ctx& c, const bf16_t* A, int lda, const WRef& w, int M, int N) 
     const int K = w.ld;
     const int s = pick_splitk(h, M, N, K);
     const int shape_bit = K >= 4 * N ? 4 : K >= 2 * N ? 2 : 1;
-    c.panel = (h->opt_gemm_panel & shape_bit) && M <= 1024;
-    gemm(c, A, lda, w, nullptr, h->p.part, h->D, M, N, EPI_PARTIAL, tile_for(h, M, true), s, (long)h->Mp * h->D);
+    const bool panel = (h->opt_gemm_panel & shape_bit) && M <= 1024;
+    gemm(c, A, lda, w, nullptr, h->p.part, h->D, M, N, EPI_PARTIAL, tile_for(h, M, true), nullptr, ZIn{}, s, (long)h->Mp * h->D, panel);
     return s;
 }
+
+// Base arguments of an un-split residual launch (EPI_RESID):  h_out = h_in + gate * (A . W^T + bias),  zu = bf16(h_out * zg),  zstat_out [N tiles][zs_stride] = the partial
+// LayerNorm statistics of h_out.  The step's edges (forward_impl) and the stand-alone hooks (ezdit_test_resid*) all start from this one and add only what their form needs
+GemmArgs resid_args(int tile, const bf16_t* A, int lda, const bf16_t* W, int ldw, int wrows, const float* bias, const float* h_in, const float* gate, const float* zg,
+                    float* h_out, bf16_t* zu, int ld_zu, float2* zstat_out, long zs_stride, int M, int N, int K) {
+    GemmArgs g;
+    memset(&g, 0, sizeof g);
+    g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.wrows = wrows; g.bias = bias;
+    g.out = h_out; g.ldo = N; g.M = M; g.N = N; g.K = K; g.splitk = 1; g.epi = EPI_RESID; g.tile = tile; g.xcd_map = 1;
+    g.resid = h_in; g.ldr = N; g.gate = gate; g.rows_per_b = 1;
+    g.zu = zu; g.ld_zu = ld_zu; g.zg = zg; g.zstat_out = zstat_out; g.zs_stride = zs_stride;
+    return g;
+}
+
+// One residual edge of the step:  h_out = h_in + gate * (A . W^T + bias),  then the LayerNorm (gain ln_g, shift ln_c) in front of the GEMM that reads the result.
+// A site of forward_impl fills it once; forward_impl's edge() picks the form and the launches.  Lives on the stack; `name` is a literal.
+struct Edge {
+    const char* name = nullptr;   // launch name of the un-split form
+    // the reader finishes the LayerNorm in its own epilogue (LayerNorm algebra): ONE un-split launch that also emits A' = bf16(h_out ln_g) and partial statistics.
+    // Otherwise split-K slabs + the row kernel, which writes the finished LayerNorm
+    bool algebra = false;
+    const bf16_t* A = nullptr; int lda = 0; const WRef* w = nullptr; const float* bias = nullptr;
+    const float* h_in = nullptr; float* h_out = nullptr;   // h_in null: no residual; h_out null: the fp32 stream is not stored
+    const float* gate = nullptr; long gate_stride = 0;     // null = 1; per modulation slot when the stride is non-zero
+    const float *ln_g = nullptr, *ln_c = nullptr; long ln_stride = 0;   // null ln_g: no LayerNorm follows
+    // ---- the un-split forms' extras (GemmArgs: DUAL / COPY2 / ZIN) ----
+    int b0 = 0, nb = -1;     // the launch covers the batch elements [b0, b0 + nb) only (nb < 0: all)
+    int dual_blk = -1;       // >= 0: DUAL form with the constant cross-attention-out vectors of this block (GemmArgs.zd)
+    bf16_t* zu = nullptr; int ld_zu = 0;   // operand buffer instead of `u` ...
+    float2* zstat_out = nullptr;           // ... and statistics instead of the shared buffer (whole-batch launches only)
+    bf16_t* zu2 = nullptr; int ld_zu2 = 0; const float* zg2 = nullptr;          // COPY2: a second operand bf16(h_out zg2)
+    const float2 *zin = nullptr, *zin2 = nullptr; const float* zG = nullptr;    // ZIN: A = bf16([x | skip] g) with the halves' statistics; G' (C' goes in `bias`)
+    // ---- the row-kernel form's extras: LayerNorm over [h_out | skip + cn_scale cn] (long skip connection, ControlNet residual) ----
+    const float *skip = nullptr, *cn = nullptr;
+};
 
 void resolve_weights(ezdit_handle* h) {
     h->blk.assign(h->nblk, BlkW{});
@@ -593,6 +648,16 @@ void resolve_workspace(ezdit_handle* h) {
     p.zstat = h->buf<float2>("zstat"); p.zt_qkv = h->buf<float>("zt_qkv"); p.zt_geglu = h->buf<float>("zt_geglu"); p.zt_q2 = h->buf<float>("zt_q2");
     p.zstat_skip = h->buf<float2>("zstat_skip"); p.zt_skip = h->buf<float>("zt_skip"); p.ucat_z = h->buf<bf16_t>("ucat_z");
     if (h->is_cn) { p.cembed = h->buf<float>("cembed"); p.cnres = h->buf<float>("cnres"); p.skipbf = h->buf<bf16_t>("skipbf"); }
+}
+
+// the launch of a stand-alone hook: a stale error of an earlier call is not this one's; a configuration the launcher refuses (non-zero return) and a failed launch are reported
+template <typename Launch>
+int hook_launch(const char* kernel, const char* config, Launch launch) {
+    (void)hipGetLastError();
+    if (launch()) return fail(EZDIT_E_UNSUPPORTED, "%s not supported", config);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of %s failed: %s", kernel, hipGetErrorString(e));
+    return EZDIT_OK;
 }
 
 }  // namespace
@@ -720,9 +785,9 @@ int ezdit_bind_workspace(ezdit_handle* h, void* ws, size_t bytes, int B, int L, 
     launch_rope_table(h->buf<float>("rope_cos"), h->buf<float>("rope_sin"), h->cfg.max_len, h->dh, st);
 #ifdef EZ_DIAG
     {   // zfake diagnostic: statistics of a zero-mean, unit-variance row in parts of zwidth() columns
-        const int zw = h->zwidth(), parts = (h->D + zw - 1) / zw;
+        const int zw = h->zwidth(), parts = h->zparts();
         if (parts <= Z_MAXP) {
-            std::vector<float2> hst((size_t)Z_MAXP * h->Mp, make_float2(0.f, 0.f));
+            std::vector<float2> hst(ezdit_handle::zrange(h->Mp), make_float2(0.f, 0.f));
             for (int k = 0; k < parts; ++k)
                 for (int r = 0; r < h->Mp; ++r) hst[(size_t)k * h->Mp + r] = make_float2(0.f, (float)(k == parts - 1 ? h->D - zw * (parts - 1) : zw));
             HIPCHK(hipMemcpyAsync(h->buf<float2>("zneutral"), hst.data(), hst.size() * sizeof(float2), hipMemcpyHostToDevice, st));
@@ -889,18 +954,19 @@ int ezdit_prepare_timesteps(ezdit_handle* h, const int32_t* ts, int n, int per_r
             const float* modb = h->p.mod + (long)b * 6 * D;
             launch_z_hilo(modb + 0 * D, modb + 1 * D, mod_slot, zA, h->ldD, n, D, st);
             gemm(c, zA, h->ldD, w.wqkv, nullptr, ztmp, N3, 4 * n, N3, EPI_F32, 25);
-            launch_z_combine(ztmp, N3, nullptr, h->p.zt_qkv + (long)b * 2 * N3, h->p.zt_qkv + (long)b * 2 * N3 + N3, (long)nblk * 2 * N3, n, N3, st);
+            const ezdit_handle::ZTab tq = h->zt_qkv_of(b), tg = h->zt_geglu_of(b), t2 = h->zt_q2_of(b);
+            launch_z_combine(ztmp, N3, nullptr, tq.G, tq.C, tq.slot_stride, n, N3, st);
             launch_z_hilo(modb + 3 * D, modb + 4 * D, mod_slot, zA, h->ldD, n, D, st);
             gemm(c, zA, h->ldD, w.w1, nullptr, ztmp, I2, 4 * n, I2, EPI_F32, 25);
-            launch_z_combine(ztmp, I2, w.b1, h->p.zt_geglu + (long)b * 2 * I2, h->p.zt_geglu + (long)b * 2 * I2 + I2, (long)nblk * 2 * I2, n, I2, st);
+            launch_z_combine(ztmp, I2, w.b1, tg.G, tg.C, tg.slot_stride, n, I2, st);
             launch_z_hilo(w.n2w, w.n2b, 0, zA, h->ldD, 1, D, st);
             gemm(c, zA, h->ldD, w.wq2, nullptr, ztmp, D, 4, D, EPI_F32, 25);
-            launch_z_combine(ztmp, D, nullptr, h->p.zt_q2 + (long)b * 2 * D, h->p.zt_q2 + (long)b * 2 * D + D, 0, 1, D, st);
+            launch_z_combine(ztmp, D, nullptr, t2.G, t2.C, t2.slot_stride, 1, D, st);
             if (b > h->nhalf && h->skip_z_usable()) {   // skip_norm (static, over the 2 D columns of [x | skip]) in front of skip_linear; C' carries skip_linear.bias
-                const int j = b - h->nhalf - 1;
+                const ezdit_handle::ZTab tk = h->zt_skip_of(b - h->nhalf - 1);
                 launch_z_hilo(w.snw, w.snb, 0, zA, h->ld2D, 1, 2 * D, st);
                 gemm(c, zA, h->ld2D, w.wskip, nullptr, ztmp, D, 4, D, EPI_F32, 25);
-                launch_z_combine(ztmp, D, w.bskip, h->p.zt_skip + (long)j * 2 * D, h->p.zt_skip + (long)j * 2 * D + D, 0, 1, D, st);
+                launch_z_combine(ztmp, D, w.bskip, tk.G, tk.C, tk.slot_stride, 1, D, st);
             }
         }
         const hipError_t e = hipGetLastError();
@@ -989,113 +1055,89 @@ static int forward_impl(ezdit_handle* h, const float* x, int in_ch, int x_rows, 
     STOPCHK();
     launch_assemble(as, st);
     c.launched("k_assemble");
-    const float* part_src = part;
-    bool u_is_z = false;   // `u` holds A' = bf16(h g) + partial statistics (LayerNorm algebra) instead of a finished LayerNorm
-    bool* u_is_z_ptr = &u_is_z;
-    auto make_row = [&](int mode, const float* h_in, float* h_out, int nsplit, const float* bias, const float* gate,
-                        long gate_stride, const float* lg, const float* lc, long ln_stride, const float* skip, const float* cnp,
-                        int ld_u) {
+    // What `u` holds: null = a finished LayerNorm (written by the row kernel); otherwise A' = bf16(h g) of the LayerNorm algebra, and the pointer is where its producer
+    // put the partial statistics.  row() and edge() set it, the consumer sites read it
+    const float2* u_stat = nullptr;
+    // the row kernel of an edge: h_out = h_in + gate * (the sum of `nsplit` slabs + bias)  (mode 1; 2: no h_in, 0: h_in alone), then u = LN(h_out) ln_g + ln_c
+    auto row = [&](const Edge& e, int mode, const float* slabs, int nsplit) {
         RowArgs r;
         memset(&r, 0, sizeof r);
-        r.h_in = h_in; r.h_out = h_out;
-        r.part = part_src; r.nsplit = nsplit; r.part_stride = (long)Mp * D; r.ld_part = D;
-        r.part_bf16 = (part_src == part) ? 1 : 0;   // the split-K slabs are bf16
+        r.h_in = e.h_in; r.h_out = e.h_out;
+        r.part = slabs; r.nsplit = nsplit; r.part_stride = (long)Mp * D; r.ld_part = D;
+        r.part_bf16 = (slabs == part) ? 1 : 0;   // the split-K slabs are bf16
         r.cn_scale = cn_scale;
-        r.bias = bias; r.gate = gate; r.gate_slot_stride = gate_stride; r.mode = mode;
-        r.ln_g = lg; r.ln_c = lc; r.ln_slot_stride = ln_stride;
-        r.skip = skip; r.cn = cnp;
-        r.u = lg ? (skip ? p.ucat : u) : nullptr; r.ld_u = ld_u;
+        r.bias = e.bias; r.gate = e.gate; r.gate_slot_stride = e.gate_stride; r.mode = mode;
+        r.ln_g = e.ln_g; r.ln_c = e.ln_c; r.ln_slot_stride = e.ln_stride;
+        r.skip = e.skip; r.cn = e.cn;
+        r.u = e.ln_g ? (e.skip ? p.ucat : u) : nullptr; r.ld_u = e.skip ? h->ld2D : h->ldD;
         r.M = M; r.D = D; r.L = h->L;
         r.cur_step = cur; r.row_slot = row_slot; r.wt = h->wt();
         r.variant = h->opt_row_variant;
         r.affine = h->opt_row_affine && M <= 1024;
-        return r;
-    };
-    auto row = [&](int mode, const float* h_in, float* h_out, int nsplit, const float* bias, const float* gate,
-                   long gate_stride, const float* lg, const float* lc, long ln_stride, const float* skip, const float* cnp,
-                   int ld_u) {
-        const RowArgs r = make_row(mode, h_in, h_out, nsplit, bias, gate, gate_stride, lg, lc, ln_stride, skip, cnp, ld_u);
         launch_row(r, st);
         c.launched("k_row");
-        if (lg && !skip) u_is_z_ptr[0] = false;   // `u` now holds a finished LayerNorm
-    };
-    // residual GEMM + its row operator: out = rowop(A . W^T as split-K slabs): two launches (the one-launch form with an in-launch
-    // hand-off measured slower in round 2 and was removed)
-    auto resid = [&](const bf16_t* A, int lda, const WRef& w, int mode, const float* h_in, float* h_out, const float* bias, const float* gate,
-                     long gate_stride, const float* lg, const float* lc, long ln_stride, const float* skip, const float* cnp, int ld_u) {
-        const int s2 = gemm_partial(c, A, lda, w, M, D);
-        if (c.bad() || (h->debug_stop > 0 && h->launches >= h->debug_stop)) return;
-        row(mode, h_in, h_out, s2, bias, gate, gate_stride, lg, lc, ln_stride, skip, cnp, ld_u);
+        if (e.ln_g && !e.skip) u_stat = nullptr;   // `u` now holds a finished LayerNorm
     };
     auto modv = [&](int blk, int which) { return mod + ((long)blk * 6 + which) * D; };
-    // LayerNorm algebra (opt_zfuse): un-split residual projection whose epilogue produces h_new, its partial LayerNorm statistics and
-    // A' = bf16(h_new * zg) for the next GEMM; the consumer finishes the LayerNorm.  u_is_z tells the next consumer what `u` holds.
     const int qkv_mode = h->qkv_mode();   // 2: fused QKV GEMM (ping-pong kernel), 0: fp32 projection + k_headnorm
     const bool zf = h->z_tables_ready && h->zfuse_usable();
-    // eb0 / enb: the launch covers the batch elements [eb0, eb0 + enb) only (enb < 0: all); dual_blk >= 0: DUAL form for block dual_blk (GemmArgs.zd)
-    struct ZExtra {   // the skip path's forms of the un-split residual projection (GemmArgs: COPY2 / ZIN); whole-batch launches only
-        bf16_t* zu = nullptr; int ld_zu = 0;          // operand buffer instead of `u`
-        float2* zstat_out = nullptr;                  // statistics instead of the shared buffer
-        bf16_t* zu2 = nullptr; int ld_zu2 = 0; const float* zg2 = nullptr;   // COPY2
-        const float2 *zin = nullptr, *zin2 = nullptr; const float* zG = nullptr; int zparts = 0, zD = 0;   // ZIN
-    };
-    const float2* zstat_next = nullptr;   // where the last producer put its statistics when not in the shared buffer (handed to the next consumer: Ctx.zstat)
-    auto resid_z = [&](const bf16_t* A, int lda, const WRef& w, const float* h_in, float* h_out, const float* bias, const float* gate, long gate_stride,
-                       const float* zg, long zg_stride, const char* what, int eb0 = 0, int enb = -1, int dual_blk = -1, const ZExtra* zx = nullptr) {
-        const long r0 = (long)eb0 * h->L;
-        const int Ms = enb < 0 ? M : enb * h->L;
-        GemmArgs g;
-        memset(&g, 0, sizeof g);
-        g.A = A + r0 * lda; g.lda = lda; g.W = w.W; g.ldw = w.ld; g.wrows = w.rows; g.bias = bias;
-        g.out = h_out ? h_out + r0 * D : nullptr; g.ldo = D; g.M = Ms; g.N = D; g.K = w.ld; g.splitk = 1; g.epi = EPI_RESID; g.tile = h->ztile();
+    // The launches of one residual edge.  Not the LayerNorm algebra: the projection as split-K slabs + the row kernel that reduces them -- two launches (the one-launch
+    // form with an in-launch hand-off measured slower in round 2 and was removed), with the debug_stop / error check of STOPCHK between them.
+    // LayerNorm algebra (opt_zfuse): ONE un-split projection whose epilogue produces h_out, its partial LayerNorm statistics and A' = bf16(h_out ln_g) for the next
+    // GEMM, which finishes the LayerNorm
+    auto edge = [&](const Edge& e) {
+        if (!e.algebra) {
+            const int s2 = gemm_partial(c, e.A, e.lda, *e.w, M, D);
+            if (c.bad() || (h->debug_stop > 0 && h->launches >= h->debug_stop)) return;
+            row(e, e.h_in ? 1 : 2, part, s2);
+            return;
+        }
+        const long r0 = (long)e.b0 * h->L;
+        const int Ms = e.nb < 0 ? M : e.nb * h->L, K = e.w->ld;
+        int tile = h->ztile();
         // few rows (the cross-attention-out projection over one prompt's conditional rows, M = 500): 48-row tiles leave 11 x 12 = 132 workgroups for 256 CUs;
         // 32 x 96 tiles (id 72) give 16 x 12 = 192 with 11 % fewer operand bytes each: 3.968 -> 3.951 ms per step, bit-identical (profiles/r05_experiments.txt)
-        if (g.tile == ezdit_handle::kZTile && dual_blk < 0 && !(zx && (zx->zu2 || zx->zin2)) && Ms <= 672 && g.K <= 2 * D) g.tile = 72;
-        g.xcd_map = 1; g.wt = h->wt();
-        g.resid = h_in ? h_in + r0 * D : nullptr; g.ldr = D; g.gate = gate; g.gate_slot_stride = gate_stride;
-        g.cur_step = cur; g.row_slot = row_slot ? row_slot + eb0 : nullptr; g.rows_per_b = h->L;
-        g.zu = u + r0 * h->ldD; g.ld_zu = h->ldD; g.zg = zg; g.zg_slot_stride = zg_stride; g.zstat_out = p.zstat + r0; g.zs_stride = h->Mp;
-        if (dual_blk >= 0) {
-            g.zd = p.zd + (size_t)dual_blk * h->B * D; g.zd_stride = D;
-            g.zg2 = modv(dual_blk, 3); g.zg2_slot_stride = mod_slot;
+        if (tile == ezdit_handle::kZTile && e.dual_blk < 0 && !e.zu2 && !e.zin2 && Ms <= 672 && K <= 2 * D) tile = 72;
+        GemmArgs g = resid_args(tile, e.A + r0 * e.lda, e.lda, e.w->W, e.w->ld, e.w->rows, e.bias, e.h_in ? e.h_in + r0 * D : nullptr, e.gate, e.ln_g,
+                                e.h_out ? e.h_out + r0 * D : nullptr, e.zu ? e.zu : u + r0 * h->ldD, e.zu ? e.ld_zu : h->ldD,
+                                e.zstat_out ? e.zstat_out : p.zstat + r0, h->Mp, Ms, D, K);
+        g.wt = h->wt(); g.gate_slot_stride = e.gate_stride; g.zg_slot_stride = e.ln_stride;
+        g.cur_step = cur; g.row_slot = row_slot ? row_slot + e.b0 : nullptr; g.rows_per_b = h->L;
+        if (e.dual_blk >= 0) {
+            g.zd = p.zd + (size_t)e.dual_blk * h->B * D; g.zd_stride = D;
+            g.zg2 = modv(e.dual_blk, 3); g.zg2_slot_stride = mod_slot;
             g.act_row0 = h->act_b0 * h->L; g.act_row1 = h->act_b1 * h->L;
         }
-        zstat_next = nullptr;
-        if (zx) {
-            if (zx->zu) { g.zu = zx->zu; g.ld_zu = zx->ld_zu; }
-            if (zx->zstat_out) { g.zstat_out = zx->zstat_out; zstat_next = zx->zstat_out; }
-            g.zu2 = zx->zu2; g.ld_zu2 = zx->ld_zu2;
-            if (zx->zu2) { g.zg2 = zx->zg2; g.zg2_slot_stride = 0; }
-            if (zx->zin2) { g.zstat_in = zx->zin; g.zstat_in2 = zx->zin2; g.zG = zx->zG; g.zparts = zx->zparts; g.zD = zx->zD; g.zeps = 1e-5f; }
-        }
+        if (e.zu2) { g.zu2 = e.zu2; g.ld_zu2 = e.ld_zu2; g.zg2 = e.zg2; g.zg2_slot_stride = 0; }
+        if (e.zin2) { g.zstat_in = e.zin; g.zstat_in2 = e.zin2; g.zG = e.zG; g.zparts = h->zparts(); g.zD = 2 * D; g.zeps = 1e-5f; }
         g.ts = c.stamps(); g.ts_cap = g_gemm_ts_cap;
-        c.launched(what, launch_gemm(g, st));
-        u_is_z = true;
+        c.launched(e.name, launch_gemm(g, st));
+        if (!e.zu) u_stat = e.zstat_out ? e.zstat_out : p.zstat;   // `u` now holds A'
     };
     // LN_2D([x | skip]) -> skip_linear by the LayerNorm algebra (opt_skip_z): not with ControlNet residuals (they change the skips)
     const bool skipz = zf && h->skip_tables_ready && h->skip_z_usable() && !(cn && n_cn > 0);
-    const int zsp = (D + h->zwidth() - 1) / h->zwidth();                      // statistics parts of a D-wide producer
-    auto ucat_of = [&](int j) { return p.ucat_z + (size_t)j * Mp * h->ld2D; };   // operand [x | skip] of out-block j
-    auto zskip_of = [&](int i) { return p.zstat_skip + (size_t)i * Z_MAXP * Mp; };   // statistics of skip i
     // single-key shortcut (opt_xkey1): cross-attention + its out-projection cover the batch elements [xb0, xb0 + xnb) only
     const bool x1 = zf && h->opt_xkey1 && h->xkey1;
     const int xb0 = x1 ? h->act_b0 : 0, xnb = x1 ? h->act_b1 - h->act_b0 : h->B;
 
     // LN1 of block 0 on the patch embedding (ControlNet: x = patch_embed(x) + controlnet_pre(condition) first, :263-266)
     STOPCHK();
-    if (zf && !cn_mode) {
-        // LayerNorm algebra: the patch embed itself is the producer for block 0's norm1 (no gate, no residual: h = acc + bias, statistics, bf16(h g)) -- no row-kernel launch
-        resid_z(p.ape, h->ldPE, h->w_pe, nullptr, hA, h->b_pe, nullptr, 0, modv(0, 0), mod_slot, "k_gemm (un-split residual: patch embed)");
-    } else {
-    gemm(c, p.ape, h->ldPE, h->w_pe, h->b_pe, hA, D, M, D, EPI_F32, M <= 2048 ? ezdit_handle::kTilePE : tile_for(h, M, false));
-    STOPCHK();
-    if (cn_mode) {
-        part_src = p.cembed;
-        row(1, hA, hA, 1, nullptr, nullptr, 0, modv(0, 0), modv(0, 1), mod_slot, nullptr, nullptr, h->ldD);
-        part_src = part;
-    } else {
-        row(0, hA, nullptr, 0, nullptr, nullptr, 0, modv(0, 0), modv(0, 1), mod_slot, nullptr, nullptr, h->ldD);
-    }
+    {
+        Edge e;
+        e.name = "k_gemm (un-split residual: patch embed)"; e.algebra = zf && !cn_mode;
+        e.A = p.ape; e.lda = h->ldPE; e.w = &h->w_pe; e.bias = h->b_pe; e.h_out = hA;
+        e.ln_g = modv(0, 0); e.ln_c = modv(0, 1); e.ln_stride = mod_slot;
+        if (e.algebra) {
+            // the patch embed itself is the producer for block 0's norm1 (no gate, no residual: h = acc + bias, statistics, bf16(h g)) -- no row-kernel launch
+            edge(e);
+        } else {
+            // not a split-K edge: the K-split fp32 GEMM applies the bias itself, the row kernel adds the condition embed (ControlNet: one fp32 "slab") and normalises
+            gemm(c, e.A, e.lda, *e.w, e.bias, hA, D, M, D, EPI_F32, M <= 2048 ? ezdit_handle::kTilePE : tile_for(h, M, false));
+            STOPCHK();
+            e.bias = nullptr; e.h_in = hA;
+            if (cn_mode) row(e, 1, p.cembed, 1);
+            else { e.h_out = nullptr; row(e, 0, part, 0); }
+        }
     }
     const float* hcur = hA;
 
@@ -1105,13 +1147,16 @@ static int forward_impl(ezdit_handle* h, const float* x, int in_ch, int x_rows, 
         if (is_out) {
             // u holds LN_2D([x | skip]) -> skip_linear (blocks.py:124-128)
             STOPCHK();
-            if (skipz) {
-                const int j = b - nhalf - 1;
-                ZExtra zx;
-                zx.zin = p.zstat + (size_t)Z_MAXP * Mp; zx.zin2 = zskip_of(nhalf - 1 - j); zx.zG = p.zt_skip + (long)j * 2 * D; zx.zparts = zsp; zx.zD = 2 * D;
-                resid_z(ucat_of(j), h->ld2D, w.wskip, nullptr, hA, zx.zG + D, nullptr, 0, modv(b, 0), mod_slot, "k_gemm (un-split residual: skip_linear ZIN)", 0, -1, -1, &zx);
-            } else if (zf) resid_z(p.ucat, h->ld2D, w.wskip, nullptr, hA, w.bskip, nullptr, 0, modv(b, 0), mod_slot, "k_gemm (un-split residual: skip_linear)");
-            else resid(p.ucat, h->ld2D, w.wskip, 2, nullptr, hA, w.bskip, nullptr, 0, modv(b, 0), modv(b, 1), mod_slot, nullptr, nullptr, h->ldD);
+            const int j = b - nhalf - 1;
+            Edge e;
+            e.name = skipz ? "k_gemm (un-split residual: skip_linear ZIN)" : "k_gemm (un-split residual: skip_linear)"; e.algebra = zf;
+            e.A = skipz ? h->ucat_of(j) : p.ucat; e.lda = h->ld2D; e.w = &w.wskip; e.bias = w.bskip; e.h_out = hA;
+            e.ln_g = modv(b, 0); e.ln_c = modv(b, 1); e.ln_stride = mod_slot;
+            if (skipz) {   // the operand is bf16([x | skip] g): finish ITS LayerNorm from the halves' statistics and G'; C' (it carries skip_linear.bias) takes the bias' place
+                const ezdit_handle::ZTab t = h->zt_skip_of(j);
+                e.zin = h->zstat_xhalf(); e.zin2 = h->zstat_skip_of(nhalf - 1 - j); e.zG = t.G; e.bias = t.C;
+            }
+            edge(e);
             hcur = hA;
         }
         // ---- self attention (blocks.py:136-141) ----
@@ -1128,9 +1173,7 @@ static int forward_impl(ezdit_handle* h, const float* x, int in_ch, int x_rows, 
         if (qkv_mode) {
             // head-norm + RoPE + the attention layouts inside the projection GEMM (128 x two-head tiles): no fp32 q|k|v round trip, one launch less
             hn.perm = 1;   // (qkv_mode == 2 <=> the weights were packed with EZDIT_T_QKROPE)
-            c.hn = &hn;
-            if (u_is_z) { c.zG = p.zt_qkv + (long)b * 2 * 3 * D; c.zC = c.zG + 3 * D; c.zt_stride = (long)nblk * 2 * 3 * D; c.zstat = zstat_next; }
-            gemm(c, u, h->ldD, w.wqkv, nullptr, nullptr, 0, M, 3 * D, EPI_QKV, h->qkv_tile());
+            gemm(c, u, h->ldD, w.wqkv, nullptr, nullptr, 0, M, 3 * D, EPI_QKV, h->qkv_tile(), &hn, ZIn{h->zt_qkv_of(b), u_stat});
         } else {
             gemm(c, u, h->ldD, w.wqkv, nullptr, p.qkv, 3 * D, M, 3 * D, EPI_F32, tile_for(h, M, false));
             STOPCHK();
@@ -1148,11 +1191,14 @@ static int forward_impl(ezdit_handle* h, const float* x, int in_ch, int x_rows, 
         at.ts = c.stamps(); at.ts_cap = g_gemm_ts_cap;
         c.launched("k_attn (self)", launch_attention(at, st));
         STOPCHK();
-        // x += (1 - gate_msa) * (proj + bias); then norm2 (plain affine LN) for cross-attention q
-        if (zf) {
-            resid_z(at.out, h->ldD, w.wo, hcur, hA, w.bo, modv(b, 2), mod_slot, w.n2w, 0, x1 ? "k_gemm (un-split residual: attention-out DUAL)" : "k_gemm (un-split residual: attention-out)", 0, -1, x1 ? b : -1);
-        } else {
-            resid(at.out, h->ldD, w.wo, 1, hcur, hA, w.bo, modv(b, 2), mod_slot, w.n2w, w.n2b, 0, nullptr, nullptr, h->ldD);
+        {   // x += (1 - gate_msa) * (proj + bias); then norm2 (plain affine LN) for cross-attention q
+            Edge e;
+            e.name = x1 ? "k_gemm (un-split residual: attention-out DUAL)" : "k_gemm (un-split residual: attention-out)"; e.algebra = zf;
+            e.A = at.out; e.lda = h->ldD; e.w = &w.wo; e.bias = w.bo; e.h_in = hcur; e.h_out = hA;
+            e.gate = modv(b, 2); e.gate_stride = mod_slot;
+            e.ln_g = w.n2w; e.ln_c = w.n2b;
+            if (x1) e.dual_blk = b;
+            edge(e);
         }
         hcur = hA;
         // ---- cross attention (blocks.py:147-151) ----
@@ -1171,27 +1217,26 @@ static int forward_impl(ezdit_handle* h, const float* x, int in_ch, int x_rows, 
             hn.B = xnb; hn.H = h->H; hn.L = h->L; hn.Lp = h->Lp; hn.dh = h->dh;
             at.xu = nullptr; at.nkh = h->opt_attn_nkh;
             at.B = xnb; at.b0 = xb0;
+            const ZIn zq{h->zt_q2_of(b), u_stat, (int)xr0, xb0};   // norm2 -> to_q by the LayerNorm algebra (static tables)
             if (fuse_q2) {
                 at.xu = u; at.ldu = h->ldD; at.xw = w.wq2.W; at.ldw = w.wq2.ld;
                 at.xw_rows = w.wq2.rows; at.xK = at.ldw;
                 at.qn_w = hn.qn_w; at.qn_b = hn.qn_b; at.nkh = 4; at.xk2 = h->opt_attn_xk2; at.qtile = h->opt_attn_qtile;
 #ifdef EZ_DIAG
-                if (!u_is_z && h->opt_zfake && (D + h->zwidth() - 1) / h->zwidth() <= Z_MAXP) {
-                    at.zw = h->zwidth(); at.zstat_in = h->buf<float2>("zneutral"); at.zs_stride = h->Mp; at.zparts = (D + at.zw - 1) / at.zw; at.zD = D; at.zeps = 1e-5f;
+                if (!u_stat && h->opt_zfake && h->zparts() <= Z_MAXP) {
+                    at.zw = h->zwidth(); at.zstat_in = h->buf<float2>("zneutral"); at.zs_stride = h->Mp; at.zparts = h->zparts(); at.zD = D; at.zeps = 1e-5f;
                     at.zG = h->buf<float>("zzeros"); at.zC = at.zG;
                 }
 #endif
-                if (u_is_z) {
-                    at.zw = h->zwidth(); at.zstat_in = p.zstat; at.zs_stride = h->Mp; at.zparts = (D + at.zw - 1) / at.zw; at.zD = D; at.zeps = 1e-5f;
-                    at.zG = p.zt_q2 + (long)b * 2 * D; at.zC = at.zG + D;
+                if (u_stat) {
+                    at.zw = h->zwidth(); at.zstat_in = u_stat; at.zs_stride = h->Mp; at.zparts = h->zparts(); at.zD = D; at.zeps = 1e-5f;
+                    at.zG = zq.t.G; at.zC = zq.t.C;
                 }
             } else if (qkv_mode == 2 && h->opt_q2_pp) {
                 // batched prompts: the q projection on the ping-pong kernel with the fused-QKV epilogue restricted to its q part (N = D, no RoPE):
                 // per-head LayerNorm and the bf16 attention layout straight out of the GEMM -- no fp32 q round trip, no 128 x 64 tile at M = 4000
                 // (k_gemm<128,64> + normalisation inside k_attn: 30 us; this: one round of 256 workgroups).  LayerNorm-algebra capable (zt_q2 is static)
-                c.hn = &hn;
-                if (u_is_z) { c.zG = p.zt_q2 + (long)b * 2 * D; c.zC = c.zG + D; c.zt_stride = 0; c.zrow0 = (int)xr0; c.zb0 = xb0; }
-                gemm(c, u + xr0 * h->ldD, h->ldD, w.wq2, nullptr, nullptr, 0, xM, D, EPI_QKV, 61);
+                gemm(c, u + xr0 * h->ldD, h->ldD, w.wq2, nullptr, nullptr, 0, xM, D, EPI_QKV, 61, &hn, zq);
                 at.q = p.q;   // (launch_attention advances it by b0)
             } else {
                 gemm(c, u + xr0 * h->ldD, h->ldD, w.wq2, nullptr, p.qkv + xr0 * D, D, xM, D, EPI_F32, tile_for(h, xM, false));
@@ -1206,48 +1251,49 @@ static int forward_impl(ezdit_handle* h, const float* x, int in_ch, int x_rows, 
             at.ts = c.stamps(); at.ts_cap = g_gemm_ts_cap;
             c.launched("k_attn (cross)", launch_attention(at, st));
             STOPCHK();
-            if (zf) {
-                at.zstat_in = nullptr;
-                resid_z(at.out, h->ldD, w.wo2, hA, hA, w.bo2, nullptr, 0, modv(b, 3), mod_slot, "k_gemm (un-split residual: cross-out)", xb0, x1 ? xnb : -1);
-            } else {
-                resid(at.out, h->ldD, w.wo2, 1, hA, hA, w.bo2, nullptr, 0, modv(b, 3), modv(b, 4), mod_slot, nullptr, nullptr, h->ldD);
-            }
-            at.B = h->B; at.b0 = 0;
+            Edge e;
+            e.name = "k_gemm (un-split residual: cross-out)"; e.algebra = zf;
+            e.A = at.out; e.lda = h->ldD; e.w = &w.wo2; e.bias = w.bo2; e.h_in = hA; e.h_out = hA;
+            e.ln_g = modv(b, 3); e.ln_c = modv(b, 4); e.ln_stride = mod_slot;
+            e.b0 = xb0; if (x1) e.nb = xnb;
+            edge(e);
         }
         // ---- GEGLU MLP (blocks.py:154-156) ----
         STOPCHK();
-        if (u_is_z) { c.zG = p.zt_geglu + (long)b * 2 * 2 * h->I; c.zC = c.zG + 2 * h->I; c.zt_stride = (long)nblk * 2 * 2 * h->I; }
-        gemm(c, u, h->ldD, w.w1, w.b1, p.act, h->ldI, M, 2 * h->I, EPI_GEGLU, h->geglu_tile());   // 128 x 288 ping-pong kernel / 128 x 144 co-resident kernel / round-1 lockstep kernel
+        gemm(c, u, h->ldD, w.w1, w.b1, p.act, h->ldI, M, 2 * h->I, EPI_GEGLU, h->geglu_tile(), nullptr, ZIn{h->zt_geglu_of(b), u_stat});   // 128 x 288 ping-pong kernel / 128 x 144 co-resident kernel / round-1 lockstep kernel
         STOPCHK();
         // x += (1 - gate_mlp) * (mlp + bias); the LN that follows belongs to the NEXT consumer
-        const float* b2 = w.b2;
+        Edge e;
+        e.A = p.act; e.lda = h->ldI; e.w = &w.w2; e.bias = w.b2; e.h_in = hA;
+        e.gate = modv(b, 5); e.gate_stride = mod_slot;
         if (cn_mode && b == nblk - 1) {
-            resid(p.act, h->ldI, w.w2, 1, hA, skips + (size_t)b * Mp * D, b2, modv(b, 5), mod_slot, nullptr, nullptr, 0, nullptr, nullptr, h->ldD);
+            e.h_out = skips + (size_t)b * Mp * D;   // the ControlNet's last skip: no LayerNorm follows
         } else if (b == nblk - 1) {
-            const float* mf = p.modf;
-            resid(p.act, h->ldI, w.w2, 1, hA, nullptr, b2, modv(b, 5), mod_slot, mf, mf + D, 2L * D, nullptr, nullptr, h->ldD);
+            e.ln_g = p.modf; e.ln_c = p.modf + D; e.ln_stride = 2L * D;   // the final block's norm; its Linear is no LayerNorm-algebra consumer
         } else if (b + 1 > nhalf) {
             const int j = b + 1 - nhalf - 1;  // out block index of the consumer
-            const float* skip = skips + (size_t)(nhalf - 1 - j) * Mp * D;
             const float* cnp = (cn && n_cn > 0) ? cn[n_cn - 1 - j] : nullptr;
             if (cnp && cn_ready) { (void)hipStreamWaitEvent(st, cn_ready, 0); cn_ready = nullptr; }   // join the ControlNet stream
+            e.ln_g = h->blk[b + 1].snw; e.ln_c = h->blk[b + 1].snb;
+            e.algebra = skipz;
             if (skipz) {   // un-split: x_new only lives on as bf16(x_new g[:D]) in the left half of the out-block's operand, statistics in the second part range of the shared buffer
-                ZExtra zx;
-                zx.zu = ucat_of(j); zx.ld_zu = h->ld2D; zx.zstat_out = p.zstat + (size_t)Z_MAXP * Mp;
-                resid_z(p.act, h->ldI, w.w2, hA, nullptr, b2, modv(b, 5), mod_slot, h->blk[b + 1].snw, 0, "k_gemm (un-split residual: MLP-out -> [x | skip])", 0, -1, -1, &zx);
-            } else
-            resid(p.act, h->ldI, w.w2, 1, hA, nullptr, b2, modv(b, 5), mod_slot, h->blk[b + 1].snw, h->blk[b + 1].snb, 0, skip, cnp, h->ld2D);
+                e.name = "k_gemm (un-split residual: MLP-out -> [x | skip])";
+                e.zu = h->ucat_of(j); e.ld_zu = h->ld2D; e.zstat_out = h->zstat_xhalf();
+            } else {
+                e.skip = skips + (size_t)(nhalf - 1 - j) * Mp * D; e.cn = cnp;
+            }
         } else {
-            float* dst = is_in ? skips + (size_t)b * Mp * D : hA;
-            if (zf && skipz && is_in) {   // COPY2: + the skip half of the matching out-block's operand, statistics kept until that out-block
+            e.h_out = is_in ? skips + (size_t)b * Mp * D : hA;
+            e.ln_g = modv(b + 1, 0); e.ln_c = modv(b + 1, 1); e.ln_stride = mod_slot;
+            e.name = "k_gemm (un-split residual: MLP-out)"; e.algebra = zf;
+            if (skipz && is_in) {   // COPY2: + the skip half of the matching out-block's operand, statistics kept until that out-block
                 const int j = nhalf - 1 - b;
-                ZExtra zx;
-                zx.zstat_out = zskip_of(b); zx.zu2 = ucat_of(j) + D; zx.ld_zu2 = h->ld2D; zx.zg2 = h->blk[nhalf + 1 + j].snw + D;
-                resid_z(p.act, h->ldI, w.w2, hA, dst, b2, modv(b, 5), mod_slot, modv(b + 1, 0), mod_slot, "k_gemm (un-split residual: MLP-out COPY2)", 0, -1, -1, &zx);
-            } else if (zf) resid_z(p.act, h->ldI, w.w2, hA, dst, b2, modv(b, 5), mod_slot, modv(b + 1, 0), mod_slot, "k_gemm (un-split residual: MLP-out)");
-            else resid(p.act, h->ldI, w.w2, 1, hA, dst, b2, modv(b, 5), mod_slot, modv(b + 1, 0), modv(b + 1, 1), mod_slot, nullptr, nullptr, h->ldD);
-            hcur = dst;
+                e.name = "k_gemm (un-split residual: MLP-out COPY2)";
+                e.zstat_out = h->zstat_skip_of(b); e.zu2 = h->ucat_of(j) + D; e.ld_zu2 = h->ld2D; e.zg2 = h->blk[nhalf + 1 + j].snw + D;
+            }
+            hcur = e.h_out;
         }
+        edge(e);
     }
     if (cn_mode) {
         // controlnet_skips[i] = zero_Linear_i(skip_i) (* conditioning_scale, applied by the consumer)  controlnet.py:311-313
@@ -1534,11 +1580,9 @@ int ezdit_test_gemm(ezdit_handle* h, int variant, const void* A, int lda, const 
     }
     if (g.epi > EPI_GEGLU || g.tile > 127) return fail(EZDIT_E_INVALID, "bad gemm variant %d", variant);
     if (g.epi != EPI_PARTIAL) g.splitk = 1;
-    (void)hipGetLastError();
-    if (launch_gemm(g, (hipStream_t)stream)) return fail(EZDIT_E_UNSUPPORTED, "gemm variant %d not supported", variant);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of k_gemm failed: %s", hipGetErrorString(e));
-    return EZDIT_OK;
+    char config[32];
+    snprintf(config, sizeof config, "gemm variant %d", variant);
+    return hook_launch("k_gemm", config, [&] { return launch_gemm(g, (hipStream_t)stream); });
 }
 
 // EPI_RESID (un-split residual projection + partial LayerNorm statistics + next operand), stand-alone:
@@ -1546,18 +1590,9 @@ int ezdit_test_gemm(ezdit_handle* h, int variant, const void* A, int lda, const 
 int ezdit_test_resid(int tile, const void* A, int lda, const void* W, int ldw, const float* bias, const float* h_in, const float* gate, const float* zg,
                      float* h_out, void* zu, int ld_zu, void* zstat, int M, int N, int K, ezdit_stream stream) {
     if (K % 64) return fail(EZDIT_E_INVALID, "K=%d must be a multiple of 64", K);
-    GemmArgs g;
-    memset(&g, 0, sizeof g);
-    g.A = (const bf16_t*)A; g.lda = lda; g.W = (const bf16_t*)W; g.ldw = ldw; g.wrows = (int)rup(N, 128); g.bias = bias;
-    g.out = h_out; g.ldo = N; g.M = M; g.N = N; g.K = K; g.splitk = 1; g.epi = EPI_RESID; g.tile = tile; g.xcd_map = 1;
-    g.resid = h_in; g.ldr = N; g.gate = gate; g.rows_per_b = 1;
-    g.zu = (bf16_t*)zu; g.ld_zu = ld_zu; g.zg = zg; g.zstat_out = (float2*)zstat; g.zs_stride = M;   // zstat [N tiles][M]
+    GemmArgs g = resid_args(tile, (const bf16_t*)A, lda, (const bf16_t*)W, ldw, (int)rup(N, 128), bias, h_in, gate, zg, h_out, (bf16_t*)zu, ld_zu, (float2*)zstat, M, M, N, K);   // zstat [N tiles][M]
     g.ts = g_gemm_ts; g.ts_cap = g_gemm_ts_cap;
-    (void)hipGetLastError();
-    if (launch_gemm(g, (hipStream_t)stream)) return fail(EZDIT_E_UNSUPPORTED, "residual GEMM configuration not supported");
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of the residual GEMM failed: %s", hipGetErrorString(e));
-    return EZDIT_OK;
+    return hook_launch("the residual GEMM", "residual GEMM configuration", [&] { return launch_gemm(g, (hipStream_t)stream); });
 }
 
 // the skip path's forms of the same launch (GemmArgs COPY2 / ZIN), stand-alone:
@@ -1568,19 +1603,10 @@ int ezdit_test_resid_skip(int tile, const void* A, int lda, const void* W, int l
                           float* h_out, void* zu, int ld_zu, void* zstat, int M, int N, int K,
                           const float* zg2, void* zu2, int ld_zu2, const void* zstat_in, const void* zstat_in2, int zparts, int zD, const float* zG, ezdit_stream stream) {
     if (K % 64) return fail(EZDIT_E_INVALID, "K=%d must be a multiple of 64", K);
-    GemmArgs g;
-    memset(&g, 0, sizeof g);
-    g.A = (const bf16_t*)A; g.lda = lda; g.W = (const bf16_t*)W; g.ldw = ldw; g.wrows = (int)rup(N, 128); g.bias = bias;
-    g.out = h_out; g.ldo = N; g.M = M; g.N = N; g.K = K; g.splitk = 1; g.epi = EPI_RESID; g.tile = tile; g.xcd_map = 1;
-    g.resid = h_in; g.ldr = N; g.gate = gate; g.rows_per_b = 1;
-    g.zu = (bf16_t*)zu; g.ld_zu = ld_zu; g.zg = zg; g.zstat_out = (float2*)zstat; g.zs_stride = M;
+    GemmArgs g = resid_args(tile, (const bf16_t*)A, lda, (const bf16_t*)W, ldw, (int)rup(N, 128), bias, h_in, gate, zg, h_out, (bf16_t*)zu, ld_zu, (float2*)zstat, M, M, N, K);   // zstat [N tiles][M]
     g.zu2 = (bf16_t*)zu2; g.ld_zu2 = ld_zu2; g.zg2 = zg2;
     g.zstat_in = (const float2*)zstat_in; g.zstat_in2 = (const float2*)zstat_in2; g.zparts = zparts; g.zD = zD; g.zG = zG; g.zeps = 1e-5f;
-    (void)hipGetLastError();
-    if (launch_gemm(g, (hipStream_t)stream)) return fail(EZDIT_E_UNSUPPORTED, "residual GEMM configuration not supported");
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of the residual GEMM failed: %s", hipGetErrorString(e));
-    return EZDIT_OK;
+    return hook_launch("the residual GEMM", "residual GEMM configuration", [&] { return launch_gemm(g, (hipStream_t)stream); });
 }
 
 // the DUAL form of the same launch (GemmArgs.zd; the attention-out projection when single-key batch elements skip cross-attention), stand-alone: the rows OUTSIDE
@@ -1590,21 +1616,13 @@ int ezdit_test_resid_dual(int tile, const void* A, int lda, const void* W, int l
                           const float* zd, long zd_stride, const float* zg2, int act_row0, int act_row1, int rows_per_b, ezdit_stream stream) {
     if (K % 64) return fail(EZDIT_E_INVALID, "K=%d must be a multiple of 64", K);
     if (!zd || rows_per_b <= 0) return fail(EZDIT_E_INVALID, "the DUAL form needs zd and rows_per_b");
-    GemmArgs g;
-    memset(&g, 0, sizeof g);
-    g.A = (const bf16_t*)A; g.lda = lda; g.W = (const bf16_t*)W; g.ldw = ldw; g.wrows = (int)rup(N, 128); g.bias = bias;
-    g.out = h_out; g.ldo = N; g.M = M; g.N = N; g.K = K; g.splitk = 1; g.epi = EPI_RESID; g.tile = tile; g.xcd_map = 1;
-    g.resid = h_in; g.ldr = N; g.gate = gate; g.rows_per_b = rows_per_b;
-    g.zu = (bf16_t*)zu; g.ld_zu = ld_zu; g.zg = zg; g.zstat_out = (float2*)zstat; g.zs_stride = M;
+    GemmArgs g = resid_args(tile, (const bf16_t*)A, lda, (const bf16_t*)W, ldw, (int)rup(N, 128), bias, h_in, gate, zg, h_out, (bf16_t*)zu, ld_zu, (float2*)zstat, M, M, N, K);   // zstat [N tiles][M]
+    g.rows_per_b = rows_per_b;
     g.zd = zd; g.zd_stride = zd_stride; g.zg2 = zg2; g.act_row0 = act_row0; g.act_row1 = act_row1;
-    (void)hipGetLastError();
-    if (launch_gemm(g, (hipStream_t)stream)) return fail(EZDIT_E_UNSUPPORTED, "residual GEMM configuration not supported");
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of the residual GEMM failed: %s", hipGetErrorString(e));
-    return EZDIT_OK;
+    return hook_launch("the residual GEMM", "residual GEMM configuration", [&] { return launch_gemm(g, (hipStream_t)stream); });
 }
 
-// consumer side of the LayerNorm algebra, stand-alone (GemmArgs.z*: what gemm() above fills from Ctx.zG / zC / zstat): epi = EPI_GEGLU (out bf16 [M][ldo]) or EPI_QKV
+// consumer side of the LayerNorm algebra, stand-alone (GemmArgs.z*: what gemm() above fills from its ZIn): epi = EPI_GEGLU (out bf16 [M][ldo]) or EPI_QKV
 // (nothing goes to `out`; q / k / v in the attention layouts, HeadNormArgs) with  acc := r (acc - mu zG[slot][col]) + zC[slot][col]  in the epilogue, (mu, r) merged from the
 // part-major partial statistics zstat_in [zparts][zs_stride], slot = *cur_step + row_slot[row / rows_per_b] (NULL = 0 each).  EPI_QKV: perm = 1 with RoPE tables is the fused
 // q | k | v projection (N = 3 H dh, W rows packed by EZDIT_T_QKROPE), perm = 0 with k = v = NULL and no tables the q-only projection of batched prompts (N = H dh)
@@ -1630,21 +1648,13 @@ int ezdit_test_consumer(int tile, int epi, int epi_lds, const void* A, int lda, 
         hn.q = (bf16_t*)q; hn.k = (bf16_t*)k; hn.v = (bf16_t*)v;
         hn.B = B; hn.H = H; hn.L = L; hn.Lp = Lp; hn.dh = dh; hn.perm = perm;
     }
-    (void)hipGetLastError();
-    if (launch_gemm(g, (hipStream_t)stream)) return fail(EZDIT_E_UNSUPPORTED, "consumer GEMM configuration not supported");
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of the consumer GEMM failed: %s", hipGetErrorString(e));
-    return EZDIT_OK;
+    return hook_launch("the consumer GEMM", "consumer GEMM configuration", [&] { return launch_gemm(g, (hipStream_t)stream); });
 }
 
 // the RoPE tables as ezdit_bind_workspace fills them: cos / sin fp32 [max_len][dh / 2]
 int ezdit_test_rope_table(float* cosT, float* sinT, int max_len, int dh, ezdit_stream stream) {
     if (!cosT || !sinT || max_len <= 0 || dh <= 0 || dh % 2) return fail(EZDIT_E_INVALID, "bad RoPE table request");
-    (void)hipGetLastError();
-    launch_rope_table(cosT, sinT, max_len, dh, (hipStream_t)stream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of k_rope_table failed: %s", hipGetErrorString(e));
-    return EZDIT_OK;
+    return hook_launch("k_rope_table", "", [&] { launch_rope_table(cosT, sinT, max_len, dh, (hipStream_t)stream); return 0; });
 }
 
 // cross-attention with its own q projection and the LayerNorm algebra, stand-alone (the AttnArgs forward_impl builds for fuse_q2): q = LN_head(r (xu . xw_h^T - mu zG) + zC),
@@ -1662,11 +1672,7 @@ int ezdit_test_cross_attention(const void* xu, int ldu, const void* xw, int ldw,
     a.xu = (const bf16_t*)xu; a.ldu = ldu; a.xw = (const bf16_t*)xw; a.ldw = ldw; a.xw_rows = xw_rows; a.xK = xK;
     a.qn_w = qn_w; a.qn_b = qn_b; a.nkh = 4; a.xk2 = xk2; a.qtile = qtile; a.xcd_map = xcd_map;
     a.zstat_in = (const float2*)zstat_in; a.zs_stride = zs_stride; a.zparts = zparts; a.zD = zD; a.zw = zw; a.zG = zG; a.zC = zC; a.zeps = zeps;
-    (void)hipGetLastError();
-    if (launch_attention(a, (hipStream_t)stream)) return fail(EZDIT_E_UNSUPPORTED, "attention configuration not supported");
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of k_attn failed: %s", hipGetErrorString(e));
-    return EZDIT_OK;
+    return hook_launch("k_attn", "attention configuration", [&] { return launch_attention(a, (hipStream_t)stream); });
 }
 
 int ezdit_test_attention(ezdit_handle* h, const void* q, const void* k, const void* v, const uint8_t* kmask, void* out, int B,
@@ -1679,11 +1685,7 @@ int ezdit_test_attention(ezdit_handle* h, const void* q, const void* k, const vo
     a.out = (bf16_t*)out; a.ldo = h->ldD;
     a.B = B; a.H = h->H; a.Lq = Lq; a.Lk = Lk; a.Lqp = Lqp; a.Lkp = Lkp; a.dh = h->dh;
     a.ts = g_gemm_ts; a.ts_cap = g_gemm_ts_cap;
-    (void)hipGetLastError();
-    if (launch_attention(a, (hipStream_t)stream)) return fail(EZDIT_E_UNSUPPORTED, "attention configuration not supported");
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of k_attn failed: %s", hipGetErrorString(e));
-    return EZDIT_OK;
+    return hook_launch("k_attn", "attention configuration", [&] { return launch_attention(a, (hipStream_t)stream); });
 }
 
 int ezdit_test_attention_varlen(ezdit_handle* h, const void* q, const void* k, const void* v, const uint8_t* kmask, void* out, int B,
@@ -1705,11 +1707,7 @@ int ezdit_test_attention_varlen(ezdit_handle* h, const void* q, const void* k, c
     a.out = (bf16_t*)out; a.ldo = h->ldD;
     a.B = B; a.H = h->H; a.Lq = Lq; a.Lk = Lk; a.Lqp = Lqp; a.Lkp = Lkp; a.dh = h->dh;
     a.klen = dev_klen;
-    (void)hipGetLastError();
-    if (launch_attention(a, (hipStream_t)stream)) return fail(EZDIT_E_UNSUPPORTED, "attention configuration not supported");
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of k_attn failed: %s", hipGetErrorString(e));
-    return EZDIT_OK;
+    return hook_launch("k_attn", "attention configuration", [&] { return launch_attention(a, (hipStream_t)stream); });
 }
 
 int ezdit_test_final_conv(const float* y, int ldy, const float* w, const float* b, float* out, int B, int C, int L, const int32_t* dev_lens,
@@ -1727,11 +1725,7 @@ int ezdit_test_final_conv(const float* y, int ldy, const float* w, const float* 
     }
     FinalConvArgs fc;
     fc.y = y; fc.ldy = ldy; fc.w = w; fc.b = b; fc.out = out; fc.B = B; fc.C = C; fc.L = L; fc.lens = dev_lens;
-    (void)hipGetLastError();
-    launch_final_conv(fc, (hipStream_t)stream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of k_final_conv failed: %s", hipGetErrorString(e));
-    return EZDIT_OK;
+    return hook_launch("k_final_conv", "", [&] { launch_final_conv(fc, (hipStream_t)stream); return 0; });
 }
 
 int ezdit_debug_buffer(ezdit_handle* h, const char* name, void** ptr, size_t* bytes) {
