@@ -21,6 +21,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch / t
     if name in ('EzAudio_ControlNet',):
         from .api import EzAudio_ControlNet
         return EzAudio_ControlNet
+    if name in ('T5Encoder',):
+        from .t5 import T5Encoder
+        return T5Encoder
     if name in ('inference', 'inference_controlnet', 'LatentSampler'):
         from . import sampler
         return getattr(sampler, name)

@@ -101,6 +101,35 @@ PROTOTYPES = {
     'ezdit_set_option': (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
 }
 
+
+class Ezt5Config(C.Structure):
+    _fields_ = [('vocab', C.c_int32), ('d_model', C.c_int32), ('d_kv', C.c_int32), ('num_heads', C.c_int32), ('d_ff', C.c_int32),
+                ('num_layers', C.c_int32), ('num_buckets', C.c_int32), ('max_distance', C.c_int32), ('eps', C.c_float),
+                ('max_len', C.c_int32), ('ff_act', C.c_int32)]
+
+
+class Ezt5TensorInfo(C.Structure):
+    _fields_ = [('name', C.c_char * 32), ('dtype', C.c_int32), ('reserved', C.c_int32), ('rows', C.c_int64), ('cols', C.c_int64),
+                ('offset', C.c_int64)]
+
+
+FF_GATED_GELU_NEW, FF_RELU, FF_GATED_GELU, FF_OTHER = 0, 1, 2, 3
+
+# the T5 encoder section of the header (ezt5_*), bound by load() like the table above
+T5_PROTOTYPES = {
+    'ezt5_create': (C.c_int, [C.POINTER(Ezt5Config), C.POINTER(C.c_void_p)]),
+    'ezt5_destroy': (C.c_int, [C.c_void_p]),
+    'ezt5_tensor_count': (C.c_int, [C.c_void_p]),
+    'ezt5_blob_bytes': (C.c_size_t, [C.c_void_p, C.POINTER(Ezt5TensorInfo), C.c_int]),
+    'ezt5_bind_weights': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    'ezt5_workspace_bytes': (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    'ezt5_bind_workspace': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int]),
+    'ezt5_encode': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    'ezt5_test_attention': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                      C.c_void_p]),
+    'ezt5_test_rms': (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -120,7 +149,7 @@ def load():
         raise EzditError(f'{LIB_PATH} is missing: the HIP extension has not been built '
                          f'(python -m ezaudio_amd.build). There is no CPU fallback.')
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in PROTOTYPES.items():
+    for name, (res, args) in list(PROTOTYPES.items()) + list(T5_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -21,7 +21,7 @@ MAX_SEED = np.iinfo(np.int32).max
 
 class EzAudio:
     def __init__(self, model_name, ckpt_path=None, vae_path=None, device='cuda',
-                 autoencoder=None, tokenizer=None, text_encoder=None, state_dict=None):
+                 autoencoder=None, tokenizer=None, text_encoder=None, state_dict=None, native_text_encoder=False):
         self.device = device
         config_name = configs[model_name]['config']
         if ckpt_path is None and state_dict is None:
@@ -30,7 +30,7 @@ class EzAudio:
             vae_path = self.download_ckpt(configs['vae'])
         (self.autoencoder, self.unet, self.tokenizer, self.text_encoder, self.noise_scheduler,
          self.params) = self.load_models(config_name, ckpt_path, vae_path, device, autoencoder, tokenizer,
-                                         text_encoder, state_dict)
+                                         text_encoder, state_dict, native_text_encoder=native_text_encoder)
 
     def download_ckpt(self, model_dict):
         """api/ezaudio.py:44-65."""
@@ -55,8 +55,9 @@ class EzAudio:
         return local_path
 
     def load_models(self, config_name, ckpt_path, vae_path, device, autoencoder=None, tokenizer=None,
-                    text_encoder=None, state_dict=None):
-        """api/ezaudio.py:68-99."""
+                    text_encoder=None, state_dict=None, native_text_encoder=False):
+        """api/ezaudio.py:68-99.  native_text_encoder: when no encoder is injected, the T5 weights are loaded as the reference loads them,
+        converted to the HIP encoder (ezaudio_amd/t5.py) and the transformers model is released."""
         params = load_yaml_with_includes(config_name)
         if autoencoder is None:   # api/ezaudio.py:75-79; an injected callable with the same surface is also accepted
             from .vae import Autoencoder
@@ -65,7 +66,14 @@ class EzAudio:
         if tokenizer is None or text_encoder is None:
             from transformers import T5EncoderModel, T5Tokenizer
             tokenizer = T5Tokenizer.from_pretrained(params['text_encoder']['model'])
-            text_encoder = T5EncoderModel.from_pretrained(params['text_encoder']['model']).to(device)
+            text_encoder = T5EncoderModel.from_pretrained(params['text_encoder']['model'])
+            if native_text_encoder:
+                from .t5 import T5Encoder
+                hf, text_encoder = text_encoder, None
+                text_encoder = T5Encoder.from_hf(hf, device, max_len=max(512, int(params['text_encoder']['max_length'])))
+                del hf
+            else:
+                text_encoder = text_encoder.to(device)
             text_encoder.eval()
         unet = MaskDiT(device=device, **params['model'])
         if state_dict is None:
@@ -152,7 +160,7 @@ class EzAudio_ControlNet(EzAudio):
     """api/controlnet.py:31-160: EzAudio-L + energy ControlNet (``model_name='energy'``)."""
 
     def __init__(self, model_name, ckpt_path=None, controlnet_path=None, vae_path=None, device='cuda', autoencoder=None,
-                 tokenizer=None, text_encoder=None, state_dict=None, controlnet_state_dict=None):
+                 tokenizer=None, text_encoder=None, state_dict=None, controlnet_state_dict=None, native_text_encoder=False):
         self.device = device
         config_name = controlnet_configs[model_name]['config']
         if ckpt_path is None and state_dict is None:
@@ -163,7 +171,7 @@ class EzAudio_ControlNet(EzAudio):
             vae_path = self.download_ckpt(controlnet_configs['vae'])
         (self.autoencoder, self.unet, self.tokenizer, self.text_encoder, self.noise_scheduler,
          self.params) = self.load_models(config_name, ckpt_path, vae_path, device, autoencoder, tokenizer, text_encoder,
-                                         state_dict)
+                                         state_dict, native_text_encoder=native_text_encoder)
         from .conditions import Conditioner
         from .controlnet import DiTControlNet
         cfg = self.params['model'].copy()

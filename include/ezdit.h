@@ -335,6 +335,69 @@ int ezdit_debug_stop_after(ezdit_handle* h, int n_launches);
  * LayerNorm with neutral tables (what the consumer side costs by itself; results change by the factor rsqrt(1 + 1e-5)). */
 int ezdit_set_option(ezdit_handle* h, const char* name, int value);
 
+/* ---- T5 text encoder (csrc/t5.hip): stands in for transformers' T5EncoderModel in the `text_encoder` slot (api/ezaudio.py:80-82, src/inference.py:42-50) --------
+ * Encoder stacks of the flan-t5 / T5 v1.1 family only: gated gelu_new feed-forward, head dim 64, no biases, T5LayerNorm (RMS), the bidirectional
+ * relative-position bias of block 0 shared by all layers.  Same conventions as above: caller-owned device memory (one weight blob, one workspace per
+ * (B, L)), errors through ezdit_last_error(), ezt5_encode asynchronous on its stream (capturable).  The tokenizer stays outside.
+ * Nothing below touches an ezdit_handle; the ABI version is unchanged (additive). */
+typedef struct ezt5_handle ezt5_handle;
+enum { EZT5_FF_GATED_GELU_NEW = 0, EZT5_FF_RELU = 1, EZT5_FF_GATED_GELU = 2, EZT5_FF_OTHER = 3 };   /* only the first is built */
+typedef struct {
+    int32_t vocab;         /* rows of the token embedding (shared.weight) */
+    int32_t d_model;       /* multiple of 64 */
+    int32_t d_kv;          /* head dim: 64 */
+    int32_t num_heads;     /* inner width = num_heads * d_kv (need not equal d_model) */
+    int32_t d_ff;          /* multiple of 64 */
+    int32_t num_layers;
+    int32_t num_buckets;   /* relative_attention_num_buckets (32) */
+    int32_t max_distance;  /* relative_attention_max_distance (128) */
+    float   eps;           /* layer_norm_epsilon */
+    int32_t max_len;       /* longest token sequence (<= 512): the expanded bias table covers the distances -(max_len - 1) .. max_len - 1 */
+    int32_t ff_act;        /* EZT5_FF_*: feed_forward_proj of the checkpoint; anything but gated gelu_new is EZDIT_E_UNSUPPORTED */
+} ezt5_config;
+/* one tensor of the weight blob.  Names / shapes / sources (Hugging Face T5EncoderModel keys, N = layer):
+ *   embed        f32  [vocab][d_model]             shared.weight (= encoder.embed_tokens.weight)
+ *   bias_table   f32  [num_heads][2 max_len - 1]   entry [h][(key - query) + max_len - 1] = encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight
+ *                                                  [bucket(key - query)][h], bucket() = T5Attention._relative_position_bucket, bidirectional (expanded once, by the packer)
+ *   blkN.ln0     f32  [d_model]                    encoder.block.N.layer.0.layer_norm.weight
+ *   blkN.wqkv    bf16 [3 inner][d_model]           ...layer.0.SelfAttention.{q, k, v}.weight stacked along dim 0
+ *   blkN.wo      bf16 [d_model][inner]             ...layer.0.SelfAttention.o.weight
+ *   blkN.ln1     f32  [d_model]                    encoder.block.N.layer.1.layer_norm.weight
+ *   blkN.wi      bf16 [2 d_ff][d_model]            ...layer.1.DenseReluDense.{wi_0, wi_1}.weight stacked along dim 0
+ *   blkN.wff     bf16 [d_model][d_ff]              ...layer.1.DenseReluDense.wo.weight
+ *   final_ln     f32  [d_model]                    encoder.final_layer_norm.weight
+ * Every matrix is stored row-major and unpadded ([rows][cols]); offsets are 256-byte aligned. */
+typedef struct {
+    char    name[32];
+    int32_t dtype;         /* EZDIT_P_* */
+    int32_t reserved;
+    int64_t rows, cols;
+    int64_t offset;        /* byte offset in the blob */
+} ezt5_tensor_info_t;
+
+/* EZDIT_E_UNSUPPORTED (nothing allocated): d_kv != 64; d_model, d_ff or num_heads * d_kv not a multiple of 64; ff_act != EZT5_FF_GATED_GELU_NEW; max_len > 512 */
+int    ezt5_create(const ezt5_config* cfg, ezt5_handle** out);
+int    ezt5_destroy(ezt5_handle* h);
+int    ezt5_tensor_count(const ezt5_handle* h);
+/* bytes of the weight blob; `table` (nullable) receives the first `capacity` entries of the tensor table, in blob order */
+size_t ezt5_blob_bytes(const ezt5_handle* h, ezt5_tensor_info_t* table, int capacity);
+int    ezt5_bind_weights(ezt5_handle* h, const void* dev_blob, size_t bytes);
+/* activations of one encode of B sequences of L tokens (0 + error message: L > max_len, or rows x widest activation >= 2^31 elements) */
+size_t ezt5_workspace_bytes(const ezt5_handle* h, int B, int L);
+/* also decides the four GEMM shapes of a layer at B * L rows: EZDIT_E_UNSUPPORTED for one the GEMM refuses, so that ezt5_encode meets none */
+int    ezt5_bind_workspace(ezt5_handle* h, void* dev_ws, size_t bytes, int B, int L);
+/* last_hidden_state: ids int32 [B][L], mask uint8 [B][L] (1 = attend; HF attention_mask) -> out fp32 [B][L][d_model].  Masked keys contribute exactly 0; rows at masked
+ * positions are computed like any other (finite).  (B, L) must be the bound workspace's: EZDIT_E_STATE otherwise, and without weights; L > max_len: EZDIT_E_UNSUPPORTED.
+ * A device index beyond the GEMM's 32 per-device slots: EZDIT_E_UNSUPPORTED.  Nothing is launched when an error other than EZDIT_E_HIP is returned
+ * (EZDIT_E_HIP: a launch failed, or the runtime refused a GEMM's LDS attribute, possibly after earlier launches of the same encode). */
+int    ezt5_encode(ezt5_handle* h, const int32_t* dev_ids, const uint8_t* dev_mask, float* dev_out, int B, int L, ezdit_stream stream);
+/* unit-test hooks (same kernels; two, one per new kernel that a test must reach below ezt5_encode): k_t5_attn on q, k, v bf16 [B L][64 H] (head h in columns [64 h, 64 h + 64)), bias fp32 [H][2 L - 1] (entry (key - query) + L - 1),
+ * mask uint8 [B][L] -> out bf16 [B L][64 H] = softmax(q k^T + bias + mask) v, no 1 / sqrt(d) scale, L <= 512 ... */
+int    ezt5_test_attention(const void* dev_q, const void* dev_k, const void* dev_v, const float* dev_bias, const uint8_t* dev_mask, void* dev_out,
+                           int B, int H, int L, ezdit_stream stream);
+/* ... and k_t5_embed_rms on x fp32 [M][D] (D % 4 == 0), w fp32 [D] -> out bf16 [M][D] = bf16(x rsqrt(mean(x^2) + eps) w) */
+int    ezt5_test_rms(const float* dev_x, const float* dev_w, float eps, void* dev_out, int M, int D, ezdit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
