@@ -87,8 +87,16 @@ class EzAudio:
                        random_seed=None, randomize_seed=False):
         """api/ezaudio.py:101-130.  `text` may also be a list of prompts (batched extension): the result is then
         an array [N, T].  With a list of prompts `length` may be a list too, one duration in seconds per prompt (mixed-length
-        batch, one call): the result is then (sr, [one 1-D array per prompt]), each trimmed to its own duration."""
+        batch, one call): the result is then (sr, [one 1-D array per prompt]), each trimmed to its own duration.
+        `guidance_scale`, `guidance_rescale`, `eta` and `random_seed` may be lists as well, one entry per prompt of the list `text`: every
+        prompt is sampled as the call with it alone would sample it (return shapes unchanged).  A prompt '' inside a list runs without
+        guidance (the "empty input" rule per prompt); `randomize_seed` draws one seed per prompt of a list."""
         neg_text = None
+        for name, v in (('guidance_scale', guidance_scale), ('guidance_rescale', guidance_rescale), ('eta', eta), ('random_seed', random_seed)):
+            if isinstance(v, (list, tuple)) and (isinstance(text, str) or len(v) != len(text)):
+                raise ValueError(f'a list of {name} needs a list of prompts of the same size')
+        if isinstance(ddim_steps, (list, tuple)):
+            raise ValueError('ddim_steps must be one value per call: per-prompt step counts are not supported')
         latent_sr = self.params['autoencoder']['latent_sr']
         per_prompt = isinstance(length, (list, tuple))
         if per_prompt:
@@ -101,8 +109,12 @@ class EzAudio:
         if text == '':
             guidance_scale = None
             print('empty input')
+        elif not isinstance(text, str) and '' in text:
+            gs = list(guidance_scale) if isinstance(guidance_scale, (list, tuple)) else [guidance_scale] * len(text)
+            guidance_scale = [None if t == '' else g for t, g in zip(text, gs)]
+            print('empty input')
         if randomize_seed:
-            random_seed = random.randint(0, MAX_SEED)
+            random_seed = random.randint(0, MAX_SEED) if isinstance(text, str) else [random.randint(0, MAX_SEED) for _ in text]
         pred = inference(self.autoencoder, self.unet, gt, gt_mask, self.tokenizer, self.text_encoder, self.params,
                          self.noise_scheduler, text, neg_text, length, guidance_scale, guidance_rescale, ddim_steps,
                          eta, random_seed, self.device)

@@ -6,6 +6,7 @@
 #include "../../include/ezdit.h"
 #include "common.h"
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -58,6 +59,7 @@ struct WsPtrs {  // workspace regions used on the per-step path, resolved once a
     float2* zstat; float *zt_qkv, *zt_geglu, *zt_q2;   // LayerNorm algebra: partial row statistics, G' / C' tables
     float2* zstat_skip; float* zt_skip; bf16_t* ucat_z;              // ... of the out-blocks' LN_2D([x | skip]) -> skip_linear: the skips' statistics (kept from the in-block to its out-block), static tables
     int* lens;   // [B] per-batch-element valid frames (ezdit_set_lengths); read by the kernels only while ezdit_handle::lens_on
+    float *spg, *spc;   // per-sample sampler settings (ezdit_sampler_set_sample_params): [P][2] (guidance_scale, guidance_rescale) and [n_steps][P][8] DDIM coefficients; read only while sp_on
     float* zd;   // [nblk][B][D] constant cross-attention-out vectors of the single-key batch elements (opt_xkey1)
 };
 
@@ -101,6 +103,11 @@ struct ezdit_handle {
     bool lens_on = false;
     std::vector<int> lens;       // host mirror, expanded to B entries (the source of the asynchronous upload: must outlive it)
     const int* lens_dev() const { return lens_on ? p.lens : nullptr; }
+    // per-sample sampler settings (ezdit_sampler_set_sample_params), the same contract: k_cfg_stats / k_cfg_apply read the device table at run time, a captured step serves
+    // every set of values, switching the table on or off changes kernel arguments and drops the graph.  Room for sp_cap(B) samples: the B / 2 of a CFG batch
+    bool sp_on = false;
+    std::vector<float> sp_host;   // host mirror: [P][2] then [n_steps][P][8] (the source of the asynchronous upload)
+    static int sp_cap(int B) { return B / 2 + 1; }
 
     int launches = 0;
     bool is_cn = false;          // ControlNet variant (cfg.controlnet)
@@ -464,6 +471,8 @@ size_t carve(const ezdit_handle* h, int B, int L, int Lc, int n_slots, std::map<
         add("zstat_skip", nskip * zr * 8);
         add("zt_skip", (size_t)ezdit_handle::ztab_floats((int)nskip, D) * 4);
         add("lens", 256 * sizeof(int));   // per-batch-element valid frames of a padded batch (B <= 240), behind everything else for the same reason
+        add("spg", (size_t)ezdit_handle::sp_cap(B) * 2 * 4);        // per-sample sampler settings, at the very end (no existing buffer moves): at most
+        add("spc", (size_t)ns * ezdit_handle::sp_cap(B) * 8 * 4);   // n_slots * (B / 2 + 1) * 32 bytes + 2 KB more workspace than without them
     }
     return off;
 }
@@ -644,7 +653,7 @@ void resolve_workspace(ezdit_handle* h) {
     p.ao = h->buf<bf16_t>("ao"); p.act = h->buf<bf16_t>("act"); p.part = h->buf<float>("part"); p.y = h->buf<float>("y");
     p.pred = h->buf<float>("pred"); p.kmask = h->buf<uint8_t>("kmask"); p.kc = h->buf<bf16_t>("kc"); p.vc = h->buf<bf16_t>("vc");
     p.mod = h->buf<float>("mod"); p.modf = h->buf<float>("modf");
-    p.zd = h->buf<float>("zd"); p.lens = h->buf<int>("lens");
+    p.zd = h->buf<float>("zd"); p.lens = h->buf<int>("lens"); p.spg = h->buf<float>("spg"); p.spc = h->buf<float>("spc");
     p.zstat = h->buf<float2>("zstat"); p.zt_qkv = h->buf<float>("zt_qkv"); p.zt_geglu = h->buf<float>("zt_geglu"); p.zt_q2 = h->buf<float>("zt_q2");
     p.zstat_skip = h->buf<float2>("zstat_skip"); p.zt_skip = h->buf<float>("zt_skip"); p.ucat_z = h->buf<bf16_t>("ucat_z");
     if (h->is_cn) { p.cembed = h->buf<float>("cembed"); p.cnres = h->buf<float>("cnres"); p.skipbf = h->buf<bf16_t>("skipbf"); }
@@ -778,6 +787,7 @@ int ezdit_bind_workspace(ezdit_handle* h, void* ws, size_t bytes, int B, int L, 
     h->steps_done = 0;
     h->ctx_ready = h->ts_ready = h->cond_ready = false;
     h->lens_on = false; h->lens.clear();
+    h->sp_on = false;
     drop_graph(h);
     for (ezdit_handle* u : h->cn_users) drop_graph(u);   // a graph captured with this ControlNet attached points at its old buffers
     // zero everything once: all padding rows / columns / keys stay zero for the lifetime of the binding
@@ -1438,6 +1448,7 @@ int ezdit_sampler_begin(ezdit_handle* h, float* latents, int P, const float* noi
     h->steps_done = 0;
     h->latents = latents; h->noise = noise; h->P = P; h->n_steps = n_steps;
     h->gscale = guidance_scale; h->grescale = guidance_rescale;
+    h->sp_on = false;   // per-sample settings belong to one sampler call (the graph is dropped below anyway)
     h->s_gt = gt; h->s_gt_mask = gt_mask;
     if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
     if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
@@ -1486,8 +1497,9 @@ static int sampler_step(ezdit_handle* h, hipStream_t st) {
     a.P = h->P; a.n = h->C * h->L;
     a.step_inc = h->p.ints; a.done = reinterpret_cast<unsigned*>(h->p.ints + 8);
     a.lens = h->lens_dev(); a.L = h->L;
+    a.sp_g = h->sp_on ? h->p.spg : nullptr; a.sp_c = h->sp_on ? h->p.spc : nullptr; a.sp_g_stride = 2;
     launch_cfg_ddim(a, h->p.cfgpart, st);   // its last kernel also advances the device step counter
-    h->launches += (h->gscale > 0.f && h->grescale > 0.f) ? 2 : 1;
+    h->launches += (h->sp_on || (h->gscale > 0.f && h->grescale > 0.f)) ? 2 : 1;
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of k_cfg_* failed: %s", hipGetErrorString(e));
     return EZDIT_OK;
@@ -1506,7 +1518,68 @@ int ezdit_cfg_ddim_step(const float* pred, float* latents, const float* noise, c
     a.P = P; a.n = n;
     a.step_inc = nullptr; a.done = nullptr;
     a.lens = nullptr; a.L = n;
+    a.sp_g = nullptr; a.sp_c = nullptr; a.sp_g_stride = 0;
     launch_cfg_ddim(a, scratch, (hipStream_t)stream);
+    return EZDIT_OK;
+}
+
+// The per-sample form of the operator above: params fp32 [P][8] ON THE DEVICE = (guidance_scale, guidance_rescale, sa, sb, c_x0, c_dir, sigma, 0) of each
+// sample; pred is [2 P][n] always (the unconditional row of a sample with guidance_scale <= 0 is not read), lens (nullable, device) as ezdit_set_lengths.
+int ezdit_cfg_ddim_step_per_sample(const float* pred, float* latents, const float* noise, const float* params, const int32_t* lens, int L, int P, int n,
+                                   float* scratch, ezdit_stream stream) {
+    if (!pred || !latents || !params || P < 1 || n < 2) return fail(EZDIT_E_INVALID, "bad argument");
+    if (!scratch) return fail(EZDIT_E_INVALID, "the per-sample step needs %d scratch floats", P * 256);
+    if (lens && (L < 1 || n % L)) return fail(EZDIT_E_INVALID, "lens given: L = %d must divide n = %d", L, n);
+    CfgDdimArgs a;
+    a.pred = pred; a.latents = latents; a.noise = noise; a.coef = nullptr; a.cur_step = nullptr;
+    for (float& v : a.hc) v = 0.f;
+    a.guidance_scale = 0.f; a.guidance_rescale = 0.f;
+    a.P = P; a.n = n;
+    a.step_inc = nullptr; a.done = nullptr;
+    a.lens = lens; a.L = lens ? L : n;
+    a.sp_g = params; a.sp_c = params + 2; a.sp_g_stride = 8;
+    return hook_launch("k_cfg_*", "", [&] { launch_cfg_ddim(a, scratch, (hipStream_t)stream); return 0; });
+}
+
+int ezdit_sampler_set_sample_params(ezdit_handle* h, const float* guidance_scale, const float* guidance_rescale, const ezdit_ddim_coef* coefs, int P,
+                                    ezdit_stream stream) {
+    if (!h) return fail(EZDIT_E_INVALID, "null handle");
+    if (!h->ws || !h->latents) return fail(EZDIT_E_STATE, "ezdit_sampler_begin first");
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    if (cs != hipStreamCaptureStatusNone) return fail(EZDIT_E_STATE, "ezdit_sampler_set_sample_params inside a stream capture (it uploads from host memory and waits)");
+    if ((!guidance_scale && !guidance_rescale && !coefs) || P == 0) {
+        if (h->sp_on) drop_graph(h);
+        h->sp_on = false;
+        return EZDIT_OK;
+    }
+    if (!guidance_scale || !guidance_rescale || !coefs) return fail(EZDIT_E_INVALID, "guidance_scale, guidance_rescale and coefs must be given together");
+    if (P != h->P) return fail(EZDIT_E_INVALID, "P = %d, the sampler was begun with P = %d", P, h->P);
+    if (P > ezdit_handle::sp_cap(h->B)) return fail(EZDIT_E_UNSUPPORTED, "per-sample settings for %d samples: a workspace of B = %d has room for %d", P, h->B, ezdit_handle::sp_cap(h->B));
+    const int ns = h->n_steps;
+    std::vector<float> v((size_t)P * 2 + (size_t)ns * P * 8, 0.f);
+    for (int p = 0; p < P; ++p) {
+        if (!std::isfinite(guidance_scale[p]) || !std::isfinite(guidance_rescale[p])) return fail(EZDIT_E_INVALID, "non-finite guidance of sample %d", p);
+        if (guidance_scale[p] > 0.f && h->B != 2 * P)
+            return fail(EZDIT_E_INVALID, "guidance_scale[%d] = %g on a sampler begun without CFG rows (B = P = %d)", p, (double)guidance_scale[p], P);
+        v[p * 2 + 0] = guidance_scale[p]; v[p * 2 + 1] = guidance_rescale[p];
+    }
+    float* c = v.data() + (size_t)P * 2;
+    for (long i = 0; i < (long)ns * P; ++i) {   // step-major: coefs[step * P + p]
+        const ezdit_ddim_coef& k = coefs[i];
+        if (!std::isfinite(k.sa) || !std::isfinite(k.sb) || !std::isfinite(k.c_x0) || !std::isfinite(k.c_dir) || !std::isfinite(k.sigma))
+            return fail(EZDIT_E_INVALID, "non-finite coefficient of step %ld, sample %ld", i / P, i % P);
+        if (k.sigma != 0.f && !h->noise) return fail(EZDIT_E_INVALID, "sigma != 0 (step %ld, sample %ld) on a sampler begun without noise", i / P, i % P);
+        c[i * 8 + 0] = k.sa; c[i * 8 + 1] = k.sb; c[i * 8 + 2] = k.c_x0; c[i * 8 + 3] = k.c_dir; c[i * 8 + 4] = k.sigma;
+    }
+    HIPCHK(hipStreamSynchronize(st));   // an earlier upload may still be reading the host mirror
+    h->sp_host.swap(v);
+    HIPCHK(hipMemcpyAsync(h->p.spg, h->sp_host.data(), (size_t)P * 2 * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(h->p.spc, h->sp_host.data() + (size_t)P * 2, (size_t)ns * P * 8 * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (!h->sp_on) drop_graph(h);
+    h->sp_on = true;
     return EZDIT_OK;
 }
 

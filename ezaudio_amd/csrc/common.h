@@ -366,6 +366,11 @@ struct CfgDdimArgs {
     // padded batch (null lens = every sample has n elements): sample p is valid on frames [0, lens[p]) of its L (n = C * L): the rescale statistics run over
     // the C * lens[p] valid elements, frames >= lens[p] of the latents are written as zero whatever pred / noise / latents hold there
     const int* lens; int L;
+    // per-sample settings (null sp_g = off: the scalar arguments above and coef / hc hold for every sample).  On: sample p takes (guidance_scale,
+    // guidance_rescale) from sp_g[p * sp_g_stride + 0 / 1] and its (sa, sb, c_x0, c_dir, sigma) of the current step from sp_c[(step * P + p) * 8 ..]
+    // (step = 0 for the stand-alone operator).  A sample with guidance_scale <= 0 does not read its unconditional row, one with sigma == 0 does not read
+    // its noise slice; both kernels are launched whatever the values are, so a captured step serves every table
+    const float* sp_g; const float* sp_c; int sp_g_stride;
 };
 void launch_cfg_ddim(const CfgDdimArgs& a, float* partial /* [P][64][4] scratch */, hipStream_t st);
 void launch_set_int(int* p, int v, int add, hipStream_t st);  // *p = add ? *p + v : v

@@ -480,7 +480,12 @@ __global__ __launch_bounds__(256) void k_cfg_stats(CfgDdimArgs a, float* partial
     const int n = a.n;
     const float* pc = a.pred + (long)p * n;
     const float* pu = a.pred + (long)(a.P + p) * n;
-    const float gs = a.guidance_scale;
+    float gs = a.guidance_scale;
+    if (a.sp_g) {   // per-sample settings: a sample without guidance or without rescale needs no statistics (workgroup-uniform)
+        const float* g = a.sp_g + (long)p * a.sp_g_stride;
+        gs = g[0];
+        if (!(gs > 0.f && g[1] > 0.f)) return;
+    }
     float s1 = 0.f, q1 = 0.f, s2 = 0.f, q2 = 0.f;
     const int len = a.lens ? a.lens[p] : 0;
     for (int i = blk * 256 + threadIdx.x; i < n; i += CFG_NB * 256) {
@@ -500,10 +505,13 @@ __global__ __launch_bounds__(256) void k_cfg_apply(CfgDdimArgs a, const float* p
     const int p = blockIdx.y, blk = blockIdx.x;
     const int n = a.n;
     const int step = a.cur_step ? *a.cur_step : 0;
-    const float* cf = a.cur_step ? a.coef + step * 8 : a.hc;
+    // the seven settings of this sample: the call's scalars, or its row of the per-sample table (one arithmetic body below either way)
+    const float* cf = a.sp_g ? a.sp_c + ((long)step * a.P + p) * 8 : a.cur_step ? a.coef + step * 8 : a.hc;
     const float sa = cf[0], sb = cf[1], cx0 = cf[2], cdir = cf[3], sigma = cf[4];
-    const bool cfg = a.guidance_scale > 0.f;
-    const bool rescale = cfg && a.guidance_rescale > 0.f;
+    const float gs = a.sp_g ? a.sp_g[(long)p * a.sp_g_stride] : a.guidance_scale;
+    const float phi = a.sp_g ? a.sp_g[(long)p * a.sp_g_stride + 1] : a.guidance_rescale;
+    const bool cfg = gs > 0.f;
+    const bool rescale = cfg && phi > 0.f;
     float ratio = 1.f;
     if (rescale) {   // wave-uniform
         // the CFG_NB partial sums of this sample: one 16-byte load per thread into LDS, then every thread adds them up in the SAME order as before
@@ -526,8 +534,8 @@ __global__ __launch_bounds__(256) void k_cfg_apply(CfgDdimArgs a, const float* p
     const float* pc = a.pred + (long)p * n;
     const float* pu = cfg ? a.pred + (long)(a.P + p) * n : nullptr;
     float* lat = a.latents + (long)p * n;
-    const float* z = a.noise ? a.noise + ((long)step * a.P + p) * n : nullptr;
-    const float gs = a.guidance_scale, phi = a.guidance_rescale;
+    // (per-sample settings: a sample whose sigma is 0 at this step draws no noise, its slice is not read)
+    const float* z = a.noise && !(a.sp_g && sigma == 0.f) ? a.noise + ((long)step * a.P + p) * n : nullptr;
     const int len = a.lens ? a.lens[p] : 0;
     for (int i = blk * 256 + threadIdx.x; i < n; i += CFG_NB * 256) {
         if (a.lens && i % a.L >= len) { lat[i] = 0.f; continue; }   // padded frame: zero, whatever pred / noise / the latents hold there
@@ -651,7 +659,8 @@ void launch_rope_table(float* cosT, float* sinT, int max_len, int dh, hipStream_
 }
 
 void launch_cfg_ddim(const CfgDdimArgs& a, float* partial, hipStream_t st) {
-    if (a.guidance_scale > 0.f && a.guidance_rescale > 0.f)
+    // per-sample settings: always both launches (which samples rescale is a run-time value of the table)
+    if (a.sp_g || (a.guidance_scale > 0.f && a.guidance_rescale > 0.f))
         hipLaunchKernelGGL(k_cfg_stats, dim3(CFG_NB, a.P), dim3(256), 0, st, a, partial);
     hipLaunchKernelGGL(k_cfg_apply, dim3(CFG_NB, a.P), dim3(256), 0, st, a, partial);
 }

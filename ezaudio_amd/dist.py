@@ -6,6 +6,8 @@ so the natural partition is by prompt with each cond/uncond pair kept on one GPU
 replicated, there is NO collective inside the denoising loop, and finished latents (P x 128 x L fp32, 256 KB per sample)
 are gathered once with `all_gather` (backend "nccl" = RCCL over xGMI on ROCm; "gloo" on CPU for tests).
 Per-sample RNG streams (seed + global sample index, sampler.draw_noises) make results independent of the placement.
+Per-prompt settings (lists of guidance_scale / guidance_rescale / eta / random_seed, one entry per prompt) are sliced with the prompts; a list of
+seeds makes a prompt's noise independent of its index altogether.
 Mixed-length batches (sampler.inference with one latent length per prompt): the lengths are sliced with the prompts, every rank pads
 its decoded shard to the GLOBAL longest duration, so `gather_samples` sees equal shapes whatever a shard's own longest sample is.
 """

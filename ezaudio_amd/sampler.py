@@ -19,6 +19,28 @@ def scale_shift_re(x, scale, shift):
     return (x / scale) - shift
 
 
+def _per_prompt(value, n_prompts, name):
+    """A per-request setting as one value per prompt (list), or None for the scalar form."""
+    if isinstance(value, (list, tuple)) or (torch.is_tensor(value) and value.dim() > 0):
+        vals = [v.item() if torch.is_tensor(v) else v for v in value]
+        if len(vals) != n_prompts:
+            raise ValueError(f'{len(vals)} values of {name} for {n_prompts} prompts')
+        return vals
+    return None
+
+
+def _collapse(value, n_prompts, name):
+    """(scalar, None) when `value` is a scalar or a list of equal values -- the scalar call, the same bits -- else (None, list of floats);
+    None / 0 = the setting is off for that sample."""
+    vals = _per_prompt(value, n_prompts, name)
+    if vals is None:
+        return value, None
+    vals = [float(v or 0.0) for v in vals]
+    if len(set(vals)) == 1:
+        return vals[0], None
+    return None, vals
+
+
 class LatentSampler:
     """prepare() once per call, then run(n) advances n DDIM steps on the device."""
 
@@ -33,10 +55,23 @@ class LatentSampler:
                 conditioning_scale=1.0, lengths=None):
         """``lengths`` (list of P ints): init_noise / step_noises / gt / gt_mask are padded to L = max(lengths) frames and sample p is valid on
         [0, lengths[p]) -- its final latent is what a call with that sample alone at its own length gives, zero beyond (include/ezdit.h
-        ezdit_set_lengths).  Not with a ControlNet."""
+        ezdit_set_lengths).  Not with a ControlNet.
+
+        ``guidance_scale``, ``guidance_rescale`` and ``eta`` may each be a list of P values (None / 0 = no guidance for that sample; scalars
+        broadcast): every sample then comes out as the call with that sample alone and its own settings gives it (include/ezdit.h
+        ezdit_sampler_set_sample_params).  Lists of equal values are the scalar call: the same bits, no table."""
         u = self.unet
         dev = u.device
         P, Cc, L = init_noise.shape
+        if isinstance(ddim_steps, (list, tuple)):
+            raise ValueError('ddim_steps must be one value per call: per-prompt step counts are not supported')
+        (guidance_scale, gs_l), (guidance_rescale, gr_l), (eta, eta_l) = (_collapse(v, P, k) for v, k in (
+            (guidance_scale, 'guidance_scale'), (guidance_rescale, 'guidance_rescale'), (eta, 'eta')))
+        table = None
+        if gs_l is not None or gr_l is not None or eta_l is not None:
+            table = tuple(l if l is not None else [float(v or 0.0)] * P for l, v in ((gs_l, guidance_scale), (gr_l, guidance_rescale), (eta_l, eta)))
+            # what ezdit_sampler_begin sees: CFG rows when any sample has guidance; the table set right after it holds every sample's values
+            guidance_scale, guidance_rescale, eta = max(table[0]), table[1][0], max(table[2])
         if lengths is not None:
             lengths = [int(v) for v in lengths]
             if len(lengths) != P:
@@ -88,6 +123,27 @@ class LatentSampler:
                                                  _ptr(self.gt), _ptr(self.gt_mask),
                                                  C.c_void_p(self.stream.cuda_stream)))
         self.n_steps = ddim_steps
+        self.P = P
+        if table is not None:
+            self.set_sample_params(*table)
+
+    def set_sample_params(self, guidance_scale=None, guidance_rescale=None, eta=None):
+        """Per-sample settings of the call prepare() began: three lists of P values (eta enters as each sample's own DDIM coefficient rows),
+        or no argument to go back to the call's scalars.  The captured step reads the table at run time: new values need no re-capture."""
+        u = self.unet
+        st = C.c_void_p(self.stream.cuda_stream)
+        with torch.cuda.stream(self.stream):
+            if guidance_scale is None and guidance_rescale is None and eta is None:
+                _lib.check(u.lib.ezdit_sampler_set_sample_params(u._h, None, None, None, 0, st))
+                return
+            P, n = self.P, self.n_steps
+            vals = [[float(v or 0.0) for v in l] for l in (guidance_scale, guidance_rescale, eta)]
+            if any(len(l) != P for l in vals):
+                raise ValueError(f'per-sample settings need {P} values each')
+            rows = sample_coefficients(self.scheduler, vals[2])
+            gs, gr = (C.c_float * P)(*vals[0]), (C.c_float * P)(*vals[1])
+            arr = (_lib.EzditDdimCoef * (n * P))(*[_lib.EzditDdimCoef(*rows[p][i]) for i in range(n) for p in range(P)])
+            _lib.check(u.lib.ezdit_sampler_set_sample_params(u._h, gs, gr, arr, P, st))
 
     def run(self, n=None, use_graph=True):
         n = self.n_steps if n is None else n
@@ -114,6 +170,16 @@ class LatentSampler:
         return self.latents
 
 
+def sample_coefficients(scheduler, etas):
+    """rows[p][i] = (sa, sb, c_x0, c_dir, sigma) of sample p at step i of the scheduler's current timesteps: `ddim_coefficients(eta_p)` per
+    sample, what a call with that sample alone uploads."""
+    by_eta = {}
+    for e in etas:
+        if e not in by_eta:
+            by_eta[e] = scheduler.ddim_coefficients(e)
+    return [by_eta[e] for e in etas]
+
+
 def _frames_list(audio_frames, n_prompts):
     """audio_frames as one length per prompt, or None for the scalar form."""
     if isinstance(audio_frames, (list, tuple)) or (torch.is_tensor(audio_frames) and audio_frames.dim() > 0):
@@ -133,31 +199,31 @@ def draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n
     prompts are sharded over GPUs.
 
     ``audio_frames`` may be a list with one length per prompt: sample i then draws (1, C, len_i) tensors -- the numbers a call with
-    that sample alone draws -- which are placed into zero-padded [.., max(lengths)] tensors."""
+    that sample alone draws -- which are placed into zero-padded [.., max(lengths)] tensors.
+
+    ``eta`` may be a list with one value per prompt: sample i draws what a call with it alone draws -- nothing per step when eta_i <= 0; its
+    slice of the step noise is then zero, and the whole tensor is None when no sample draws.  ``random_seed`` may be a list of seeds: sample
+    i seeds its generator with random_seed[i], as a single-prompt call with that seed does (a scalar seed keeps seed + first_index + i)."""
     lens = _frames_list(audio_frames, n_prompts)
-    if lens is not None:
-        Lmax = max(lens)
-        init = torch.zeros((n_prompts, codec_dim, Lmax), device=device)
-        step = torch.zeros((ddim_steps, n_prompts, codec_dim, Lmax), device=device) if eta > 0 else None
-        for i, li in enumerate(lens):
-            ini, st = draw_noises(codec_dim, li, ddim_steps, eta, random_seed, device, 1, first_index + i)
-            init[i:i + 1, :, :li] = ini
-            if st is not None:
-                step[:, i:i + 1, :, :li] = st
-        return init, step
-    inits, steps = [], []
+    etas = _per_prompt(eta, n_prompts, 'eta') or [eta] * n_prompts
+    etas = [e or 0 for e in etas]
+    seeds = _per_prompt(random_seed, n_prompts, 'random_seed')
+    Lmax = max(lens) if lens is not None else audio_frames
+    init = torch.zeros((n_prompts, codec_dim, Lmax), device=device)
+    step = torch.zeros((ddim_steps, n_prompts, codec_dim, Lmax), device=device) if max(etas) > 0 else None
     for i in range(n_prompts):
+        li = lens[i] if lens is not None else audio_frames
         g = torch.Generator(device=device)
-        if random_seed is not None:
+        if seeds is not None and seeds[i] is not None:
+            g.manual_seed(int(seeds[i]))
+        elif seeds is None and random_seed is not None:
             g.manual_seed(random_seed + first_index + i)
         else:
             g.seed()
-        inits.append(torch.randn((1, codec_dim, audio_frames), generator=g, device=device))
-        if eta > 0:
-            steps.append(torch.stack([torch.randn((1, codec_dim, audio_frames), generator=g, device=device)
-                                      for _ in range(ddim_steps)], dim=0))
-    init = torch.cat(inits, dim=0)
-    step = torch.cat(steps, dim=1) if steps else None
+        init[i:i + 1, :, :li] = torch.randn((1, codec_dim, li), generator=g, device=device)
+        if etas[i] > 0:
+            for k in range(ddim_steps):
+                step[k, i:i + 1, :, :li] = torch.randn((1, codec_dim, li), generator=g, device=device)
     return init, step
 
 
@@ -182,6 +248,9 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
     Extension: with ``torch.distributed`` initialised and several prompts, every rank samples AND
     VAE-decodes its own contiguous shard of the prompts and the waveforms are all-gathered once (RCCL).
 
+    Extension: ``guidance_scale``, ``guidance_rescale``, ``eta`` and ``random_seed`` may each be a list with one entry per prompt (a guidance of
+    None / 0 = that prompt runs without guidance): every prompt comes out as the call with it alone gives it.  ``ddim_steps`` stays one value.
+
     Extension: ``audio_frames`` may be a list with one latent length per prompt (mixed-length batch).  gt / gt_mask are then padded to
     max(audio_frames) frames; a prompt WITHOUT a reference clip in a batch that has some carries gt_mask all ones (that is the
     reference's no-gt input, src/models/conditioners.py:173-176).  The VAE decodes every sample at its own length (its convolutions have
@@ -190,6 +259,10 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
         neg_text = [""]
     if isinstance(text_raw, str):
         text_raw = [text_raw]
+    if isinstance(ddim_steps, (list, tuple)):
+        raise ValueError('ddim_steps must be one value per call: per-prompt step counts are not supported (the prompts of a call share its timesteps)')
+    for name, v in (('guidance_scale', guidance_scale), ('guidance_rescale', guidance_rescale), ('eta', eta), ('random_seed', random_seed)):
+        _per_prompt(v, len(text_raw), name)   # a list has one entry per prompt
     import torch.distributed as dist
     frames = _frames_list(audio_frames, len(text_raw))
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and len(text_raw) > 1 and first_index is None:
@@ -204,16 +277,17 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
                 ratio = params['autoencoder']['sr'] // params['autoencoder']['latent_sr']
                 return torch.zeros(0, 1, t_all if frames is not None else audio_frames * ratio, device=device)
             sl = lambda t: t if t is None or t.shape[0] == 1 else t[s:e]   # noqa: E731  per-prompt tensors are sliced
+            pp = lambda v: list(v[s:e]) if _per_prompt(v, n_all, 'setting') is not None else v   # noqa: E731  ... and so are per-prompt settings
             if frames is None:
                 return inference(autoencoder, unet, sl(gt), sl(gt_mask), tokenizer, text_encoder, params, noise_scheduler,
-                                 list(text_raw[s:e]), neg_all[s:e], audio_frames, guidance_scale, guidance_rescale, ddim_steps, eta,
-                                 random_seed, device, use_graph, controlnet, sl(condition), conditioning_scale, first_index=s)
+                                 list(text_raw[s:e]), neg_all[s:e], audio_frames, pp(guidance_scale), pp(guidance_rescale), ddim_steps, pp(eta),
+                                 pp(random_seed), device, use_graph, controlnet, sl(condition), conditioning_scale, first_index=s)
             # mixed lengths: the lengths are sliced with the prompts, per-prompt tensors additionally cut to the shard's own padded length
             lmax = max(frames[s:e])
             cut = lambda t: t if t is None else sl(t)[..., :lmax]   # noqa: E731
             wav = inference(autoencoder, unet, cut(gt), cut(gt_mask), tokenizer, text_encoder, params, noise_scheduler,
-                            list(text_raw[s:e]), neg_all[s:e], frames[s:e], guidance_scale, guidance_rescale, ddim_steps, eta,
-                            random_seed, device, use_graph, controlnet, sl(condition), conditioning_scale, first_index=s)
+                            list(text_raw[s:e]), neg_all[s:e], frames[s:e], pp(guidance_scale), pp(guidance_rescale), ddim_steps, pp(eta),
+                            pp(random_seed), device, use_graph, controlnet, sl(condition), conditioning_scale, first_index=s)
             out = torch.zeros(wav.shape[0], wav.shape[1], t_all, dtype=wav.dtype, device=wav.device)
             out[..., :wav.shape[-1]] = wav
             return out

@@ -11,11 +11,12 @@
  *     allocates or frees persistent device memory.  Weights live in one caller-owned blob laid out
  *     by ezdit_param_info(); all activations / tables live in one caller-owned workspace.
  *   - the PER-STEP entry points (ezdit_forward, ezdit_controlnet_forward, ezdit_sampler_run, ezdit_set_step,
- *     ezdit_cfg_ddim_step, the ezvae_* ops) are ASYNCHRONOUS on their stream: no device sync, no host read of
+ *     ezdit_cfg_ddim_step, ezdit_cfg_ddim_step_per_sample, the ezvae_* ops) are ASYNCHRONOUS on their stream: no device sync, no host read of
  *     device data (a sampler step is hipGraph-capturable).  The once-per-call SET-UP entry points synchronise the
  *     stream and must not be called inside a stream capture: ezdit_bind_workspace (diagnostic builds only),
  *     ezdit_prepare_context (reads the context mask back to find single-key batch elements when `xkey1` is on),
- *     ezdit_prepare_timesteps and ezdit_sampler_begin (host staging buffers of the timestep / coefficient tables).
+ *     ezdit_prepare_timesteps, ezdit_sampler_begin and ezdit_sampler_set_sample_params (host staging buffers of the timestep /
+ *     coefficient tables).
  *   - return 0 = OK, negative = error; ezdit_last_error() gives a thread-local message.  No C++
  *     exception crosses the ABI.
  *   - a handle is bound to the device that was current at ezdit_create() and is NOT thread-safe:
@@ -199,6 +200,39 @@ int ezdit_sampler_begin(ezdit_handle* h, float* dev_latents, int P, const float*
  * hipGraph on first use and replays it (no host work between kernels).  Running past the prepared steps (n_steps of
  * ezdit_sampler_begin / n of ezdit_prepare_timesteps) is refused with EZDIT_E_STATE; ezdit_set_step rewinds. */
 int ezdit_sampler_run(ezdit_handle* h, int n, int use_graph, ezdit_stream stream);
+
+/* ---- per-sample sampler settings: guidance_scale, guidance_rescale and eta per prompt of ONE batched call ------------------- */
+/* After ezdit_sampler_begin, sample p of the call takes guidance_scale[p], guidance_rescale[p] and, at step i, the coefficients
+ * coefs[i * P + p] (step-major, n_steps * P entries: each sample's own eta enters through its c_dir and sigma) instead of the call's
+ * scalars.  All three are HOST arrays; all three NULL (or P = 0) clears the table: the scalars of ezdit_sampler_begin hold again, bit
+ * for bit.  Every sample comes out as the call with that sample alone and its settings would give it (the forward of a row depends
+ * on that row only); a table in which every sample holds the call's scalars gives bitwise the latents of the scalar path.
+ *   guidance_scale[p] <= 0   sample p has no guidance: v = pred[p], no rescale; its unconditional row pred[P + p] is computed by the
+ *                            denoiser (the batch keeps its 2 P rows) but not read by the update -- the reference's `guidance_scale=None`
+ *                            run (src/inference.py:94-96) inside a CFG batch
+ *   guidance_rescale[p] <= 0 no rescale statistics for sample p
+ *   sigma == 0 at a step     sample p draws no noise at that step: its slice of dev_noise is not read (it may hold NaN).  dev_noise of
+ *                            ezdit_sampler_begin is NULL only when every sample has eta <= 0
+ * Per-sample lengths (ezdit_set_lengths) work together with the table.  The table lives at the END of the workspace and is read by the
+ * last two kernels of the step at run time: a captured step graph serves every set of values; only switching the table on or off
+ * drops the graph.  With the table on both kernels are launched whatever the values are.  A backbone with a ControlNet attached
+ * accepts the table.  ezdit_workspace_bytes is at most n_slots * (B / 2 + 1) * 32 + 2048 bytes larger for it: room for B / 2 + 1
+ * samples, the B / 2 of a CFG batch.
+ * A set-up entry point like ezdit_set_lengths: it uploads from host memory and waits for `stream`; refused with EZDIT_E_STATE inside a
+ * stream capture and before ezdit_sampler_begin, which clears the table (as ezdit_bind_workspace does).
+ * EZDIT_E_INVALID: P is not the P of ezdit_sampler_begin; only some of the arrays given; a non-finite value; guidance_scale[p] > 0 on a
+ * sampler begun without CFG rows (B == P); sigma != 0 on a sampler begun without noise.  EZDIT_E_UNSUPPORTED: P > B / 2 + 1 (a batch
+ * begun without CFG rows of more than two samples).  A refused call changes nothing. */
+int ezdit_sampler_set_sample_params(ezdit_handle* h, const float* guidance_scale, const float* guidance_rescale,
+                                    const ezdit_ddim_coef* coefs, int P, ezdit_stream stream);
+
+/* The per-sample form of ezdit_cfg_ddim_step, for callers that keep their own loop: dev_params fp32 [P][8] ON THE DEVICE holds
+ * (guidance_scale, guidance_rescale, sa, sb, c_x0, c_dir, sigma, 0) of each sample, with the rules above.  dev_pred is fp32 [2P][n]
+ * always, dev_noise fp32 [P][n] for this step or NULL, dev_scratch >= P*256 floats (always needed).  dev_lens (nullable, device,
+ * int32 [P]): sample p is valid on frames [0, dev_lens[p]) of its L (L divides n), as ezdit_set_lengths; 1 <= dev_lens[p] <= L is
+ * the caller's to guarantee (no value makes the kernels touch memory outside the P * n elements).  Asynchronous, no handle needed. */
+int ezdit_cfg_ddim_step_per_sample(const float* dev_pred, float* dev_latents, const float* dev_noise, const float* dev_params,
+                                   const int32_t* dev_lens, int L, int P, int n, float* dev_scratch, ezdit_stream stream);
 
 /* ---- Oobleck VAE decoder building blocks (src/modules/stable_vae/models/autoencoders.py:38-61,82-113,149-190) --------
  * Stateless ops on caller-owned device buffers; the layer sequence is host code (ezaudio_amd/vae.py), run once per call.
