@@ -147,7 +147,12 @@ struct ezdit_handle {
     int opt_geglu_co = 0;
     int opt_qkv_co = 1;   // the same choice for the fused QKV GEMM (no k-split exchange in the 4-wave form).  Default 1 since round 6: four prompts per GPU 10.25 -> 10.07 ... 10.11 ms per step (-1.5 %),
                           // 768 workgroups = three per CU, two of them resident; at one prompt (192 workgroups, one per CU: nothing to overlap with) the 4-wave form loses 1.3 %
-    int qkv_tile() const { return (opt_qkv_co == 2 || (opt_qkv_co == 1 && M > kCoM)) ? 66 : 61; }
+    // qkv_form: the form of the fused QKV GEMM on the ping-pong kernel, up to kCoM rows.  1 (default) = tile 67, the un-split 8-wave form (every wave walks every K tile of its
+    // 16 rows x two heads: no exchange behind the loop, twice the fragment reads per K tile); 0 = tile 61, the k-split schedule (each wave group takes every other K tile, the
+    // two partial tiles meet through the LDS behind the loop).  The option list is closed, so the form rides on `qkv_co`: adding 4 to its value selects form 0.
+    // Default 1: at one prompt both the K loop and the epilogue of the launch are shorter in this form (stamps and the step-time comparison: DESIGN.md section 4)
+    int opt_qkv_form = 1;
+    int qkv_tile() const { return (opt_qkv_co == 2 || (opt_qkv_co == 1 && M > kCoM)) ? 66 : (opt_qkv_form == 1 && M <= kCoM) ? 67 : 61; }
     static constexpr int kCoM = 2048;
     int geglu_tile() const { return !(opt_gemm_pp & 1) ? 13 : (opt_geglu_co == 2 || (opt_geglu_co == 1 && M > kCoM)) ? 66 : 60; }
     // Single-key cross-attention shortcut (needs the LayerNorm-algebra path).  Softmax over ONE valid key is exactly 1, so for a batch element whose
@@ -1706,7 +1711,8 @@ int ezdit_test_consumer(int tile, int epi, int epi_lds, const void* A, int lda, 
                         void* q, void* k, void* v, int B, int H, int L, int Lp, int dh, int perm, ezdit_stream stream) {
     if (K % 64) return fail(EZDIT_E_INVALID, "K=%d must be a multiple of 64", K);
     if (epi != EPI_GEGLU && epi != EPI_QKV) return fail(EZDIT_E_INVALID, "epi %d is no LayerNorm-algebra consumer", epi);
-    if (!zstat_in || rows_per_b <= 0) return fail(EZDIT_E_INVALID, "the consumer form needs zstat_in and rows_per_b");
+    // (EPI_QKV without statistics: the plain projection of a finished operand -- the instantiation the step launches with the LayerNorm algebra off)
+    if ((!zstat_in && epi != EPI_QKV) || rows_per_b <= 0) return fail(EZDIT_E_INVALID, "the consumer form needs zstat_in and rows_per_b");
     GemmArgs g;
     memset(&g, 0, sizeof g);
     g.A = (const bf16_t*)A; g.lda = lda; g.W = (const bf16_t*)W; g.ldw = ldw; g.wrows = wrows; g.bias = bias; g.out = out; g.ldo = ldo;
@@ -1822,7 +1828,7 @@ int ezdit_set_option(ezdit_handle* h, const char* name, int value) {
     else if (!strcmp(name, "xkey1")) h->opt_xkey1 = value;
     else if (!strcmp(name, "skip_z")) h->opt_skip_z = value;
     else if (!strcmp(name, "geglu_co")) h->opt_geglu_co = value;
-    else if (!strcmp(name, "qkv_co")) h->opt_qkv_co = value;
+    else if (!strcmp(name, "qkv_co")) { h->opt_qkv_co = value & 3; h->opt_qkv_form = (value & 4) ? 0 : 1; }   // (+ 4: qkv_form = 0, the k-split form up to kCoM rows)
     else if (!strcmp(name, "wt")) h->opt_wt = value;
     else if (!strcmp(name, "gemm_pp")) h->opt_gemm_pp = value;
     else if (!strcmp(name, "tile_partial")) h->opt_tile_partial = value;

@@ -499,6 +499,7 @@ int launch_t(const GemmArgs& a0, hipStream_t st) {
 //   61  128x144  4x1 per group        ring 4  144 KB  k_gemm_pp SCHED 2 (k-split); fused QKV GEMM (two heads of 72 per tile)
 //   62  128x128  4x2 (32x64)          ring 3   96 KB  k_gemm_pp SCHED 1
 //   66  128x144  4 waves (32x144)     ring 2   74 KB  k_gemm_co: TWO workgroups per CU; GEGLU GEMM (round 6)
+//   67  128x144  8x1 (16x144)         ring 4  144 KB  k_gemm_pp SCHED 1 (un-split): fused QKV GEMM only, every wave walks every K tile -- no k-split exchange behind the loop
 //   (63-65: ping-pong experiments 64x128 / 128x144 ring 3 / 128x128 2x2, deleted in round 5)
 //   70, 72, 73  k_gemm_ks (K split over the waves of a workgroup, no ring): see launch_ks_tile
 template <int EPI>
@@ -546,12 +547,18 @@ int launch_e(const GemmArgs& a, hipStream_t st) {
 
 int launch_gemm(const GemmArgs& a, hipStream_t st) {
     if (a.K <= 0 || a.K % BK) return 1;
-    if (a.epi == EPI_QKV && a.tile >= 60) {   // ping-pong kernel, k-split schedule: 128 x (2 whole heads), ring 4
+    if (a.epi == EPI_QKV && a.tile >= 60) {   // 128 x (2 whole heads): ping-pong kernel, ring 4 (61 k-split, 67 un-split), or the co-resident kernel (66)
         if (a.zstat_in && !(a.zG && a.zC && a.zparts > 0 && a.zparts <= Z_MAXP && a.zs_stride > 0 && a.zw > 0)) return 1;
         if (a.tile == 66) {   // co-resident kernel (gemm_co.h): the register epilogue only
             if (!a.hn.perm) return 1;
             if (a.hn.dh == 72) return a.zstat_in ? launch_co<128, 144, EPI_QKV, 64>(a, st) : launch_co<128, 144, EPI_QKV, 0>(a, st);
             if (a.hn.dh == 64) return a.zstat_in ? launch_co<128, 128, EPI_QKV, 64>(a, st) : launch_co<128, 128, EPI_QKV, 0>(a, st);
+            return 1;
+        }
+        if (a.tile == 67) {   // un-split 8-wave form (SCHED 1, 16 x BN wave tiles): the register epilogue only
+            if (!a.hn.perm) return 1;
+            if (a.hn.dh == 72) return a.zstat_in ? launch_pp<128, 144, 8, 1, 4, EPI_QKV, 1, 64>(a, st) : launch_pp<128, 144, 8, 1, 4, EPI_QKV, 1>(a, st);
+            if (a.hn.dh == 64) return a.zstat_in ? launch_pp<128, 128, 8, 1, 4, EPI_QKV, 1, 64>(a, st) : launch_pp<128, 128, 8, 1, 4, EPI_QKV, 1>(a, st);
             return 1;
         }
         if (a.hn.dh == 72) return a.zstat_in ? launch_pp<128, 144, 4, 1, 4, EPI_QKV, 2, 64>(a, st) : launch_pp<128, 144, 4, 1, 4, EPI_QKV, 2>(a, st);

@@ -1355,6 +1355,17 @@ __global__ __launch_bounds__(512) void k_gemm_pp(GemmArgs a) {
         }
         if constexpr (EPI == EPI_F32 || EPI == EPI_PARTIAL) pp_store_direct<HF, FN, TM / 2, TN, EPI>(a, half, row0, col0, ewm, wn, lane, z);
     } else {
+        if constexpr (EPI == EPI_QKV) {
+            // un-split 8-wave form of the fused q | k | v projection (WM = 8, WN = 1): every wave walked every K tile and holds 16 rows x two whole heads -- the layout the
+            // register epilogue sees behind the k-split exchange, with no exchange: no partial-tile park, no barrier of its own, no read-back.  The RoPE rows and the LayerNorm
+            // affine are requested here, behind the statistics' vmcnt(0), and land under the epilogue's first barrier and its LayerNorm-algebra / reduction passes
+            static_assert(WN == 1 && FM == 1, "a wave holds one 16-row fragment over the whole tile width");
+            static_assert(BN == 144 || BN == 128, "EPI_QKV tiles hold two whole heads (head_dim 72 / 64)");
+            static_assert(BM * (BN + 8) * 2 <= NS * STAGE, "bf16 staging tile must fit the ring");
+            QkvOperands<BN / 2, FM> qop;
+            qkv_request<BN / 2, FM>(a, col0, row0 + wm * TM + (lane & 15), lane, tid, qop);
+            pp_store_qkv_reg<BM, BN, BN / 2, FM, FN, TM, TN, NT, ZM>(a, acc, smem, row0, col0, wm, lane, tid, zmr, zgc, reinterpret_cast<float*>(smem + NS * STAGE + BM * 8 + 2 * BN * 4 + 8 * 256), slot0, qop, ts);
+        }
         if constexpr (EPI == EPI_GEGLU || EPI == EPI_PARTIAL) {
             constexpr bool lds_ok = BM * ((EPI == EPI_GEGLU ? BN / 2 : BN) + 8) * 2 <= NS * STAGE;
             if constexpr (lds_ok) {

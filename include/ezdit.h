@@ -285,14 +285,15 @@ int ezdit_test_resid_dual(int tile, const void* dev_a_bf16, int lda, const void*
                           const float* dev_gate, const float* dev_zg, float* dev_h_out, void* dev_zu_bf16, int ld_zu, void* dev_zstat,
                           int M, int N, int K, const float* dev_zd, long zd_stride, const float* dev_zg2, int act_row0, int act_row1, int rows_per_b,
                           ezdit_stream stream);
-/* unit-test hook of the LayerNorm algebra's CONSUMER side (csrc/common.h GemmArgs.z*; tiles 60, 61, 66): epi 2 (GEGLU: dev_out bf16 [M][ldo], ldo >= N / 2, W rows and the
+/* unit-test hook of the LayerNorm algebra's CONSUMER side (csrc/common.h GemmArgs.z*; tiles 60, 61, 66, 67): epi 2 (GEGLU: dev_out bf16 [M][ldo], ldo >= N / 2, W rows and the
  * tables in the interleaved 8 value / 8 gate order) or epi 3 (fused QKV: dev_out unused).  The operand is A' = bf16(x g); the epilogue applies
  * acc := r (acc - mu zG[slot][col]) + zC[slot][col] with (mu, r) of row m merged from dev_zstat_in -- float pairs (sum, sum of squares) [zparts][zs_stride], PART-MAJOR,
  * part p = the columns [p zw, min((p + 1) zw, zD)) of x -- and slot = *dev_cur_step + dev_row_slot[m / rows_per_b] (either NULL = 0); zG, zC fp32 [slots][zt_slot_stride].
  * dev_bias is what the forward passes along (C' already holds it: the consumer form must not add it again).  epi 3: M = B L token rows; q, k bf16 [B][H][Lp][DQK], v bf16
  * [B][H][Lp][DV] (DQK / DV = 64 / 64 or 80 / 96 for head_dim 64 / 72; only rows < L and columns < dh are written); qn / kn: the per-head LayerNorm affine [dh]; rope
  * cos / sin fp32 [>= L][dh / 2] or NULL.  perm 1: N = 3 H dh, W rows packed by EZDIT_T_QKROPE, q and k leave in that column order (two heads per tile); perm 0 with
- * dev_k = dev_v = NULL and no tables: the q-only projection of batched prompts (tile 61, N = H dh, natural order). */
+ * dev_k = dev_v = NULL and no tables: the q-only projection of batched prompts (tile 61, N = H dh, natural order).  epi 3 with dev_zstat_in = NULL: the plain projection
+ * (no LayerNorm algebra: the operand is a finished LayerNorm), as the step launches it with zfuse off. */
 int ezdit_test_consumer(int tile, int epi, int epi_lds, const void* dev_a_bf16, int lda, const void* dev_w_bf16, int ldw, int w_rows, const float* dev_bias,
                         void* dev_out, int ldo, int M, int N, int K,
                         const void* dev_zstat_in, long zs_stride, int zparts, int zD, int zw, const float* dev_zG, const float* dev_zC, long zt_slot_stride, float zeps,
@@ -350,7 +351,10 @@ int ezdit_debug_stop_after(ezdit_handle* h, int n_launches);
  *     skip_linear finishes the LayerNorm in its epilogue: one launch less per out-block; 0 = split-K slabs + the row kernel on that edge)
  *   geglu_co / qkv_co 0/1/2 (GEGLU GEMM / fused QKV GEMM on the co-resident kernel k_gemm_co (csrc/gemm_co.h): 4-wave workgroups, 128 x 144 tiles, TWO per CU, so that one
  *     workgroup's prologue / epilogue runs under the other's K loop; 1 = above 2048 token rows (batched prompts), 2 = always, 0 = the ping-pong kernel's 128 x 288 tile.
- *     Defaults: geglu_co 0, qkv_co 1 -- four prompts per GPU -1.5 % per step, one prompt untouched)
+ *     Defaults: geglu_co 0, qkv_co 1 -- four prompts per GPU -1.5 % per step, one prompt untouched.
+ *     qkv_form: the fused QKV GEMM's form on the ping-pong kernel up to 2048 token rows.  1 (default) = tile 67, the un-split 8-wave form: every wave walks every K tile of
+ *     16 rows x two heads, nothing is exchanged behind the loop; 0 = tile 61, the k-split schedule with the partial-tile exchange (results differ in the fp32 summation order
+ *     over K only).  The option list is closed, so the form rides on this knob: qkv_co + 4 selects qkv_form = 0.  Above 2048 rows qkv_co decides as before)
  *   gemm_pp (ping-pong kernel k_gemm_pp: bit 0 GEGLU GEMM; 0 = the round-1 lockstep kernel for it and no LayerNorm algebra.  Bit 1 -- the fused QKV GEMM -- is
  *     retired: since round 6 that GEMM always runs on the ping-pong kernel, its weights are packed for it, EZDIT_T_QKROPE)
  *   tile_partial (tile id of the split-K residual GEMMs at M <= 2048 rows: 9 = lockstep 128 x 128, 62 = the same tile on the ping-pong kernel; csrc/gemm.hip table)
