@@ -13,7 +13,7 @@ import torch
 
 from .config import configs, controlnet_configs, load_yaml_with_includes
 from .denoiser import MaskDiT
-from .sampler import inference, inference_controlnet
+from .sampler import check_solver, inference, inference_controlnet
 from .scheduler import DDIMScheduler
 
 MAX_SEED = np.iinfo(np.int32).max
@@ -84,14 +84,17 @@ class EzAudio:
         return autoencoder, unet, tokenizer, text_encoder, noise_scheduler, params
 
     def generate_audio(self, text, length=10, guidance_scale=5, guidance_rescale=0.75, ddim_steps=100, eta=1,
-                       random_seed=None, randomize_seed=False):
+                       random_seed=None, randomize_seed=False, solver='ddim'):
         """api/ezaudio.py:101-130.  `text` may also be a list of prompts (batched extension): the result is then
         an array [N, T].  With a list of prompts `length` may be a list too, one duration in seconds per prompt (mixed-length
         batch, one call): the result is then (sr, [one 1-D array per prompt]), each trimmed to its own duration.
         `guidance_scale`, `guidance_rescale`, `eta` and `random_seed` may be lists as well, one entry per prompt of the list `text`: every
         prompt is sampled as the call with it alone would sample it (return shapes unchanged).  A prompt '' inside a list runs without
-        guidance (the "empty input" rule per prompt); `randomize_seed` draws one seed per prompt of a list."""
+        guidance (the "empty input" rule per prompt); `randomize_seed` draws one seed per prompt of a list.
+        `solver='dpmpp_2m'` samples with DPM-Solver++(2M) instead of DDIM; it is deterministic, so pass eta=0 with it (the default eta=1
+        raises).  Quality at reduced `ddim_steps` on the real checkpoints is unmeasured."""
         neg_text = None
+        check_solver(solver, eta)
         for name, v in (('guidance_scale', guidance_scale), ('guidance_rescale', guidance_rescale), ('eta', eta), ('random_seed', random_seed)):
             if isinstance(v, (list, tuple)) and (isinstance(text, str) or len(v) != len(text)):
                 raise ValueError(f'a list of {name} needs a list of prompts of the same size')
@@ -117,7 +120,7 @@ class EzAudio:
             random_seed = random.randint(0, MAX_SEED) if isinstance(text, str) else [random.randint(0, MAX_SEED) for _ in text]
         pred = inference(self.autoencoder, self.unet, gt, gt_mask, self.tokenizer, self.text_encoder, self.params,
                          self.noise_scheduler, text, neg_text, length, guidance_scale, guidance_rescale, ddim_steps,
-                         eta, random_seed, self.device)
+                         eta, random_seed, self.device, solver=solver)
         pred = pred.cpu().numpy()
         if per_prompt:
             ratio = self.params['autoencoder']['sr'] // latent_sr
@@ -126,8 +129,9 @@ class EzAudio:
         return self.params['autoencoder']['sr'], pred
 
     def editing_audio(self, text, boundary, gt_file, mask_start, mask_length, guidance_scale=3.5, guidance_rescale=0,
-                      ddim_steps=100, eta=1, random_seed=None, randomize_seed=False):
-        """api/ezaudio.py:132-207 (crop / pad / mask bookkeeping on the host, sampling on the GPU)."""
+                      ddim_steps=100, eta=1, random_seed=None, randomize_seed=False, solver='ddim'):
+        """api/ezaudio.py:132-207 (crop / pad / mask bookkeeping on the host, sampling on the GPU).  `solver` as in generate_audio."""
+        check_solver(solver, eta)
         import librosa
         neg_text = None
         if text == '':
@@ -160,7 +164,7 @@ class EzAudio:
             random_seed = random.randint(0, MAX_SEED)
         pred = inference(self.autoencoder, self.unet, gt_latent, gt_mask, self.tokenizer, self.text_encoder,
                          self.params, self.noise_scheduler, text, neg_text, L, guidance_scale, guidance_rescale,
-                         ddim_steps, eta, random_seed, self.device)
+                         ddim_steps, eta, random_seed, self.device, solver=solver)
         pred = pred.cpu().numpy().squeeze(0).squeeze(0)
         chunk_length = end_idx - start_idx
         pred = pred[:round(chunk_length * sr)]
@@ -195,8 +199,9 @@ class EzAudio_ControlNet(EzAudio):
         self.conditioner = Conditioner(**self.params['conditioner'])
 
     def generate_audio(self, text, audio_path, surpass_noise=0, guidance_scale=3.5, guidance_rescale=0, ddim_steps=50,
-                       eta=1, conditioning_scale=1, random_seed=None, randomize_seed=False):
-        """api/controlnet.py:113-160: the control curve is the frame energy of a reference recording."""
+                       eta=1, conditioning_scale=1, random_seed=None, randomize_seed=False, solver='ddim'):
+        """api/controlnet.py:113-160: the control curve is the frame energy of a reference recording.  `solver` as in EzAudio.generate_audio."""
+        check_solver(solver, eta)
         import librosa
         sr = self.params['autoencoder']['sr']
         gt, _ = librosa.load(audio_path, sr=sr)
@@ -216,6 +221,6 @@ class EzAudio_ControlNet(EzAudio):
                                     self.text_encoder, self.params, self.noise_scheduler, text, neg_text=None,
                                     audio_frames=audio_frames, guidance_scale=guidance_scale,
                                     guidance_rescale=guidance_rescale, ddim_steps=ddim_steps, eta=eta,
-                                    random_seed=random_seed, conditioning_scale=conditioning_scale, device=self.device)
+                                    random_seed=random_seed, conditioning_scale=conditioning_scale, device=self.device, solver=solver)
         pred = pred.cpu().numpy().squeeze(0).squeeze(0)[:original_length]
         return sr, pred

@@ -108,6 +108,11 @@ struct ezdit_handle {
     bool sp_on = false;
     std::vector<float> sp_host;   // host mirror: [P][2] then [n_steps][P][8] (the source of the asynchronous upload)
     static int sp_cap(int B) { return B / 2 + 1; }
+    // multistep solver (ezdit_sampler_set_multistep): c_hist lives in slot 5 of the `coef` rows (coef_host is their host mirror and the source of the
+    // asynchronous upload), the history of data predictions is the caller's; switching it on or off changes the kernel and drops the graph
+    bool ms_on = false;
+    float* ms_hist = nullptr;
+    std::vector<float> coef_host;
 
     int launches = 0;
     bool is_cn = false;          // ControlNet variant (cfg.controlnet)
@@ -793,6 +798,7 @@ int ezdit_bind_workspace(ezdit_handle* h, void* ws, size_t bytes, int B, int L, 
     h->ctx_ready = h->ts_ready = h->cond_ready = false;
     h->lens_on = false; h->lens.clear();
     h->sp_on = false;
+    h->ms_on = false; h->ms_hist = nullptr; h->coef_host.clear();
     drop_graph(h);
     for (ezdit_handle* u : h->cn_users) drop_graph(u);   // a graph captured with this ControlNet attached points at its old buffers
     // zero everything once: all padding rows / columns / keys stay zero for the lifetime of the binding
@@ -999,6 +1005,7 @@ int ezdit_prepare_timesteps(ezdit_handle* h, const int32_t* ts, int n, int per_r
 int ezdit_set_step(ezdit_handle* h, int step, ezdit_stream stream) {
     if (!h || !h->ws) return fail(EZDIT_E_STATE, "bind workspace first");
     if (step < 0 || step >= h->n_slots) return fail(EZDIT_E_INVALID, "step %d out of range", step);
+    if (h->ms_on && step != 0) return fail(EZDIT_E_STATE, "multistep solver: the history is not step %d's (only a rewind to step 0 keeps it right)", step - 1);
     launch_set_int(h->p.ints, step, 0, (hipStream_t)stream);
     h->steps_done = step;
     return EZDIT_OK;
@@ -1447,13 +1454,16 @@ int ezdit_sampler_begin(ezdit_handle* h, float* latents, int P, const float* noi
         cf[i * 8 + 0] = coefs[i].sa; cf[i * 8 + 1] = coefs[i].sb; cf[i * 8 + 2] = coefs[i].c_x0;
         cf[i * 8 + 3] = coefs[i].c_dir; cf[i * 8 + 4] = coefs[i].sigma;
     }
-    HIPCHK(hipMemcpyAsync(h->buf<float>("coef"), cf.data(), cf.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));   // an earlier upload may still be reading the host mirror
+    h->coef_host.swap(cf);
+    HIPCHK(hipMemcpyAsync(h->buf<float>("coef"), h->coef_host.data(), h->coef_host.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
     launch_set_int(h->p.ints, 0, 0, st);
     h->steps_done = 0;
     h->latents = latents; h->noise = noise; h->P = P; h->n_steps = n_steps;
     h->gscale = guidance_scale; h->grescale = guidance_rescale;
     h->sp_on = false;   // per-sample settings belong to one sampler call (the graph is dropped below anyway)
+    h->ms_on = false; h->ms_hist = nullptr;   // ... and so does the multistep solver
     h->s_gt = gt; h->s_gt_mask = gt_mask;
     if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
     if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
@@ -1503,6 +1513,7 @@ static int sampler_step(ezdit_handle* h, hipStream_t st) {
     a.step_inc = h->p.ints; a.done = reinterpret_cast<unsigned*>(h->p.ints + 8);
     a.lens = h->lens_dev(); a.L = h->L;
     a.sp_g = h->sp_on ? h->p.spg : nullptr; a.sp_c = h->sp_on ? h->p.spc : nullptr; a.sp_g_stride = 2;
+    a.x0_hist = h->ms_on ? h->ms_hist : nullptr;
     launch_cfg_ddim(a, h->p.cfgpart, st);   // its last kernel also advances the device step counter
     h->launches += (h->sp_on || (h->gscale > 0.f && h->grescale > 0.f)) ? 2 : 1;
     const hipError_t e = hipGetLastError();
@@ -1518,12 +1529,13 @@ int ezdit_cfg_ddim_step(const float* pred, float* latents, const float* noise, c
     if (guidance_scale > 0.f && guidance_rescale > 0.f && !scratch) return fail(EZDIT_E_INVALID, "guidance_rescale needs %d scratch floats", P * 256);
     CfgDdimArgs a;
     a.pred = pred; a.latents = latents; a.noise = noise; a.coef = nullptr; a.cur_step = nullptr;
-    a.hc[0] = coef->sa; a.hc[1] = coef->sb; a.hc[2] = coef->c_x0; a.hc[3] = coef->c_dir; a.hc[4] = coef->sigma;
+    a.hc[0] = coef->sa; a.hc[1] = coef->sb; a.hc[2] = coef->c_x0; a.hc[3] = coef->c_dir; a.hc[4] = coef->sigma; a.hc[5] = 0.f;
     a.guidance_scale = guidance_scale; a.guidance_rescale = guidance_rescale;
     a.P = P; a.n = n;
     a.step_inc = nullptr; a.done = nullptr;
     a.lens = nullptr; a.L = n;
     a.sp_g = nullptr; a.sp_c = nullptr; a.sp_g_stride = 0;
+    a.x0_hist = nullptr;
     launch_cfg_ddim(a, scratch, (hipStream_t)stream);
     return EZDIT_OK;
 }
@@ -1543,7 +1555,59 @@ int ezdit_cfg_ddim_step_per_sample(const float* pred, float* latents, const floa
     a.step_inc = nullptr; a.done = nullptr;
     a.lens = lens; a.L = lens ? L : n;
     a.sp_g = params; a.sp_c = params + 2; a.sp_g_stride = 8;
+    a.x0_hist = nullptr;
     return hook_launch("k_cfg_*", "", [&] { launch_cfg_ddim(a, scratch, (hipStream_t)stream); return 0; });
+}
+
+// The multistep form of the per-sample operator: params[p][7] is c_hist of sample p (slot 5 of the row sp_c = params + 2 points at), x0_hist the data
+// prediction of the step before, rewritten with this step's.
+int ezdit_cfg_multistep_step(const float* pred, float* latents, float* x0_hist, const float* params, const int32_t* lens, int L, int P, int n,
+                             float* scratch, ezdit_stream stream) {
+    if (!pred || !latents || !x0_hist || !params || P < 1 || n < 2) return fail(EZDIT_E_INVALID, "bad argument");
+    if (!scratch) return fail(EZDIT_E_INVALID, "the multistep step needs %d scratch floats", P * 256);
+    if (lens && (L < 1 || n % L)) return fail(EZDIT_E_INVALID, "lens given: L = %d must divide n = %d", L, n);
+    CfgDdimArgs a;
+    a.pred = pred; a.latents = latents; a.noise = nullptr; a.coef = nullptr; a.cur_step = nullptr;
+    for (float& v : a.hc) v = 0.f;
+    a.guidance_scale = 0.f; a.guidance_rescale = 0.f;
+    a.P = P; a.n = n;
+    a.step_inc = nullptr; a.done = nullptr;
+    a.lens = lens; a.L = lens ? L : n;
+    a.sp_g = params; a.sp_c = params + 2; a.sp_g_stride = 8;
+    a.x0_hist = x0_hist;
+    return hook_launch("k_cfg_*", "", [&] { launch_cfg_ddim(a, scratch, (hipStream_t)stream); return 0; });
+}
+
+int ezdit_sampler_set_multistep(ezdit_handle* h, const float* c_hist, int n_steps, float* x0_hist, ezdit_stream stream) {
+    if (!h) return fail(EZDIT_E_INVALID, "null handle");
+    if (!h->ws || !h->latents) return fail(EZDIT_E_STATE, "ezdit_sampler_begin first");
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    if (cs != hipStreamCaptureStatusNone) return fail(EZDIT_E_STATE, "ezdit_sampler_set_multistep inside a stream capture (it uploads from host memory and waits)");
+    const int ns = h->n_steps;
+    if ((int)h->coef_host.size() != ns * 8) return fail(EZDIT_E_STATE, "ezdit_sampler_begin first");
+    if (c_hist) {
+        if (n_steps != ns) return fail(EZDIT_E_INVALID, "n_steps = %d, the sampler was begun with %d", n_steps, ns);
+        if (!x0_hist) return fail(EZDIT_E_INVALID, "c_hist given without a history buffer");
+        for (int i = 0; i < ns; ++i)
+            if (!std::isfinite(c_hist[i])) return fail(EZDIT_E_INVALID, "non-finite c_hist of step %d", i);
+        if (h->noise) return fail(EZDIT_E_INVALID, "the multistep solver is deterministic: the sampler was begun with noise");
+        if (h->sp_on) {
+            const float* c = h->sp_host.data() + (size_t)h->P * 2;
+            for (long i = 0; i < (long)ns * h->P; ++i)
+                if (c[i * 8 + 4] != 0.f) return fail(EZDIT_E_INVALID, "the multistep solver is deterministic: sigma != 0 in the sample table (step %ld, sample %ld)", i / h->P, i % h->P);
+        }
+    }
+    HIPCHK(hipStreamSynchronize(st));   // an earlier upload may still be reading the host mirror
+    for (int i = 0; i < ns; ++i) h->coef_host[(size_t)i * 8 + 5] = c_hist ? c_hist[i] : 0.f;
+    HIPCHK(hipMemcpyAsync(h->p.coef, h->coef_host.data(), h->coef_host.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const bool on = c_hist != nullptr;
+    if (on != h->ms_on || (on && x0_hist != h->ms_hist)) drop_graph(h);   // (another history buffer is another kernel argument)
+    h->ms_on = on;
+    h->ms_hist = on ? x0_hist : nullptr;
+    return EZDIT_OK;
 }
 
 int ezdit_sampler_set_sample_params(ezdit_handle* h, const float* guidance_scale, const float* guidance_rescale, const ezdit_ddim_coef* coefs, int P,
@@ -1576,6 +1640,7 @@ int ezdit_sampler_set_sample_params(ezdit_handle* h, const float* guidance_scale
         if (!std::isfinite(k.sa) || !std::isfinite(k.sb) || !std::isfinite(k.c_x0) || !std::isfinite(k.c_dir) || !std::isfinite(k.sigma))
             return fail(EZDIT_E_INVALID, "non-finite coefficient of step %ld, sample %ld", i / P, i % P);
         if (k.sigma != 0.f && !h->noise) return fail(EZDIT_E_INVALID, "sigma != 0 (step %ld, sample %ld) on a sampler begun without noise", i / P, i % P);
+        if (k.sigma != 0.f && h->ms_on) return fail(EZDIT_E_INVALID, "sigma != 0 (step %ld, sample %ld) while the multistep solver is on (it is deterministic)", i / P, i % P);
         c[i * 8 + 0] = k.sa; c[i * 8 + 1] = k.sb; c[i * 8 + 2] = k.c_x0; c[i * 8 + 3] = k.c_dir; c[i * 8 + 4] = k.sigma;
     }
     HIPCHK(hipStreamSynchronize(st));   // an earlier upload may still be reading the host mirror

@@ -355,9 +355,9 @@ struct CfgDdimArgs {
     const float* pred;   // [B][C][L]; rows [0,P) cond, [P,2P) uncond (or B = P without CFG)
     float* latents;      // [P][C][L] in/out
     const float* noise;  // [n_steps][P][C][L] or null
-    const float* coef;   // [n_steps][8] (sa, sb, c_x0, c_dir, sigma, 0,0,0)
+    const float* coef;   // [n_steps][8] (sa, sb, c_x0, c_dir, sigma, c_hist, 0,0)
     const int* cur_step; // null: standalone step, coefficients in hc[], noise is this step's slice
-    float hc[5];         // (sa, sb, c_x0, c_dir, sigma) when cur_step is null
+    float hc[6];         // (sa, sb, c_x0, c_dir, sigma, c_hist) when cur_step is null
     float guidance_scale, guidance_rescale;  // guidance_scale <= 0: no CFG
     int P, n;            // n = C*L elements per sample
     // fused sampler: the LAST workgroup to finish (arrival counter `done`, zero between launches) advances the device step
@@ -371,6 +371,11 @@ struct CfgDdimArgs {
     // (step = 0 for the stand-alone operator).  A sample with guidance_scale <= 0 does not read its unconditional row, one with sigma == 0 does not read
     // its noise slice; both kernels are launched whatever the values are, so a captured step serves every table
     const float* sp_g; const float* sp_c; int sp_g_stride;
+    // multistep solver, DPM-Solver++(2M) (null x0_hist = off: the DDIM update, the kernel it has always been).  On: x0_hist fp32 [P][n] holds the data
+    // prediction x0 of the step before; prev += c_hist * (x0 - x0_hist) after the DDIM expression, then x0_hist = x0 (0 on padded frames).  c_hist is slot 5
+    // of the CALL's row coef[step * 8 ..] in the fused sampler, the per-sample table on or off (it depends on the schedule only); in the stand-alone
+    // operator it is slot 5 of the sample's row sp_c[p * 8 ..], or hc[5].  c_hist == 0: x0_hist is written, not read
+    float* x0_hist;
 };
 void launch_cfg_ddim(const CfgDdimArgs& a, float* partial /* [P][64][4] scratch */, hipStream_t st);
 void launch_set_int(int* p, int v, int add, hipStream_t st);  // *p = add ? *p + v : v

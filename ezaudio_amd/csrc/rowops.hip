@@ -472,6 +472,8 @@ __global__ void k_rope_table(float* cosT, float* sinT, int max_len, int dh) {
 //   k_cfg_stats : per (sample, chunk) partial sums  S(c), S(c^2), S(g), S(g^2)   with g = u + s (c - u)
 //   k_cfg_apply : every workgroup re-reduces the NB partials in double (deterministic, no atomics), forms
 //                 std(c)/std(g) with torch.std's unbiased normalisation, and updates its chunk of the latent.
+//                 MS (CfgDdimArgs.x0_hist given): the DPM-Solver++(2M) form of the update, prev += c_hist (x0 - x0 of the step before); MS = false is
+//                 the DDIM kernel as it was, instruction for instruction.
 constexpr int CFG_NB = 64;
 
 __global__ __launch_bounds__(256) void k_cfg_stats(CfgDdimArgs a, float* partial) {
@@ -501,6 +503,7 @@ __global__ __launch_bounds__(256) void k_cfg_stats(CfgDdimArgs a, float* partial
     }
 }
 
+template <bool MS>
 __global__ __launch_bounds__(256) void k_cfg_apply(CfgDdimArgs a, const float* partial) {
     const int p = blockIdx.y, blk = blockIdx.x;
     const int n = a.n;
@@ -537,8 +540,20 @@ __global__ __launch_bounds__(256) void k_cfg_apply(CfgDdimArgs a, const float* p
     // (per-sample settings: a sample whose sigma is 0 at this step draws no noise, its slice is not read)
     const float* z = a.noise && !(a.sp_g && sigma == 0.f) ? a.noise + ((long)step * a.P + p) * n : nullptr;
     const int len = a.lens ? a.lens[p] : 0;
+    // multistep: c_hist is slot 5 of the CALL's row (it depends on the schedule only, also with the per-sample table on), of the sample's own row in the
+    // stand-alone operator.  c_hist == 0 (workgroup-uniform): the history is written but not read, it may hold anything on the first steps
+    float ch = 0.f;
+    float* hist = nullptr;
+    if constexpr (MS) {
+        ch = (a.cur_step ? a.coef + step * 8 : a.sp_g ? a.sp_c + (long)p * 8 : a.hc)[5];
+        hist = a.x0_hist + (long)p * n;
+    }
     for (int i = blk * 256 + threadIdx.x; i < n; i += CFG_NB * 256) {
-        if (a.lens && i % a.L >= len) { lat[i] = 0.f; continue; }   // padded frame: zero, whatever pred / noise / the latents hold there
+        if (a.lens && i % a.L >= len) {   // padded frame: zero, whatever pred / noise / the latents hold there
+            lat[i] = 0.f;
+            if constexpr (MS) hist[i] = 0.f;
+            continue;
+        }
         float v = pc[i];
         if (cfg) {
             const float u = pu[i];
@@ -550,6 +565,10 @@ __global__ __launch_bounds__(256) void k_cfg_apply(CfgDdimArgs a, const float* p
         const float eps = sa * v + sb * x;
         float prev = cx0 * x0 + cdir * eps;
         if (z) prev += sigma * z[i];
+        if constexpr (MS) {
+            if (ch != 0.f) prev += ch * (x0 - hist[i]);
+            hist[i] = x0;
+        }
         lat[i] = prev;
     }
     // Every workgroup has read *cur_step above.  The last one to arrive here advances it for the next step (device-scope
@@ -662,7 +681,8 @@ void launch_cfg_ddim(const CfgDdimArgs& a, float* partial, hipStream_t st) {
     // per-sample settings: always both launches (which samples rescale is a run-time value of the table)
     if (a.sp_g || (a.guidance_scale > 0.f && a.guidance_rescale > 0.f))
         hipLaunchKernelGGL(k_cfg_stats, dim3(CFG_NB, a.P), dim3(256), 0, st, a, partial);
-    hipLaunchKernelGGL(k_cfg_apply, dim3(CFG_NB, a.P), dim3(256), 0, st, a, partial);
+    if (a.x0_hist) hipLaunchKernelGGL(k_cfg_apply<true>, dim3(CFG_NB, a.P), dim3(256), 0, st, a, partial);
+    else hipLaunchKernelGGL(k_cfg_apply<false>, dim3(CFG_NB, a.P), dim3(256), 0, st, a, partial);
 }
 
 // ---- LayerNorm algebra tables (common.h, GemmArgs.z*): G' = g W^T and C' = c W^T (+ bias) for every modulation slot.  The gain / shift

@@ -41,8 +41,21 @@ def _collapse(value, n_prompts, name):
     return None, vals
 
 
+SOLVERS = ('ddim', 'dpmpp_2m')
+
+
+def check_solver(solver, eta):
+    """'ddim' (the default: the reference's scheduler) or 'dpmpp_2m' (DPM-Solver++(2M), deterministic: eta must be 0, every entry of a list)."""
+    if solver not in SOLVERS:
+        raise ValueError(f'solver={solver!r}: expected one of {SOLVERS}')
+    if solver == 'dpmpp_2m':
+        etas = eta if isinstance(eta, (list, tuple)) or (torch.is_tensor(eta) and eta.dim() > 0) else [eta]
+        if any(float(e or 0.0) != 0.0 for e in etas):
+            raise ValueError(f"solver='dpmpp_2m' is deterministic and takes no step noise: pass eta=0 (got eta={eta!r})")
+
+
 class LatentSampler:
-    """prepare() once per call, then run(n) advances n DDIM steps on the device."""
+    """prepare() once per call, then run(n) advances n steps (DDIM, or DPM-Solver++(2M) with solver='dpmpp_2m') on the device."""
 
     def __init__(self, unet, scheduler):
         self.unet = unet
@@ -52,14 +65,19 @@ class LatentSampler:
 
     def prepare(self, text, text_mask, uncond_text, uncond_mask, init_noise, step_noises, guidance_scale,
                 guidance_rescale, ddim_steps, eta, gt=None, gt_mask=None, controlnet=None, condition=None,
-                conditioning_scale=1.0, lengths=None):
+                conditioning_scale=1.0, lengths=None, solver='ddim'):
         """``lengths`` (list of P ints): init_noise / step_noises / gt / gt_mask are padded to L = max(lengths) frames and sample p is valid on
         [0, lengths[p]) -- its final latent is what a call with that sample alone at its own length gives, zero beyond (include/ezdit.h
         ezdit_set_lengths).  Not with a ControlNet.
 
         ``guidance_scale``, ``guidance_rescale`` and ``eta`` may each be a list of P values (None / 0 = no guidance for that sample; scalars
         broadcast): every sample then comes out as the call with that sample alone and its own settings gives it (include/ezdit.h
-        ezdit_sampler_set_sample_params).  Lists of equal values are the scalar call: the same bits, no table."""
+        ezdit_sampler_set_sample_params).  Lists of equal values are the scalar call: the same bits, no table.
+
+        ``solver='dpmpp_2m'``: the second-order multistep update (scheduler.multistep_coefficients, include/ezdit.h ezdit_sampler_set_multistep)
+        in place of DDIM's; eta must be 0.  The history of data predictions is allocated here and lives on the sampler, so run() may be
+        called in pieces.  'ddim' calls nothing new."""
+        check_solver(solver, eta)
         u = self.unet
         dev = u.device
         P, Cc, L = init_noise.shape
@@ -124,8 +142,15 @@ class LatentSampler:
                                                  C.c_void_p(self.stream.cuda_stream)))
         self.n_steps = ddim_steps
         self.P = P
+        self.x0_hist = None
         if table is not None:
             self.set_sample_params(*table)
+        if solver == 'dpmpp_2m':   # after the sample table: the library checks the two against each other
+            self.x0_hist = torch.zeros_like(self.latents)
+            ch = self.scheduler.multistep_coefficients()
+            with torch.cuda.stream(self.stream):
+                _lib.check(u.lib.ezdit_sampler_set_multistep(u._h, (C.c_float * ddim_steps)(*ch), ddim_steps, _ptr(self.x0_hist),
+                                                             C.c_void_p(self.stream.cuda_stream)))
 
     def set_sample_params(self, guidance_scale=None, guidance_rescale=None, eta=None):
         """Per-sample settings of the call prepare() began: three lists of P values (eta enters as each sample's own DDIM coefficient rows),
@@ -231,19 +256,22 @@ def draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n
 def inference_controlnet(autoencoder, unet, controlnet, gt, gt_mask, condition, tokenizer, text_encoder, params,
                          noise_scheduler, text_raw, neg_text=None, audio_frames=500, guidance_scale=3,
                          guidance_rescale=0.0, ddim_steps=50, eta=1, random_seed=2024, conditioning_scale=1.0,
-                         device='cuda', use_graph=True):
-    """Same signature and semantics as the reference's ControlNet ``inference`` (src/inference_controlnet.py:27-129)."""
+                         device='cuda', use_graph=True, solver='ddim'):
+    """Same signature and semantics as the reference's ControlNet ``inference`` (src/inference_controlnet.py:27-129); ``solver`` as in ``inference``."""
     return inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, noise_scheduler, text_raw, neg_text,
                      audio_frames, guidance_scale, guidance_rescale, ddim_steps, eta, random_seed, device, use_graph,
-                     controlnet=controlnet, condition=condition, conditioning_scale=conditioning_scale)
+                     controlnet=controlnet, condition=condition, conditioning_scale=conditioning_scale, solver=solver)
 
 
 @torch.no_grad()
 def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, noise_scheduler, text_raw,
               neg_text=None, audio_frames=500, guidance_scale=3, guidance_rescale=0.0, ddim_steps=50, eta=1,
               random_seed=2024, device='cuda', use_graph=True, controlnet=None, condition=None, conditioning_scale=1.0,
-              first_index=None):
+              first_index=None, solver='ddim'):
     """Same signature and semantics as the reference's ``inference`` (src/inference.py:26-107).
+
+    Extension: ``solver='dpmpp_2m'`` samples with DPM-Solver++(2M) instead of DDIM (deterministic: eta must be 0, the signature's
+    default eta=1 is refused, not ignored).  How few steps give the quality of a longer DDIM run on the real checkpoints is unmeasured.
 
     Extension: with ``torch.distributed`` initialised and several prompts, every rank samples AND
     VAE-decodes its own contiguous shard of the prompts and the waveforms are all-gathered once (RCCL).
@@ -263,6 +291,7 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
         raise ValueError('ddim_steps must be one value per call: per-prompt step counts are not supported (the prompts of a call share its timesteps)')
     for name, v in (('guidance_scale', guidance_scale), ('guidance_rescale', guidance_rescale), ('eta', eta), ('random_seed', random_seed)):
         _per_prompt(v, len(text_raw), name)   # a list has one entry per prompt
+    check_solver(solver, eta)
     import torch.distributed as dist
     frames = _frames_list(audio_frames, len(text_raw))
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and len(text_raw) > 1 and first_index is None:
@@ -281,13 +310,13 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
             if frames is None:
                 return inference(autoencoder, unet, sl(gt), sl(gt_mask), tokenizer, text_encoder, params, noise_scheduler,
                                  list(text_raw[s:e]), neg_all[s:e], audio_frames, pp(guidance_scale), pp(guidance_rescale), ddim_steps, pp(eta),
-                                 pp(random_seed), device, use_graph, controlnet, sl(condition), conditioning_scale, first_index=s)
+                                 pp(random_seed), device, use_graph, controlnet, sl(condition), conditioning_scale, first_index=s, solver=solver)
             # mixed lengths: the lengths are sliced with the prompts, per-prompt tensors additionally cut to the shard's own padded length
             lmax = max(frames[s:e])
             cut = lambda t: t if t is None else sl(t)[..., :lmax]   # noqa: E731
             wav = inference(autoencoder, unet, cut(gt), cut(gt_mask), tokenizer, text_encoder, params, noise_scheduler,
                             list(text_raw[s:e]), neg_all[s:e], frames[s:e], pp(guidance_scale), pp(guidance_rescale), ddim_steps, pp(eta),
-                            pp(random_seed), device, use_graph, controlnet, sl(condition), conditioning_scale, first_index=s)
+                            pp(random_seed), device, use_graph, controlnet, sl(condition), conditioning_scale, first_index=s, solver=solver)
             out = torch.zeros(wav.shape[0], wav.shape[1], t_all, dtype=wav.dtype, device=wav.device)
             out[..., :wav.shape[-1]] = wav
             return out
@@ -312,6 +341,8 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
     # equal lengths are the unpadded batch (the same bits; include/ezdit.h ezdit_set_lengths): the length table is for ragged batches only
     ragged = frames is not None and len(set(frames)) > 1
     kw = dict(lengths=frames) if ragged else {}
+    if solver != 'ddim':
+        kw['solver'] = solver
     smp.prepare(text.float(), text_mask, uncond_text.float(), uncond_mask, init, step_noises, guidance_scale,
                 guidance_rescale, ddim_steps, eta, gt=gt, gt_mask=gt_mask, controlnet=controlnet, condition=condition,
                 conditioning_scale=conditioning_scale, **kw)

@@ -99,6 +99,39 @@ class DDIMScheduler:
         """[(sa, sb, c_x0, c_dir, sigma)] per step, float32, for ezdit_sampler_begin / ezdit_cfg_ddim_step."""
         return [self._coef(t, eta) for t in self.timesteps]
 
+    def multistep_coefficients(self):
+        """[c_hist_i] per step of the current timesteps: the one coefficient DPM-Solver++(2M) adds to the eta = 0 rows of `ddim_coefficients`
+        (for v-prediction the DDIM update at eta = 0 is first-order DPM-Solver++; ezdit_sampler_set_multistep, ezdit_cfg_multistep_step):
+
+            x_next = c_x0 x0_i + c_dir eps_i + c_hist_i (x0_i - x0_{i-1})
+            c_hist_i = alpha' (1 - exp(-h_i)) / (2 r_i),   h_i = lambda' - lambda_i,   r_i = h_{i-1} / h_i,   lambda = ln(alpha / sigma)
+
+        with alpha, sigma = sqrt(alpha_bar), sqrt(1 - alpha_bar) at the step's t and (primed) at its prev_t, as `_scalars` picks them.
+        c_hist_i = 0 whenever h_i or h_{i-1} is not finite: with zero terminal SNR (lambda = -inf at t = 999) and alpha_bar = 1 past the
+        end (lambda = +inf) steps 0, 1 and the last one are first-order -- the published solver's `lower_order_final` with a zero final
+        sigma.  Python floats (fp64) on the float32 alpha_bar table."""
+        import math
+
+        def lam(a):
+            a = float(a)
+            if a <= 0.0:
+                return -math.inf
+            if a >= 1.0:
+                return math.inf
+            return 0.5 * math.log(a / (1.0 - a))
+
+        hs, out = [], []
+        for i, t in enumerate(self.timesteps):
+            a_t, a_prev = self._scalars(t)
+            h = lam(a_prev) - lam(a_t)
+            hs.append(h)
+            if i == 0 or not math.isfinite(h) or not math.isfinite(hs[i - 1]):
+                out.append(0.0)
+                continue
+            r = hs[i - 1] / h
+            out.append(math.sqrt(float(a_prev)) * (1.0 - math.exp(-h)) / (2.0 * r))
+        return out
+
     def step(self, model_output, timestep, sample, eta=0.0, generator=None, variance_noise=None, **unused):
         if sample.is_cuda:   # the reference's own loop driving this scheduler on the GPU: one HIP launch, no torch math
             return self._step_hip(model_output, timestep, sample, eta, generator, variance_noise)

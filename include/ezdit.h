@@ -11,12 +11,12 @@
  *     allocates or frees persistent device memory.  Weights live in one caller-owned blob laid out
  *     by ezdit_param_info(); all activations / tables live in one caller-owned workspace.
  *   - the PER-STEP entry points (ezdit_forward, ezdit_controlnet_forward, ezdit_sampler_run, ezdit_set_step,
- *     ezdit_cfg_ddim_step, ezdit_cfg_ddim_step_per_sample, the ezvae_* ops) are ASYNCHRONOUS on their stream: no device sync, no host read of
+ *     ezdit_cfg_ddim_step, ezdit_cfg_ddim_step_per_sample, ezdit_cfg_multistep_step, the ezvae_* ops) are ASYNCHRONOUS on their stream: no device sync, no host read of
  *     device data (a sampler step is hipGraph-capturable).  The once-per-call SET-UP entry points synchronise the
  *     stream and must not be called inside a stream capture: ezdit_bind_workspace (diagnostic builds only),
  *     ezdit_prepare_context (reads the context mask back to find single-key batch elements when `xkey1` is on),
- *     ezdit_prepare_timesteps, ezdit_sampler_begin and ezdit_sampler_set_sample_params (host staging buffers of the timestep /
- *     coefficient tables).
+ *     ezdit_prepare_timesteps, ezdit_sampler_begin, ezdit_sampler_set_sample_params and ezdit_sampler_set_multistep (host staging
+ *     buffers of the timestep / coefficient tables).
  *   - return 0 = OK, negative = error; ezdit_last_error() gives a thread-local message.  No C++
  *     exception crosses the ABI.
  *   - a handle is bound to the device that was current at ezdit_create() and is NOT thread-safe:
@@ -233,6 +233,34 @@ int ezdit_sampler_set_sample_params(ezdit_handle* h, const float* guidance_scale
  * the caller's to guarantee (no value makes the kernels touch memory outside the P * n elements).  Asynchronous, no handle needed. */
 int ezdit_cfg_ddim_step_per_sample(const float* dev_pred, float* dev_latents, const float* dev_noise, const float* dev_params,
                                    const int32_t* dev_lens, int L, int P, int n, float* dev_scratch, ezdit_stream stream);
+
+/* ---- multistep solver: DPM-Solver++(2M) in the fused sampler step ------------------------------------------------------------- */
+/* For v-prediction the DDIM update at eta = 0 is first-order DPM-Solver++; the 2M solver adds one term in the data prediction of the
+ * step before:   x0_i = sa x - sb v,  eps_i = sa v + sb x  (as ezdit_ddim_coef),   x_next = c_x0 x0_i + c_dir eps_i + c_hist_i (x0_i - x0_{i-1}).
+ * After ezdit_sampler_begin (which switches it off, as ezdit_bind_workspace does), c_hist is a HOST array of n_steps values (the n_steps of
+ * ezdit_sampler_begin; ezaudio_amd/scheduler.py multistep_coefficients) and dev_x0_hist a caller-owned fp32 [P][C][L] device buffer that
+ * must live as long as the sampler runs: the last kernel of every step reads x0_{i-1} from it and writes x0_i back (0 on the padded
+ * frames of ezdit_set_lengths).  c_hist NULL switches it off: the DDIM step again, bit for bit.
+ *   c_hist_i == 0     step i is first-order and does NOT read the history: the buffer may hold anything (NaN included) when the run
+ *                     starts, c_hist_0 being 0 by construction.  The history is still written.
+ * The values go into a spare slot of the coefficient rows already in the workspace (ezdit_workspace_bytes is unchanged) and are read
+ * at run time: new values keep the captured step graph, switching the solver on or off (or another history buffer) drops it.  c_hist
+ * depends on the schedule only, so with a per-sample table (ezdit_sampler_set_sample_params) every sample takes the call's c_hist_i;
+ * per-sample lengths, per-sample guidance and rescale, editing (gt / gt_mask) and an attached ControlNet work unchanged.
+ * A set-up entry point like ezdit_set_lengths: it uploads from host memory and waits for `stream`; refused with EZDIT_E_STATE inside a
+ * stream capture and before ezdit_sampler_begin.  While it is on, ezdit_set_step(k) with k != 0 is refused with EZDIT_E_STATE (the
+ * history would not be step k - 1's; k = 0 is fine, c_hist_0 = 0).
+ * EZDIT_E_INVALID: n_steps is not the sampler's; a non-finite value; c_hist without dev_x0_hist; a sampler begun with noise, or a
+ * per-sample table with any sigma != 0 (the solver is deterministic; ezdit_sampler_set_sample_params in turn refuses sigma != 0 while
+ * the solver is on).  A refused call changes nothing. */
+int ezdit_sampler_set_multistep(ezdit_handle* h, const float* c_hist, int n_steps, float* dev_x0_hist, ezdit_stream stream);
+
+/* The multistep form of ezdit_cfg_ddim_step_per_sample, for callers that keep their own loop: dev_params[p][7], the spare zero of that
+ * operator, is c_hist of sample p; dev_x0_hist fp32 [P][n] holds x0 of the step before and is rewritten with this step's (0 on padded
+ * frames; not read for a sample whose c_hist is 0).  Guidance, rescale and dev_lens as there; no noise (sigma, dev_params[p][6], is
+ * not applied).  dev_scratch >= P*256 floats.  Asynchronous, no handle needed. */
+int ezdit_cfg_multistep_step(const float* dev_pred, float* dev_latents, float* dev_x0_hist, const float* dev_params,
+                             const int32_t* dev_lens, int L, int P, int n, float* dev_scratch, ezdit_stream stream);
 
 /* ---- Oobleck VAE decoder building blocks (src/modules/stable_vae/models/autoencoders.py:38-61,82-113,149-190) --------
  * Stateless ops on caller-owned device buffers; the layer sequence is host code (ezaudio_amd/vae.py), run once per call.
