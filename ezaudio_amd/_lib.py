@@ -57,6 +57,8 @@ PROTOTYPES = {
     'ezdit_controlnet_residuals': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int]),
     'ezdit_sampler_attach_controlnet': (C.c_int, [C.c_void_p, C.c_void_p, C.c_float]),
     'ezdit_set_cn_scale': (C.c_int, [C.c_void_p, C.c_float]),
+    'ezdit_sampler_set_pair_lengths': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p]),
+    'ezdit_sampler_set_cn_scales': (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
     'ezdit_sampler_begin': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(EzditDdimCoef), C.c_int,
                                       C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     'ezdit_sampler_run': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

@@ -198,29 +198,85 @@ class EzAudio_ControlNet(EzAudio):
         self.controlnet.load_state_dict(controlnet_state_dict)
         self.conditioner = Conditioner(**self.params['conditioner'])
 
-    def generate_audio(self, text, audio_path, surpass_noise=0, guidance_scale=3.5, guidance_rescale=0, ddim_steps=50,
-                       eta=1, conditioning_scale=1, random_seed=None, randomize_seed=False, solver='ddim'):
-        """api/controlnet.py:113-160: the control curve is the frame energy of a reference recording.  `solver` as in EzAudio.generate_audio."""
-        check_solver(solver, eta)
-        import librosa
+    def _load_clip(self, audio, surpass_noise, seconds):
+        """One reference recording as the reference prepares it (api/controlnet.py:118-127): peak-normalised, gated, padded or cut to `seconds`.
+        `audio` is a path (librosa) or a 1-D numpy waveform at the model's sample rate.  Returns (waveform, its length before padding / cutting)."""
         sr = self.params['autoencoder']['sr']
-        gt, _ = librosa.load(audio_path, sr=sr)
+        if isinstance(audio, np.ndarray):
+            if audio.ndim != 1:
+                raise ValueError(f'a waveform must be 1-D, got shape {audio.shape}')
+            gt = audio.astype(np.float32)
+        else:
+            import librosa
+            gt, _ = librosa.load(audio, sr=sr)
         gt = gt / (np.max(np.abs(gt)) + 1e-9)
         if surpass_noise > 0:
             gt[np.abs(gt) <= surpass_noise] = 0
         original_length = len(gt)
-        num_samples = int(10 * sr)
-        audio_frames = round(num_samples / sr * self.params['autoencoder']['latent_sr'])
+        num_samples = int(round(seconds * sr))
         gt = np.pad(gt, (0, num_samples - len(gt)), 'constant') if len(gt) < num_samples else gt[:num_samples]
-        gt_audio = torch.tensor(gt).unsqueeze(0).unsqueeze(1).to(self.device)
-        latent_shape = (1, self.params['autoencoder']['dim'], audio_frames)   # the reference encodes only to get this shape
-        condition = self.conditioner(gt_audio.squeeze(1), latent_shape)
+        return gt, original_length
+
+    def generate_audio(self, text, audio_path, surpass_noise=0, guidance_scale=3.5, guidance_rescale=0, ddim_steps=50,
+                       eta=1, conditioning_scale=1, random_seed=None, randomize_seed=False, length=None, solver='ddim'):
+        """api/controlnet.py:113-160: the control curve is the frame energy of a reference recording.  `solver` as in EzAudio.generate_audio.
+
+        Batched extension: `text` and `audio_path` may be lists of equal size (an `audio_path` entry is a file or a 1-D numpy waveform at the model's
+        sample rate), one energy-controlled request per entry in ONE sampler call; the result is then (sr, [one 1-D array per prompt]).
+        `length` (seconds; None = the reference's fixed 10 s) may be one value or one per prompt: the clip is padded or cut to it, and each array
+        comes back trimmed to min(its recording's length, its duration).  `conditioning_scale`, `surpass_noise`, `guidance_scale`,
+        `guidance_rescale`, `eta` and `random_seed` may be lists with one entry per prompt; `ddim_steps` stays one value.  Every clip's energy curve
+        is normalised by its own maximum, and every prompt comes out as the call with it alone gives it."""
+        check_solver(solver, eta)
+        sr = self.params['autoencoder']['sr']
+        latent_sr = self.params['autoencoder']['latent_sr']
+        batched = not isinstance(text, str)
+        if isinstance(ddim_steps, (list, tuple)):
+            raise ValueError('ddim_steps must be one value per call: per-prompt step counts are not supported')
+        if batched != isinstance(audio_path, (list, tuple)) or (batched and len(audio_path) != len(text)):
+            raise ValueError('a list of prompts needs a list of recordings of the same size (and the other way round)')
+        for name, v in (('conditioning_scale', conditioning_scale), ('surpass_noise', surpass_noise), ('guidance_scale', guidance_scale),
+                        ('guidance_rescale', guidance_rescale), ('eta', eta), ('random_seed', random_seed), ('length', length)):
+            if isinstance(v, (list, tuple)) and (not batched or len(v) != len(text)):
+                raise ValueError(f'a list of {name} needs a list of prompts of the same size')
+        if not batched:
+            seconds = 10 if length is None else length
+            gt, original_length = self._load_clip(audio_path, surpass_noise, seconds)
+            num_samples = len(gt)
+            audio_frames = round(num_samples / sr * latent_sr) if length is None else int(round(length * latent_sr))
+            gt_audio = torch.tensor(gt).unsqueeze(0).unsqueeze(1).to(self.device)
+            latent_shape = (1, self.params['autoencoder']['dim'], audio_frames)   # the reference encodes only to get this shape
+            condition = self.conditioner(gt_audio.squeeze(1), latent_shape)
+            if length is not None:   # two control frames per latent frame, whatever the rounding of the duration left
+                condition = torch.nn.functional.pad(condition, (0, max(0, 2 * audio_frames - condition.shape[-1])))[..., :2 * audio_frames]
+            if randomize_seed:
+                random_seed = random.randint(0, MAX_SEED)
+            pred = inference_controlnet(self.autoencoder, self.unet, self.controlnet, None, None, condition, self.tokenizer,
+                                        self.text_encoder, self.params, self.noise_scheduler, text, neg_text=None,
+                                        audio_frames=audio_frames, guidance_scale=guidance_scale,
+                                        guidance_rescale=guidance_rescale, ddim_steps=ddim_steps, eta=eta,
+                                        random_seed=random_seed, conditioning_scale=conditioning_scale, device=self.device, solver=solver)
+            pred = pred.cpu().numpy().squeeze(0).squeeze(0)[:original_length]
+            return sr, pred
+        n = len(text)
+        seconds = list(length) if isinstance(length, (list, tuple)) else [10 if length is None else length] * n
+        gates = list(surpass_noise) if isinstance(surpass_noise, (list, tuple)) else [surpass_noise] * n
+        frames, conditions, keep = [], [], []
+        for clip, gate, sec in zip(audio_path, gates, seconds):
+            gt, original_length = self._load_clip(clip, gate, sec)
+            f = int(round(sec * latent_sr))
+            # per clip: the curve's normalisation takes THIS clip's maximum (a batch through the extractor would still do that per row, but clips differ in length)
+            c = self.conditioner(torch.tensor(gt).unsqueeze(0).to(self.device), (1, self.params['autoencoder']['dim'], f))
+            c = torch.nn.functional.pad(c, (0, max(0, 2 * f - c.shape[-1])))[..., :2 * f]
+            frames.append(f)
+            conditions.append(c)
+            keep.append(min(original_length, len(gt)))
         if randomize_seed:
-            random_seed = random.randint(0, MAX_SEED)
-        pred = inference_controlnet(self.autoencoder, self.unet, self.controlnet, None, None, condition, self.tokenizer,
-                                    self.text_encoder, self.params, self.noise_scheduler, text, neg_text=None,
-                                    audio_frames=audio_frames, guidance_scale=guidance_scale,
+            random_seed = [random.randint(0, MAX_SEED) for _ in text]
+        pred = inference_controlnet(self.autoencoder, self.unet, self.controlnet, None, None, conditions, self.tokenizer,
+                                    self.text_encoder, self.params, self.noise_scheduler, list(text), neg_text=None,
+                                    audio_frames=frames, guidance_scale=guidance_scale,
                                     guidance_rescale=guidance_rescale, ddim_steps=ddim_steps, eta=eta,
                                     random_seed=random_seed, conditioning_scale=conditioning_scale, device=self.device, solver=solver)
-        pred = pred.cpu().numpy().squeeze(0).squeeze(0)[:original_length]
-        return sr, pred
+        pred = pred.cpu().numpy()
+        return sr, [pred[i, 0, :k] for i, k in enumerate(keep)]

@@ -76,11 +76,25 @@ class DiTControlNet:
         _lib.check(self.lib.ezdit_prepare_timesteps(self._h, arr, len(ts), 1 if per_row else 0, _stream()))
 
     def prepare_condition(self, condition):
+        """condition [B, cond_in, 2 L] for the bound (B, L); with the lengths of an attached pair set (ezdit_sampler_set_pair_lengths) still 2 L frames,
+        padded: sample b's signal is its first 2 * len_b frames."""
         cond = condition.to(self.device, torch.float32).contiguous()
         if cond.dim() != 3 or cond.shape[1] != self.cond_in:
             raise AssertionError(f'condition must be [B, {self.cond_in}, 2L], got {tuple(cond.shape)}')
+        if self._ws_key is None:
+            raise _lib.EzditError('bind a workspace first')
+        if cond.shape[0] != self._ws_key[0]:   # the library reads B rows
+            raise AssertionError(f'condition has {cond.shape[0]} rows, the bound batch has {self._ws_key[0]}')
         _lib.check(self.lib.ezdit_prepare_condition(self._h, _ptr(cond), cond.shape[2], _stream()))
         self._keep = [cond]
+
+    def debug_buffer(self, name, dtype, shape=None):
+        """Copy of an internal workspace buffer (tests / debugging), as MaskDiT.debug_buffer."""
+        p, n = C.c_void_p(), C.c_size_t()
+        _lib.check(self.lib.ezdit_debug_buffer(self._h, name.encode(), C.byref(p), C.byref(n)))
+        off = p.value - self._ws.data_ptr()
+        t = self._ws[off:off + n.value].view(dtype).clone()
+        return t if shape is None else t[:int(torch.tensor(shape).prod())].reshape(shape)
 
     def residual_views(self, B, L):
         """Zero-copy views of the residuals of the last forward: list of [B, L, D] fp32 (unscaled)."""
@@ -106,6 +120,7 @@ class DiTControlNet:
         self.bind(B, L, context.shape[1], max(len(t_list), 1))
         self.prepare_context(context, context_mask)
         self.prepare_timesteps(t_list, per_row)
+        _lib.check(self.lib.ezdit_set_lengths(self._h, None, 0, _stream()))   # the drop-in call is unpadded: a table an earlier attached pair left is cleared
         self.prepare_condition(condition)
         x = x.to(self.device, torch.float32).contiguous()
         _lib.check(self.lib.ezdit_controlnet_forward(self._h, _ptr(x), cin, B, None, None, None, _stream()))

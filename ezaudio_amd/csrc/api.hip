@@ -60,6 +60,7 @@ struct WsPtrs {  // workspace regions used on the per-step path, resolved once a
     float2* zstat_skip; float* zt_skip; bf16_t* ucat_z;              // ... of the out-blocks' LN_2D([x | skip]) -> skip_linear: the skips' statistics (kept from the in-block to its out-block), static tables
     int* lens;   // [B] per-batch-element valid frames (ezdit_set_lengths); read by the kernels only while ezdit_handle::lens_on
     float *spg, *spc;   // per-sample sampler settings (ezdit_sampler_set_sample_params): [P][2] (guidance_scale, guidance_rescale) and [n_steps][P][8] DDIM coefficients; read only while sp_on
+    float* cns;  // [B] per-batch-element conditioning_scale of the attached ControlNet (ezdit_sampler_set_cn_scales); read by the row kernel only while ezdit_handle::cns_on
     float* zd;   // [nblk][B][D] constant cross-attention-out vectors of the single-key batch elements (opt_xkey1)
 };
 
@@ -120,6 +121,10 @@ struct ezdit_handle {
     ezdit_handle* cn = nullptr;  // ControlNet attached to this backbone's sampler
     float cn_scale = 1.0f;       // conditioning_scale of the ATTACHED ControlNet (fused sampler only)
     float fwd_cn_scale = 1.0f;   // scale ezdit_forward applies to caller-provided residuals (ezdit_set_cn_scale; default 1)
+    // per-sample conditioning_scale (ezdit_sampler_set_cn_scales), the contract of `lens`: the row kernel reads the device table at run time, a captured step serves every
+    // set of values, switching between the scalar and the table changes a kernel argument and drops the graph
+    bool cns_on = false;
+    std::vector<float> cns_host;   // host mirror, expanded to B entries (the source of the asynchronous upload)
     std::vector<ezdit_handle*> cn_users;  // backbones whose sampler has this ControlNet attached (cleared on destroy)
     const float* ext_mask_embed = nullptr;
     // ---- fixed tile / split-K choices (measured on MI355X in rounds 1-4; the per-shape override options they used to be
@@ -483,6 +488,7 @@ size_t carve(const ezdit_handle* h, int B, int L, int Lc, int n_slots, std::map<
         add("lens", 256 * sizeof(int));   // per-batch-element valid frames of a padded batch (B <= 240), behind everything else for the same reason
         add("spg", (size_t)ezdit_handle::sp_cap(B) * 2 * 4);        // per-sample sampler settings, at the very end (no existing buffer moves): at most
         add("spc", (size_t)ns * ezdit_handle::sp_cap(B) * 8 * 4);   // n_slots * (B / 2 + 1) * 32 bytes + 2 KB more workspace than without them
+        add("cns", 256 * sizeof(float));   // per-batch-element conditioning_scale (B <= 240), behind `lens` and the sample tables for the same reason: no existing buffer moves
     }
     return off;
 }
@@ -663,7 +669,7 @@ void resolve_workspace(ezdit_handle* h) {
     p.ao = h->buf<bf16_t>("ao"); p.act = h->buf<bf16_t>("act"); p.part = h->buf<float>("part"); p.y = h->buf<float>("y");
     p.pred = h->buf<float>("pred"); p.kmask = h->buf<uint8_t>("kmask"); p.kc = h->buf<bf16_t>("kc"); p.vc = h->buf<bf16_t>("vc");
     p.mod = h->buf<float>("mod"); p.modf = h->buf<float>("modf");
-    p.zd = h->buf<float>("zd"); p.lens = h->buf<int>("lens"); p.spg = h->buf<float>("spg"); p.spc = h->buf<float>("spc");
+    p.zd = h->buf<float>("zd"); p.lens = h->buf<int>("lens"); p.spg = h->buf<float>("spg"); p.spc = h->buf<float>("spc"); p.cns = h->buf<float>("cns");
     p.zstat = h->buf<float2>("zstat"); p.zt_qkv = h->buf<float>("zt_qkv"); p.zt_geglu = h->buf<float>("zt_geglu"); p.zt_q2 = h->buf<float>("zt_q2");
     p.zstat_skip = h->buf<float2>("zstat_skip"); p.zt_skip = h->buf<float>("zt_skip"); p.ucat_z = h->buf<bf16_t>("ucat_z");
     if (h->is_cn) { p.cembed = h->buf<float>("cembed"); p.cnres = h->buf<float>("cnres"); p.skipbf = h->buf<bf16_t>("skipbf"); }
@@ -740,13 +746,23 @@ static void drop_graph(ezdit_handle* h) {
     if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
 }
 
+// A ControlNet handle carries a length table only as half of an attached pair (ezdit_sampler_set_pair_lengths): when the pair ends -- detach, or the
+// backbone is destroyed -- the table goes, and with it the condition embed that was computed from it.  The backbone keeps its own table.
+static void clear_cn_lengths(ezdit_handle* cn) {
+    if (!cn->lens_on) return;
+    cn->lens_on = false; cn->lens.clear();
+    cn->cond_ready = false;
+    for (ezdit_handle* u : cn->cn_users) drop_graph(u);
+}
+
 int ezdit_destroy(ezdit_handle* h) {
     if (!h) return EZDIT_OK;
     for (ezdit_handle* u : h->cn_users)   // a backbone must not keep a dangling pointer to this ControlNet
-        if (u->cn == h) { u->cn = nullptr; u->cn_scale = 1.0f; drop_graph(u); }
+        if (u->cn == h) { u->cn = nullptr; u->cn_scale = 1.0f; u->cns_on = false; drop_graph(u); }
     if (h->cn) {
         auto& v = h->cn->cn_users;
         for (size_t i = 0; i < v.size(); ++i) if (v[i] == h) { v.erase(v.begin() + i); break; }
+        clear_cn_lengths(h->cn);
     }
     if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
     if (h->graph) (void)hipGraphDestroy(h->graph);
@@ -798,6 +814,7 @@ int ezdit_bind_workspace(ezdit_handle* h, void* ws, size_t bytes, int B, int L, 
     h->ctx_ready = h->ts_ready = h->cond_ready = false;
     h->lens_on = false; h->lens.clear();
     h->sp_on = false;
+    h->cns_on = false;
     h->ms_on = false; h->ms_hist = nullptr; h->coef_host.clear();
     drop_graph(h);
     for (ezdit_handle* u : h->cn_users) drop_graph(u);   // a graph captured with this ControlNet attached points at its old buffers
@@ -1019,12 +1036,14 @@ int ezdit_set_lengths(ezdit_handle* h, const int32_t* lengths, int n, ezdit_stre
     if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
     if (cs != hipStreamCaptureStatusNone) return fail(EZDIT_E_STATE, "ezdit_set_lengths inside a stream capture (it uploads from host memory and waits)");
     if (!lengths || n == 0) {
+        if (h->is_cn) { clear_cn_lengths(h); return EZDIT_OK; }   // (a table the pair call left on a ControlNet: its embed goes with it)
         if (h->lens_on) drop_graph(h);
         h->lens_on = false; h->lens.clear();
         return EZDIT_OK;
     }
-    if (h->is_cn) return fail(EZDIT_E_UNSUPPORTED, "per-sample lengths on a ControlNet handle (its condition embed has a convolution boundary of its own)");
-    if (h->cn) return fail(EZDIT_E_UNSUPPORTED, "per-sample lengths with a ControlNet attached");
+    // one handle's call can set only one of the two tables of an attached pair, and they must agree: the pair has its own call
+    if (h->is_cn) return fail(EZDIT_E_UNSUPPORTED, "per-sample lengths on a ControlNet handle (its condition embed is computed from the table: ezdit_sampler_set_pair_lengths on the backbone it is attached to)");
+    if (h->cn) return fail(EZDIT_E_UNSUPPORTED, "per-sample lengths with a ControlNet attached: ezdit_sampler_set_pair_lengths sets both tables");
     if (n < 0 || n > h->B || h->B % n) return fail(EZDIT_E_INVALID, "%d lengths do not divide B = %d", n, h->B);
     for (int i = 0; i < n; ++i)
         if (lengths[i] < 1 || lengths[i] > h->L) return fail(EZDIT_E_INVALID, "lengths[%d] = %d outside [1, L = %d]", i, (int)lengths[i], h->L);
@@ -1039,6 +1058,73 @@ int ezdit_set_lengths(ezdit_handle* h, const int32_t* lengths, int n, ezdit_stre
     return EZDIT_OK;
 }
 
+// The lengths of an attached pair: one table, uploaded to the backbone AND its ControlNet.  The ControlNet's condition embed is computed from the table
+// (ezdit_prepare_condition moves the convolution boundary to 2 len_b), so a new table invalidates it.
+int ezdit_sampler_set_pair_lengths(ezdit_handle* h, const int32_t* lengths, int n, ezdit_stream stream) {
+    if (!h) return fail(EZDIT_E_INVALID, "null handle");
+    if (h->is_cn) return fail(EZDIT_E_INVALID, "first argument must be a backbone handle");
+    if (!h->ws) return fail(EZDIT_E_STATE, "bind workspace first");
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    if (cs != hipStreamCaptureStatusNone) return fail(EZDIT_E_STATE, "ezdit_sampler_set_pair_lengths inside a stream capture (it uploads from host memory and waits)");
+    ezdit_handle* cn = h->cn;
+    if (!cn) return fail(EZDIT_E_STATE, "no ControlNet attached (ezdit_sampler_attach_controlnet first; a backbone alone takes ezdit_set_lengths)");
+    if (!cn->ws || cn->B != h->B || cn->L != h->L)
+        return fail(EZDIT_E_STATE, "the attached ControlNet is bound to (B, L) = (%d, %d), the backbone to (%d, %d)", cn->ws ? cn->B : 0, cn->ws ? cn->L : 0, h->B, h->L);
+    if (!lengths || n == 0) {
+        if (h->lens_on) drop_graph(h);
+        h->lens_on = false; h->lens.clear();
+        clear_cn_lengths(cn);
+        return EZDIT_OK;
+    }
+    if (n < 0 || n > h->B || h->B % n) return fail(EZDIT_E_INVALID, "%d lengths do not divide B = %d", n, h->B);
+    for (int i = 0; i < n; ++i)
+        if (lengths[i] < 1 || lengths[i] > h->L) return fail(EZDIT_E_INVALID, "lengths[%d] = %d outside [1, L = %d]", i, (int)lengths[i], h->L);
+    std::vector<int> v((size_t)h->B);
+    for (int b = 0; b < h->B; ++b) v[b] = lengths[b % n];
+    HIPCHK(hipStreamSynchronize(st));   // an earlier upload may still be reading the host mirrors
+    const bool cn_changed = !cn->lens_on || cn->lens != v;
+    h->lens = v; cn->lens = v;
+    HIPCHK(hipMemcpyAsync(h->p.lens, h->lens.data(), (size_t)h->B * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(cn->p.lens, cn->lens.data(), (size_t)h->B * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (!cn->lens_on) for (ezdit_handle* u : cn->cn_users) drop_graph(u);   // null <-> table in the ControlNet's kernels, which the backbone's step captured
+    if (!h->lens_on) drop_graph(h);
+    h->lens_on = true; cn->lens_on = true;
+    if (cn_changed) cn->cond_ready = false;   // the embed of the old table: ezdit_prepare_condition again
+    return EZDIT_OK;
+}
+
+// conditioning_scale per batch element of the fused sampler's ControlNet residuals (row b: scales[b % n], the rule of the lengths: a CFG pair shares its scale)
+int ezdit_sampler_set_cn_scales(ezdit_handle* h, const float* scales, int n, ezdit_stream stream) {
+    if (!h) return fail(EZDIT_E_INVALID, "null handle");
+    if (h->is_cn) return fail(EZDIT_E_INVALID, "first argument must be a backbone handle");
+    if (!h->ws) return fail(EZDIT_E_STATE, "bind workspace first");
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    if (cs != hipStreamCaptureStatusNone) return fail(EZDIT_E_STATE, "ezdit_sampler_set_cn_scales inside a stream capture (it uploads from host memory and waits)");
+    if (!h->cn) return fail(EZDIT_E_STATE, "no ControlNet attached (ezdit_sampler_attach_controlnet first)");
+    if (!scales || n == 0) {
+        if (h->cns_on) drop_graph(h);
+        h->cns_on = false;
+        return EZDIT_OK;
+    }
+    if (n < 0 || n > h->B || h->B % n) return fail(EZDIT_E_INVALID, "%d scales do not divide B = %d", n, h->B);
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(scales[i])) return fail(EZDIT_E_INVALID, "non-finite conditioning scale of sample %d", i);
+    std::vector<float> v((size_t)h->B);
+    for (int b = 0; b < h->B; ++b) v[b] = scales[b % n];
+    HIPCHK(hipStreamSynchronize(st));   // an earlier upload may still be reading the host mirror
+    h->cns_host.swap(v);
+    HIPCHK(hipMemcpyAsync(h->p.cns, h->cns_host.data(), (size_t)h->B * sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (!h->cns_on) drop_graph(h);
+    h->cns_on = true;
+    return EZDIT_OK;
+}
+
 // ------------------------------------------------------------------------------------------------------
 // cn_scale multiplies the ControlNet residuals `cn` (conditioning_scale, controlnet.py:313): the fused sampler passes the
 // attached ControlNet's scale, ezdit_forward passes 1 (the caller's residuals are already scaled, as DiTControlNet.forward returns them)
@@ -1047,7 +1133,7 @@ int ezdit_set_lengths(ezdit_handle* h, const int32_t* lengths, int n, ezdit_stre
 // src/inference_controlnet.py:89-99 + udit.py:345-348).
 static int forward_impl(ezdit_handle* h, const float* x, int in_ch, int x_rows, const float* gt, const uint8_t* gt_mask,
                         const float* const* cn, int n_cn, float cn_scale, float* out, hipStream_t st, hipEvent_t cn_ready = nullptr,
-                        const int* cur_override = nullptr) {
+                        const int* cur_override = nullptr, const float* cn_tab = nullptr) {
     const bool cn_mode = h->is_cn;  // ControlNet: in-blocks only, then one zero-Linear per skip (controlnet.py:303-315)
     Ctx c{h, st};
     const WsPtrs& p = h->p;
@@ -1087,7 +1173,7 @@ static int forward_impl(ezdit_handle* h, const float* x, int in_ch, int x_rows, 
         r.h_in = e.h_in; r.h_out = e.h_out;
         r.part = slabs; r.nsplit = nsplit; r.part_stride = (long)Mp * D; r.ld_part = D;
         r.part_bf16 = (slabs == part) ? 1 : 0;   // the split-K slabs are bf16
-        r.cn_scale = cn_scale;
+        r.cn_scale = cn_scale; r.cn_tab = cn_tab;   // (cn_tab: the fused sampler's per-sample scales; ezdit_forward never passes one)
         r.bias = e.bias; r.gate = e.gate; r.gate_slot_stride = e.gate_stride; r.mode = mode;
         r.ln_g = e.ln_g; r.ln_c = e.ln_c; r.ln_slot_stride = e.ln_stride;
         r.skip = e.skip; r.cn = e.cn;
@@ -1368,18 +1454,21 @@ int ezdit_prepare_condition(ezdit_handle* h, const float* cond, int Lcond, ezdit
     // conv_in: Conv1d(cond_in, c0, 1)                                               controlnet.py:15,66
     a.x = cond; a.w = h->w<float>("cn.cin.w"); a.b = h->w<float>("cn.cin.b"); a.out = h->buf<float>("cn_e0");
     a.B = h->B; a.Cin = h->cfg.cond_in; a.cin_valid = a.Cin; a.Cout = h->c0; a.Lin = Lcond; a.Lout = Lcond; a.ksize = 1; a.stride = 1; a.pad = 0;
+    // padded batch (the pair call's table): batch element b is its own [cond_in, 2 len_b] condition -- every layer's zero padding sits at ITS end, not at
+    // 2 L (after the 1 x 1 conv_in a padded frame would hold the bias, which the k = 3 layer behind it reads at frame 2 len_b)
+    a.lens = h->lens_dev(); a.lin_mul = 2; a.lout_mul = 2;
     launch_conv1d(a, st);
     // eval: no position is masked, the appended mask channel is all zeros (:68-74) -> channel c0 is an implicit zero input
     a.x = h->buf<float>("cn_e0"); a.w = h->w<float>("cn.c0.w"); a.b = h->w<float>("cn.c0.b"); a.out = h->buf<float>("cn_e1");
     a.Cin = h->c0m; a.cin_valid = h->c0; a.Cout = h->c0m; a.ksize = 3; a.pad = 1; a.act = 1;
     launch_conv1d(a, st);
     a.x = h->buf<float>("cn_e1"); a.w = h->w<float>("cn.c1.w"); a.b = h->w<float>("cn.c1.b"); a.out = h->buf<float>("cn_e2");
-    a.Cin = h->c0m; a.cin_valid = h->c0m; a.Cout = h->c1; a.Lout = h->L; a.stride = 2;
+    a.Cin = h->c0m; a.cin_valid = h->c0m; a.Cout = h->c1; a.Lout = h->L; a.stride = 2; a.lout_mul = 1;
     launch_conv1d(a, st);
     // conv_out: Conv1d(c1, D, 1) then transpose to [B, L, D]                         :37,79-82
     a.x = h->buf<float>("cn_e2"); a.w = h->w<float>("cn.cout.w"); a.b = h->w<float>("cn.cout.b"); a.out = h->buf<float>("cembed");
     a.Cin = h->c1; a.cin_valid = h->c1; a.Cout = h->D; a.Lin = h->L; a.Lout = h->L; a.ksize = 1; a.stride = 1; a.pad = 0; a.act = 0;
-    a.out_token_major = 1;
+    a.out_token_major = 1; a.lin_mul = 1;
     launch_conv1d(a, st);
     {
         const hipError_t e = hipGetLastError();
@@ -1415,10 +1504,12 @@ int ezdit_sampler_attach_controlnet(ezdit_handle* h, ezdit_handle* cn, float con
     if (h->cn && h->cn != cn) {
         auto& v = h->cn->cn_users;
         for (size_t i = 0; i < v.size(); ++i) if (v[i] == h) { v.erase(v.begin() + i); break; }
+        clear_cn_lengths(h->cn);   // the pair ends: the ControlNet's half of its table goes, the backbone keeps its own
     }
     if (cn && h->cn != cn) cn->cn_users.push_back(h);
     h->cn = cn;
     h->cn_scale = cn ? conditioning_scale : 1.0f;
+    h->cns_on = false;   // an attach gives every sample this scalar; ezdit_sampler_set_cn_scales comes after it
     if (cn && !h->cn_stream) {   // side stream + fork / join events of the overlapped ControlNet branch: created here, never inside a stream capture
         HIPCHK(hipStreamCreateWithFlags(&h->cn_stream, hipStreamNonBlocking));
         HIPCHK(hipEventCreateWithFlags(&h->cn_fork, hipEventDisableTiming));
@@ -1475,7 +1566,6 @@ static int sampler_step(ezdit_handle* h, hipStream_t st) {
     const float* cnp[64];
     int n_cn = 0;
     hipEvent_t cn_ready = nullptr;
-    if (h->cn && h->lens_on) return fail(EZDIT_E_UNSUPPORTED, "per-sample lengths with a ControlNet attached");
     if (h->cn) {  // src/inference_controlnet.py:89-99: ControlNet on the same assembled input, then the backbone with its skips
         ezdit_handle* cn = h->cn;
         if (cn->B != h->B || cn->L != h->L || cn->nhalf != h->nhalf || cn->D != h->D || !cn->ctx_ready || !cn->ts_ready || !cn->cond_ready)
@@ -1501,7 +1591,8 @@ static int sampler_step(ezdit_handle* h, hipStream_t st) {
         n_cn = cn->nhalf;
         for (int i = 0; i < n_cn; ++i) cnp[i] = cn->p.cnres + (size_t)i * cn->Mp * cn->D;
     }
-    int rc = forward_impl(h, h->latents, h->C, h->P, h->s_gt, h->s_gt_mask, n_cn ? cnp : nullptr, n_cn, h->cn_scale, pred, st, cn_ready);
+    int rc = forward_impl(h, h->latents, h->C, h->P, h->s_gt, h->s_gt_mask, n_cn ? cnp : nullptr, n_cn, h->cn_scale, pred, st, cn_ready, nullptr,
+                          (n_cn && h->cns_on) ? h->p.cns : nullptr);
     if (rc && cn_ready) (void)hipStreamWaitEvent(st, cn_ready, 0);
     if (rc) return rc;
     CfgDdimArgs a;
@@ -1662,6 +1753,20 @@ int ezdit_sampler_run(ezdit_handle* h, int n, int use_graph, ezdit_stream stream
     if (n < 0 || h->steps_done + n > h->n_steps || h->steps_done + n > h->n_ts)
         return fail(EZDIT_E_STATE, "run of %d steps from step %d exceeds the %d prepared steps (ezdit_set_step rewinds)", n,
                     h->steps_done, h->n_steps < h->n_ts ? h->n_steps : h->n_ts);
+    if (h->cn) {
+        // an attached pair runs on ONE length table held twice (ezdit_sampler_set_pair_lengths) and on the condition embed computed from it.  Checked here, not in the
+        // step: a replay of the captured graph reads the tables too
+        const ezdit_handle* cn = h->cn;
+        if (h->lens_on != cn->lens_on)
+            return fail(EZDIT_E_STATE, "per-sample lengths are set on the %s only: an attached pair takes them through ezdit_sampler_set_pair_lengths", h->lens_on ? "backbone" : "ControlNet");
+        if (h->lens_on && h->lens != cn->lens) {
+            size_t b = 0;
+            while (b < h->lens.size() && b < cn->lens.size() && h->lens[b] == cn->lens[b]) ++b;
+            return fail(EZDIT_E_STATE, "the length tables of the backbone and the attached ControlNet differ at batch row %zu (%d, %d)", b,
+                        b < h->lens.size() ? h->lens[b] : -1, b < cn->lens.size() ? cn->lens[b] : -1);
+        }
+        if (!cn->cond_ready) return fail(EZDIT_E_STATE, "the attached ControlNet has no condition embed for its current lengths: ezdit_prepare_condition first");
+    }
     hipStream_t st = (hipStream_t)stream;
     if (!use_graph) {
         for (int i = 0; i < n; ++i) {

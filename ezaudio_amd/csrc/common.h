@@ -200,6 +200,9 @@ struct RowArgs {
     int wt;                // output stores are write-through (sc1)
     int variant;           // 0: one 256-thread workgroup per row; 1: one wave per row (no LDS, no barriers)
     int affine;            // wave-per-row form: rows [128 p, 128 p + 128) are processed on XCD p % 8 (see k_row_w)
+    // per-batch-element conditioning_scale (nullable [B], device; ezdit_sampler_set_cn_scales): row m multiplies cn by cn_tab[m / L] instead of cn_scale.  Read at run time,
+    // once per row: one captured graph serves every set of scales.  At the END of the struct: the offsets of everything above stay what they were
+    const float* cn_tab;
 };
 
 struct GemmArgs {
@@ -384,6 +387,9 @@ struct Conv1dArgs {  // out[b][co][lo] = act(bias[co] + sum_{ci,k} w[co][ci][k] 
     int B, Cin, Cout, Lin, Lout, ksize, stride, pad, act;  // act 1 = SiLU
     int cin_valid;      // channels >= cin_valid of x are implicit zeros (the eval-time mask channel)
     int out_token_major;  // 1: out[b][lo][co] (token-major rows, ld = Cout)
+    // padded batch (null lens = every batch element has Lin inputs and Lout outputs): batch element b has lens[b] * lin_mul valid input and lens[b] * lout_mul valid
+    // output positions.  Inputs at positions beyond read as zero whatever the buffer holds (the convolution's own zero padding moves there), outputs beyond are written as zero
+    const int* lens; int lin_mul, lout_mul;
 };
 void launch_conv1d(const Conv1dArgs& a, hipStream_t st);
 void launch_cast_bf16(const float* x, int ldx, bf16_t* out, int ldo, int M, int N, int act, hipStream_t st);  // act 1 = silu

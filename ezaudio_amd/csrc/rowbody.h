@@ -37,6 +37,8 @@ __device__ __forceinline__ void row_wave(const RowArgs& a, int row, int lane) {
     const float* lc = a.u ? a.ln_c + (long)slot * a.ln_slot_stride : nullptr;
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
     const float4 one = make_float4(1.f, 1.f, 1.f, 1.f);
+    float cns = a.cn_scale;   // uniform over the row: one load per row, issued with the rest
+    if constexpr (CONCAT) { if (a.cn_tab) cns = a.cn_tab[b]; }
 
     float4 v[RW], sb[RW], g[RW], G0[RW], C0[RW], y[CONCAT ? RW : 1], w[CONCAT ? RW : 1], G1[CONCAT ? RW : 1], C1[CONCAT ? RW : 1];
     uint2 pb[RW][RW_MAXS];
@@ -104,7 +106,7 @@ __device__ __forceinline__ void row_wave(const RowArgs& a, int row, int lane) {
         s1 += v[j].x + v[j].y + v[j].z + v[j].w;
         if constexpr (CONCAT) {
             if (c < nc) {
-                y[j].x += a.cn_scale * w[j].x; y[j].y += a.cn_scale * w[j].y; y[j].z += a.cn_scale * w[j].z; y[j].w += a.cn_scale * w[j].w;
+                y[j].x += cns * w[j].x; y[j].y += cns * w[j].y; y[j].z += cns * w[j].z; y[j].w += cns * w[j].w;
             }
             s1 += y[j].x + y[j].y + y[j].z + y[j].w;
         }

@@ -110,6 +110,7 @@ __global__ __launch_bounds__(256) void k_row(RowArgs a) {
         // LayerNorm over the concatenation [h_new | skip (+ controlnet residual)], width 2D  (blocks.py:124-127)
         float4 y[RJ];
         float s = 0.f;
+        const float cns = a.cn_tab ? a.cn_tab[b] : a.cn_scale;   // uniform over the row: one load per row
 #pragma unroll
         for (int j = 0; j < RJ; ++j) {
             const int c = tid + 256 * j;
@@ -118,7 +119,7 @@ __global__ __launch_bounds__(256) void k_row(RowArgs a) {
                 float4 v = ld4(a.skip + (long)row * D + c * 4);
                 if (a.cn) {
                     const float4 w = ld4(a.cn + (long)row * D + c * 4);
-                    v.x += a.cn_scale * w.x; v.y += a.cn_scale * w.y; v.z += a.cn_scale * w.z; v.w += a.cn_scale * w.w;
+                    v.x += cns * w.x; v.y += cns * w.y; v.z += cns * w.z; v.w += cns * w.w;
                 }
                 y[j] = v;
             }
@@ -596,16 +597,20 @@ __global__ __launch_bounds__(256) void k_conv1d(Conv1dArgs a) {
     const int lo = (int)(idx % a.Lout);
     const int co = (int)((idx / a.Lout) % a.Cout);
     const int b = (int)(idx / ((long)a.Lout * a.Cout));
+    // padded batch: this batch element ends at vin inputs / vout outputs (lens[b] <= L, so vin <= Lin and vout <= Lout)
+    int vin = a.Lin, vout = a.Lout;
+    if (a.lens) { const int n = a.lens[b]; vin = n * a.lin_mul; vout = n * a.lout_mul; }
     float acc = a.b ? a.b[co] : 0.f;
     for (int ci = 0; ci < a.cin_valid; ++ci) {
         const float* xr = a.x + ((long)b * a.cin_valid + ci) * a.Lin;
         const float* wr = a.w + ((long)co * a.Cin + ci) * a.ksize;
         for (int k = 0; k < a.ksize; ++k) {
             const int li = lo * a.stride + k - a.pad;
-            if (li >= 0 && li < a.Lin) acc += wr[k] * xr[li];
+            if (li >= 0 && li < vin) acc += wr[k] * xr[li];
         }
     }
     if (a.act == 1) acc = acc / (1.f + expf(-acc));
+    if (lo >= vout) acc = 0.f;
     if (a.out_token_major) a.out[((long)b * a.Lout + lo) * a.Cout + co] = acc;
     else a.out[((long)b * a.Cout + co) * a.Lout + lo] = acc;
 }

@@ -68,7 +68,12 @@ class LatentSampler:
                 conditioning_scale=1.0, lengths=None, solver='ddim'):
         """``lengths`` (list of P ints): init_noise / step_noises / gt / gt_mask are padded to L = max(lengths) frames and sample p is valid on
         [0, lengths[p]) -- its final latent is what a call with that sample alone at its own length gives, zero beyond (include/ezdit.h
-        ezdit_set_lengths).  Not with a ControlNet.
+        ezdit_set_lengths).  With a ControlNet the table goes to the attached pair (ezdit_sampler_set_pair_lengths) and ``condition`` is
+        [P, cond_in, 2 * max(lengths)], padded: sample p's control signal is its first 2 * lengths[p] frames, whatever lies behind is ignored.
+
+        ``condition`` may be one shared [1, cond_in, 2 L] row (broadcast over the prompts, as gt is).  ``conditioning_scale`` may be a list of P
+        values: equal values are the scalar call (the same bits, no table), otherwise every sample's residuals take its own scale
+        (ezdit_sampler_set_cn_scales; set_cn_scales() replaces the values of a prepared call).
 
         ``guidance_scale``, ``guidance_rescale`` and ``eta`` may each be a list of P values (None / 0 = no guidance for that sample; scalars
         broadcast): every sample then comes out as the call with that sample alone and its own settings gives it (include/ezdit.h
@@ -94,8 +99,13 @@ class LatentSampler:
             lengths = [int(v) for v in lengths]
             if len(lengths) != P:
                 raise ValueError(f'{len(lengths)} lengths for P={P} samples')
-            if controlnet is not None:
-                raise NotImplementedError('per-sample lengths with a ControlNet are not implemented')
+        cn_scales = None
+        if controlnet is not None:
+            conditioning_scale, cn_scales = _collapse(conditioning_scale, P, 'conditioning_scale')
+            if cn_scales is not None:
+                conditioning_scale = max(cn_scales)   # what ezdit_sampler_attach_controlnet sees; the table set behind it holds every sample's value
+            if condition is None or condition.dim() != 3 or condition.shape[0] not in (1, P) or condition.shape[2] != 2 * L:
+                raise ValueError(f'condition must be [1 or P={P}, cond_in, 2 L = {2 * L}], got {None if condition is None else tuple(condition.shape)}')
         self.scheduler.set_timesteps(ddim_steps)
         ts = [int(t) for t in self.scheduler.timesteps]
         coefs = self.scheduler.ddim_coefficients(eta)
@@ -125,16 +135,23 @@ class LatentSampler:
             u.bind(B, L, ctx.shape[1], ddim_steps)
             u.prepare_context(ctx, msk)
             u.prepare_timesteps(ts, per_row=False)
-            if controlnet is not None:  # src/inference_controlnet.py:78-99: condition duplicated for the CFG pair
-                cond = torch.cat([condition, condition], dim=0) if use_cfg else condition
+            st = C.c_void_p(self.stream.cuda_stream)
+            if controlnet is not None:
                 controlnet.bind(B, L, ctx.shape[1], ddim_steps)
                 controlnet.prepare_context(ctx, msk)
                 controlnet.prepare_timesteps(ts, per_row=False)
-                controlnet.prepare_condition(cond)
             _lib.check(u.lib.ezdit_sampler_attach_controlnet(u._h, controlnet._h if controlnet is not None else None,
                                                              float(conditioning_scale)))
             self.controlnet = controlnet
-            u.set_lengths(lengths, C.c_void_p(self.stream.cuda_stream))   # (always: the binding is cached, None clears an earlier call's)
+            # (always: the bindings are cached, None clears an earlier call's)
+            if controlnet is None:
+                u.set_lengths(lengths, st)
+            else:  # the pair's table first, then the condition embed that is computed from it
+                arr = None if lengths is None else (C.c_int32 * P)(*lengths)
+                _lib.check(u.lib.ezdit_sampler_set_pair_lengths(u._h, arr, 0 if lengths is None else P, st))
+                cond = condition.to(dev, torch.float32).expand(P, -1, -1)
+                cond = torch.cat([cond, cond], dim=0) if use_cfg else cond   # src/inference_controlnet.py:78-99: duplicated for the CFG pair
+                controlnet.prepare_condition(cond)
             arr = (_lib.EzditDdimCoef * ddim_steps)(*[_lib.EzditDdimCoef(*c) for c in coefs])
             _lib.check(u.lib.ezdit_sampler_begin(u._h, _ptr(self.latents), P, _ptr(self.noise), arr, ddim_steps,
                                                  float(guidance_scale or 0.0), float(guidance_rescale or 0.0),
@@ -145,6 +162,8 @@ class LatentSampler:
         self.x0_hist = None
         if table is not None:
             self.set_sample_params(*table)
+        if cn_scales is not None:
+            self.set_cn_scales(cn_scales)
         if solver == 'dpmpp_2m':   # after the sample table: the library checks the two against each other
             self.x0_hist = torch.zeros_like(self.latents)
             ch = self.scheduler.multistep_coefficients()
@@ -169,6 +188,20 @@ class LatentSampler:
             gs, gr = (C.c_float * P)(*vals[0]), (C.c_float * P)(*vals[1])
             arr = (_lib.EzditDdimCoef * (n * P))(*[_lib.EzditDdimCoef(*rows[p][i]) for i in range(n) for p in range(P)])
             _lib.check(u.lib.ezdit_sampler_set_sample_params(u._h, gs, gr, arr, P, st))
+
+    def set_cn_scales(self, scales=None):
+        """conditioning_scale per sample of the call prepare() began with a ControlNet: a list of P values, or None to go back to the call's scalar.
+        The captured step reads the table at run time: new values need no re-capture."""
+        u = self.unet
+        st = C.c_void_p(self.stream.cuda_stream)
+        with torch.cuda.stream(self.stream):
+            if scales is None:
+                _lib.check(u.lib.ezdit_sampler_set_cn_scales(u._h, None, 0, st))
+                return
+            vals = [float(v) for v in scales]
+            if len(vals) != self.P:
+                raise ValueError(f'{len(vals)} conditioning scales for P={self.P} samples')
+            _lib.check(u.lib.ezdit_sampler_set_cn_scales(u._h, (C.c_float * self.P)(*vals), self.P, st))
 
     def run(self, n=None, use_graph=True):
         n = self.n_steps if n is None else n
@@ -215,6 +248,28 @@ def _frames_list(audio_frames, n_prompts):
             raise ValueError(f'lengths must be positive: {lens}')
         return lens
     return None
+
+
+def pad_conditions(condition, frames, n_prompts):
+    """The control signal of a call as ONE tensor [n_prompts or 1, cond_in, 2 * max(frames)]: a list of per-prompt tensors [1, cond_in, 2 * frames[i]]
+    (or [cond_in, 2 * frames[i]]) is zero-padded behind each prompt's own frames; a tensor is checked and passed on."""
+    lmax = max(frames) if isinstance(frames, (list, tuple)) else int(frames)
+    if isinstance(condition, (list, tuple)):
+        if len(condition) != n_prompts:
+            raise ValueError(f'{len(condition)} conditions for {n_prompts} prompts')
+        rows = [c if c.dim() == 3 else c.unsqueeze(0) for c in condition]
+        for i, c in enumerate(rows):
+            want = 2 * (frames[i] if isinstance(frames, (list, tuple)) else lmax)
+            if c.shape[0] != 1 or c.shape[-1] != want:
+                raise ValueError(f'condition {i} has shape {tuple(c.shape)}; expected [1, cond_in, {want}]')
+        out = torch.zeros(n_prompts, rows[0].shape[1], 2 * lmax, dtype=rows[0].dtype, device=rows[0].device)
+        for i, c in enumerate(rows):
+            out[i:i + 1, :, :c.shape[-1]] = c
+        return out
+    if condition is None or condition.dim() != 3 or condition.shape[0] not in (1, n_prompts) or condition.shape[-1] != 2 * lmax:
+        raise ValueError(f'condition must be [1 or {n_prompts}, cond_in, {2 * lmax}] or a list of per-prompt tensors, '
+                         f'got {None if condition is None else tuple(condition.shape)}')
+    return condition
 
 
 def draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n_prompts=1, first_index=0):
@@ -282,18 +337,25 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
     Extension: ``audio_frames`` may be a list with one latent length per prompt (mixed-length batch).  gt / gt_mask are then padded to
     max(audio_frames) frames; a prompt WITHOUT a reference clip in a batch that has some carries gt_mask all ones (that is the
     reference's no-gt input, src/models/conditioners.py:173-176).  The VAE decodes every sample at its own length (its convolutions have
-    boundaries too); the result is [N, 1, Tmax], zero beyond each sample's own duration."""
+    boundaries too); the result is [N, 1, Tmax], zero beyond each sample's own duration.
+
+    Extension: all of this with a ControlNet too.  ``condition`` is then [N or 1, cond_in, 2 * max(audio_frames)], padded (what lies behind a
+    sample's own 2 * audio_frames[i] frames is ignored), or a list of N tensors [1, cond_in, 2 * audio_frames[i]], which is padded here;
+    ``conditioning_scale`` may be a list with one value per prompt."""
     if neg_text is None:
         neg_text = [""]
     if isinstance(text_raw, str):
         text_raw = [text_raw]
     if isinstance(ddim_steps, (list, tuple)):
         raise ValueError('ddim_steps must be one value per call: per-prompt step counts are not supported (the prompts of a call share its timesteps)')
-    for name, v in (('guidance_scale', guidance_scale), ('guidance_rescale', guidance_rescale), ('eta', eta), ('random_seed', random_seed)):
+    for name, v in (('guidance_scale', guidance_scale), ('guidance_rescale', guidance_rescale), ('eta', eta), ('random_seed', random_seed),
+                    ('conditioning_scale', conditioning_scale)):
         _per_prompt(v, len(text_raw), name)   # a list has one entry per prompt
     check_solver(solver, eta)
     import torch.distributed as dist
     frames = _frames_list(audio_frames, len(text_raw))
+    if controlnet is not None:
+        condition = pad_conditions(condition, frames if frames is not None else audio_frames, len(text_raw))
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and len(text_raw) > 1 and first_index is None:
         from .dist import sample_sharded
         n_all = len(text_raw)
@@ -310,13 +372,14 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
             if frames is None:
                 return inference(autoencoder, unet, sl(gt), sl(gt_mask), tokenizer, text_encoder, params, noise_scheduler,
                                  list(text_raw[s:e]), neg_all[s:e], audio_frames, pp(guidance_scale), pp(guidance_rescale), ddim_steps, pp(eta),
-                                 pp(random_seed), device, use_graph, controlnet, sl(condition), conditioning_scale, first_index=s, solver=solver)
+                                 pp(random_seed), device, use_graph, controlnet, sl(condition), pp(conditioning_scale), first_index=s, solver=solver)
             # mixed lengths: the lengths are sliced with the prompts, per-prompt tensors additionally cut to the shard's own padded length
             lmax = max(frames[s:e])
             cut = lambda t: t if t is None else sl(t)[..., :lmax]   # noqa: E731
+            cond = condition if condition is None else sl(condition)[..., :2 * lmax]   # (the control signal has two frames per latent frame)
             wav = inference(autoencoder, unet, cut(gt), cut(gt_mask), tokenizer, text_encoder, params, noise_scheduler,
                             list(text_raw[s:e]), neg_all[s:e], frames[s:e], pp(guidance_scale), pp(guidance_rescale), ddim_steps, pp(eta),
-                            pp(random_seed), device, use_graph, controlnet, sl(condition), conditioning_scale, first_index=s, solver=solver)
+                            pp(random_seed), device, use_graph, controlnet, cond, pp(conditioning_scale), first_index=s, solver=solver)
             out = torch.zeros(wav.shape[0], wav.shape[1], t_all, dtype=wav.dtype, device=wav.device)
             out[..., :wav.shape[-1]] = wav
             return out

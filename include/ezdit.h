@@ -16,7 +16,8 @@
  *     stream and must not be called inside a stream capture: ezdit_bind_workspace (diagnostic builds only),
  *     ezdit_prepare_context (reads the context mask back to find single-key batch elements when `xkey1` is on),
  *     ezdit_prepare_timesteps, ezdit_sampler_begin, ezdit_sampler_set_sample_params and ezdit_sampler_set_multistep (host staging
- *     buffers of the timestep / coefficient tables).
+ *     buffers of the timestep / coefficient tables), ezdit_set_lengths, ezdit_sampler_set_pair_lengths and ezdit_sampler_set_cn_scales
+ *     (host mirrors of the length / scale tables).
  *   - return 0 = OK, negative = error; ezdit_last_error() gives a thread-local message.  No C++
  *     exception crosses the ABI.
  *   - a handle is bound to the device that was current at ezdit_create() and is NOT thread-safe:
@@ -139,8 +140,9 @@ int ezdit_set_step(ezdit_handle* h, int step, ezdit_stream stream);
  * bound (B, L).  A set-up entry point like ezdit_prepare_* / ezdit_sampler_begin: it uploads from host memory and waits for `stream`;
  * refused with EZDIT_E_STATE inside a stream capture and before a workspace is bound.  ezdit_bind_workspace clears the lengths.
  * EZDIT_E_INVALID: a length outside [1, L], n not dividing B.  EZDIT_E_UNSUPPORTED: a ControlNet handle, a backbone with a ControlNet
- * attached; ezdit_forward with cn_skips and ezdit_sampler_run with an attached ControlNet refuse likewise while lengths are set (the
- * condition embed's stride-2 convolutions have a boundary of their own).  ezdit_sampler_begin checks that both rows of a CFG pair
+ * attached (this call can set one of the two tables that must agree: the pair has ezdit_sampler_set_pair_lengths below; clearing with
+ * NULL is allowed on either handle); ezdit_forward with cn_skips refuses likewise while lengths are set (the caller's residuals come
+ * from a condition embed whose convolutions have a boundary of their own).  ezdit_sampler_begin checks that both rows of a CFG pair
  * have the same length. */
 int ezdit_set_lengths(ezdit_handle* h, const int32_t* lengths, int n, ezdit_stream stream);
 
@@ -159,7 +161,8 @@ int ezdit_forward(ezdit_handle* h, const float* dev_x, int in_ch, int x_rows,
 
 /* ---- ControlNet (handle created with cfg.controlnet = 1) ------------------------------------------------ */
 /* DiTControlNetEmbed (controlnet.py:65-84) on the control signal, hoisted out of the step loop (it depends on the
- * condition only): cond fp32 [B, cond_in, Lcond] with Lcond = 2 L (the embed has one stride-2 conv). */
+ * condition only): cond fp32 [B, cond_in, Lcond] with Lcond = 2 L (the embed has one stride-2 conv).  With the lengths of an attached
+ * pair set (ezdit_sampler_set_pair_lengths) Lcond is still 2 L, the padded form, and each sample's boundary sits at 2 len_b. */
 int ezdit_prepare_condition(ezdit_handle* cn, const float* dev_cond, int Lcond, ezdit_stream stream);
 /* DiTControlNet.forward (controlnet.py:252-315): x as in ezdit_forward (in_ch = C needs `dev_mask_embed`, the [C] fp32
  * mask_embed of the MaskDiT that assembles the input, conditioners.py:161-176); the depth/2 residuals
@@ -173,6 +176,35 @@ int ezdit_sampler_attach_controlnet(ezdit_handle* h, ezdit_handle* cn, float con
 /* scale applied to cn_skips inside ezdit_forward (default 1.0: residuals already scaled by the caller, as DiTControlNet.forward
  * returns them).  Independent of the conditioning_scale of a ControlNet attached to the fused sampler. */
 int ezdit_set_cn_scale(ezdit_handle* h, float scale);
+
+/* ---- batched ControlNet: per-sample lengths and conditioning scales of an ATTACHED pair ------------------------------------- */
+/* ezdit_set_lengths for a backbone `h` with a ControlNet attached, both bound to the same (B, L): the same validation (HOST array,
+ * 1 <= lengths[i] <= L, n divides B, batch row b reads lengths[b % n]), the table uploaded to BOTH handles; NULL or n = 0 clears both.
+ * With the table on, ezdit_prepare_condition still takes the padded [B, cond_in, 2 L] condition, but batch element b is its own
+ * [cond_in, 2 len_b] signal: every layer of the embed reads zero at and beyond its valid input length (2 len_b; len_b behind the
+ * stride-2 layer) whatever the buffer holds -- NaN included -- and writes zero at and beyond its valid output length, so rows
+ * [0, len_b) of the embed are what that sample's own condition gives and the rows beyond are exactly 0.  ezdit_controlnet_forward
+ * and the fused sampler's ControlNet branch then run on the table as the backbone does (input assembly, self-attention keys); the
+ * residuals of padded rows are finite and read by nobody.
+ * The embed is computed from the table: setting another table, or clearing one, invalidates it -- ezdit_controlnet_forward and
+ * ezdit_sampler_run return EZDIT_E_STATE until ezdit_prepare_condition has run again.  ezdit_sampler_run also returns EZDIT_E_STATE,
+ * naming the mismatch, when the two handles' tables differ (one of them cleared or re-bound behind the pair's back).
+ * Detaching (ezdit_sampler_attach_controlnet(h, NULL, ..)) or destroying the backbone clears the ControlNet's table and leaves the
+ * backbone's; destroying either handle leaves the other usable.  The captured step reads both tables at run time: new values keep
+ * the graph, switching on or off drops it.
+ * A set-up entry point: uploads from host memory and waits for `stream`; EZDIT_E_STATE inside a stream capture, before a workspace is
+ * bound, without an attached ControlNet, or when the two handles are bound to different (B, L).  EZDIT_E_INVALID as ezdit_set_lengths.
+ * A refused call changes nothing. */
+int ezdit_sampler_set_pair_lengths(ezdit_handle* h, const int32_t* lengths, int n, ezdit_stream stream);
+/* conditioning_scale per sample of the fused sampler: `scales` is a HOST array of n floats, n divides B, batch row b multiplies the
+ * attached ControlNet's residuals by scales[b % n] (the rule of the lengths: the CFG pair of a sample shares its scale) instead of the
+ * scalar of ezdit_sampler_attach_controlnet; NULL or n = 0 goes back to that scalar, as a later ezdit_sampler_attach_controlnet and
+ * ezdit_bind_workspace do.  The table lives at the end of the workspace (ezdit_workspace_bytes grows by 1 KB) and is read by the row
+ * kernel at run time, once per token row: new values keep the captured step graph, switching between scalar and table drops it.
+ * ezdit_forward with caller-provided residuals never reads the table (ezdit_set_cn_scale is its scale).
+ * A set-up entry point like the one above.  EZDIT_E_STATE: inside a stream capture, no workspace, no ControlNet attached.
+ * EZDIT_E_INVALID: n not dividing B, a non-finite value.  A refused call changes nothing. */
+int ezdit_sampler_set_cn_scales(ezdit_handle* h, const float* scales, int n, ezdit_stream stream);
 
 /* ---- sampler: CFG + rescale + DDIM, src/inference.py:70-100 + diffusers DDIMScheduler.step ---- */
 typedef struct {
