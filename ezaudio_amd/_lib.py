@@ -77,6 +77,12 @@ PROTOTYPES = {
     'ezvae_conv_out1': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p]),
     'ezvae_conv_in1': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p]),
     'ezvae_sample': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    'ezvae_snake_bf16_seg': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_void_p, C.c_int,
+                                       C.c_long, C.c_long, C.c_long, C.c_long, C.c_void_p]),
+    'ezvae_conv_out1_seg': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_long,
+                                      C.c_void_p]),
+    'ezvae_conv_in1_seg': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_void_p]),
+    'ezvae_sample_seg': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_long, C.c_void_p]),
     'ezdit_test_gemm': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'ezdit_debug_gemm_timestamps': (C.c_int, [C.c_void_p, C.c_long]),

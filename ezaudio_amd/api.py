@@ -128,37 +128,73 @@ class EzAudio:
         pred = pred.squeeze(0).squeeze(0) if isinstance(text, str) or len(text) == 1 else pred.squeeze(1)
         return self.params['autoencoder']['sr'], pred
 
-    def editing_audio(self, text, boundary, gt_file, mask_start, mask_length, guidance_scale=3.5, guidance_rescale=0,
-                      ddim_steps=100, eta=1, random_seed=None, randomize_seed=False, solver='ddim'):
-        """api/ezaudio.py:132-207 (crop / pad / mask bookkeeping on the host, sampling on the GPU).  `solver` as in generate_audio."""
-        check_solver(solver, eta)
-        import librosa
-        neg_text = None
-        if text == '':
-            guidance_scale = None
-            print('empty input')
+    def _load_edit_clip(self, gt_file):
+        """The recording of an edit, peak-normalised (api/ezaudio.py:143-144): a path (librosa) or a 1-D numpy waveform at the model's sample rate."""
         sr = self.params['autoencoder']['sr']
-        latent_sr = self.params['autoencoder']['latent_sr']
+        if isinstance(gt_file, np.ndarray):
+            if gt_file.ndim != 1:
+                raise ValueError(f'a waveform must be 1-D, got shape {gt_file.shape}')
+            gt = gt_file.astype(np.float32)
+        else:
+            import librosa
+            gt, _ = librosa.load(gt_file, sr=sr)
+        return gt / (np.max(np.abs(gt)) + 1e-9)
+
+    def _edit_request(self, gt, boundary, mask_start, mask_length):
+        """The crop / pad / mask bookkeeping of ONE edit (api/ezaudio.py:145-157) on a normalised recording `gt`: the recording the result is pasted into
+        (padded behind when the mask runs past its end), the chunk that is re-synthesised (samples [lo, hi) of it), the mask inside the chunk in seconds,
+        and the chunk's duration.  The single and the batched form share it, so they share its arithmetic."""
+        sr = self.params['autoencoder']['sr']
         mask_end = mask_start + mask_length
-        gt, _ = librosa.load(gt_file, sr=sr)
-        gt = gt / (np.max(np.abs(gt)) + 1e-9)
         audio_length = len(gt) / sr
         mask_start = min(mask_start, audio_length)
         if mask_end > audio_length:  # out-padding mode
             gt = np.pad(gt, (0, round((mask_end - audio_length) * sr)), 'constant')
             audio_length = len(gt) / sr
         output_audio = gt.copy()
-        gt = torch.tensor(gt).unsqueeze(0).unsqueeze(1).to(self.device)
         boundary = min((mask_end - mask_start) / 2, boundary)
         start_idx = max(mask_start - boundary, 0)
         end_idx = min(mask_end + boundary, audio_length)
         mask_start -= start_idx
         mask_end -= start_idx
-        gt = gt[:, :, round(start_idx * sr):round(end_idx * sr)]
+        lo, hi = round(start_idx * sr), round(end_idx * sr)
+        return dict(output_audio=output_audio, chunk=gt[lo:hi], lo=lo, hi=hi, mask_start=mask_start, mask_end=mask_end,
+                    chunk_length=end_idx - start_idx)
+
+    def editing_audio(self, text, boundary, gt_file, mask_start, mask_length, guidance_scale=3.5, guidance_rescale=0,
+                      ddim_steps=100, eta=1, random_seed=None, randomize_seed=False, solver='ddim'):
+        """api/ezaudio.py:132-207 (crop / pad / mask bookkeeping on the host, sampling on the GPU).  `solver` as in generate_audio.  `gt_file` is a path or a
+        1-D numpy waveform at the model's sample rate.
+
+        Batched extension: `text` may be a list of prompts, one edit per entry in ONE encode, ONE sampler call and ONE decode; the result is then
+        (sr, [one 1-D array per request]), each its own normalised recording with its own chunk pasted in, as the single call returns it.  `gt_file` is then
+        a list of the same size, or one recording for every request (loaded once, cropped per request).  `boundary`, `mask_start`, `mask_length`,
+        `guidance_scale`, `guidance_rescale`, `eta` and `random_seed` may each be one value or a list with one entry per request; `ddim_steps` stays one
+        value.  A prompt '' inside a list runs without guidance; `randomize_seed` draws one seed per request.  The VAE bottleneck's noise is drawn per clip
+        from the global generator, in list order: the draws the single calls in that order make.  The autoencoder must take `lengths=` and have
+        `latent_lengths` (this package's Autoencoder does)."""
+        check_solver(solver, eta)
+        if not isinstance(text, str):
+            return self._editing_audio_batch(list(text), boundary, gt_file, mask_start, mask_length, guidance_scale, guidance_rescale, ddim_steps, eta,
+                                             random_seed, randomize_seed, solver)
+        for name, v in (('gt_file', gt_file), ('boundary', boundary), ('mask_start', mask_start), ('mask_length', mask_length),
+                        ('guidance_scale', guidance_scale), ('guidance_rescale', guidance_rescale), ('eta', eta), ('random_seed', random_seed)):
+            if isinstance(v, (list, tuple)):
+                raise ValueError(f'a list of {name} needs a list of prompts of the same size')
+        if isinstance(ddim_steps, (list, tuple)):
+            raise ValueError('ddim_steps must be one value per call: per-prompt step counts are not supported')
+        neg_text = None
+        if text == '':
+            guidance_scale = None
+            print('empty input')
+        sr = self.params['autoencoder']['sr']
+        latent_sr = self.params['autoencoder']['latent_sr']
+        req = self._edit_request(self._load_edit_clip(gt_file), boundary, mask_start, mask_length)
+        gt = torch.tensor(req['chunk']).unsqueeze(0).unsqueeze(1).to(self.device)
         gt_latent = self.autoencoder(audio=gt)
         B, D, L = gt_latent.shape
         gt_mask = torch.zeros(B, D, L).to(self.device)
-        gt_mask[:, :, round(mask_start * latent_sr): round(mask_end * latent_sr)] = 1
+        gt_mask[:, :, round(req['mask_start'] * latent_sr): round(req['mask_end'] * latent_sr)] = 1
         gt_mask = gt_mask.bool()
         if randomize_seed:
             random_seed = random.randint(0, MAX_SEED)
@@ -166,10 +202,59 @@ class EzAudio:
                          self.params, self.noise_scheduler, text, neg_text, L, guidance_scale, guidance_rescale,
                          ddim_steps, eta, random_seed, self.device, solver=solver)
         pred = pred.cpu().numpy().squeeze(0).squeeze(0)
-        chunk_length = end_idx - start_idx
-        pred = pred[:round(chunk_length * sr)]
-        output_audio[round(start_idx * sr):round(end_idx * sr)] = pred
+        pred = pred[:round(req['chunk_length'] * sr)]
+        output_audio = req['output_audio']
+        output_audio[req['lo']:req['hi']] = pred
         return sr, output_audio
+
+    def _editing_audio_batch(self, text, boundary, gt_file, mask_start, mask_length, guidance_scale, guidance_rescale, ddim_steps, eta, random_seed,
+                             randomize_seed, solver):
+        """editing_audio for a list of prompts: N crops in one ragged encode, one sampler call at per-request latent lengths, one ragged decode."""
+        n = len(text)
+        if isinstance(ddim_steps, (list, tuple)):
+            raise ValueError('ddim_steps must be one value per call: per-prompt step counts are not supported')
+        for name, v in (('gt_file', gt_file), ('boundary', boundary), ('mask_start', mask_start), ('mask_length', mask_length),
+                        ('guidance_scale', guidance_scale), ('guidance_rescale', guidance_rescale), ('eta', eta), ('random_seed', random_seed)):
+            if isinstance(v, (list, tuple)) and len(v) != n:
+                raise ValueError(f'a list of {name} needs a list of prompts of the same size')
+        if n == 0:
+            raise ValueError('a list of prompts needs at least one prompt')
+        if not hasattr(self.autoencoder, 'latent_lengths'):
+            raise NotImplementedError('a batched edit needs an autoencoder that takes lengths= and has latent_lengths (ezaudio_amd.vae.Autoencoder)')
+        per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n   # noqa: E731
+        sr = self.params['autoencoder']['sr']
+        latent_sr = self.params['autoencoder']['latent_sr']
+        if isinstance(gt_file, (list, tuple)):
+            clips = [self._load_edit_clip(f) for f in gt_file]
+        else:
+            clips = [self._load_edit_clip(gt_file)] * n                         # one recording for every request: loaded once, cropped per request
+        reqs = [self._edit_request(c, b, ms, ml) for c, b, ms, ml in zip(clips, per(boundary), per(mask_start), per(mask_length))]
+        if '' in text:
+            guidance_scale = [None if t == '' else g for t, g in zip(text, per(guidance_scale))]
+            print('empty input')
+        samples = [len(r['chunk']) for r in reqs]
+        wav = torch.zeros(n, 1, max(samples))
+        for i, r in enumerate(reqs):
+            wav[i, 0, :samples[i]] = torch.from_numpy(r['chunk'])
+        gt_latent = self.autoencoder(audio=wav.to(self.device), lengths=samples)
+        frames = [int(v) for v in self.autoencoder.latent_lengths(samples)]
+        _, D, L = gt_latent.shape
+        gt_mask = torch.zeros(n, D, L)
+        for i, r in enumerate(reqs):   # each clip's mask at its own latent length, nothing beyond
+            gt_mask[i, :, min(round(r['mask_start'] * latent_sr), frames[i]):min(round(r['mask_end'] * latent_sr), frames[i])] = 1
+        gt_mask = gt_mask.to(self.device).bool()
+        if randomize_seed:
+            random_seed = [random.randint(0, MAX_SEED) for _ in text]
+        pred = inference(self.autoencoder, self.unet, gt_latent, gt_mask, self.tokenizer, self.text_encoder,
+                         self.params, self.noise_scheduler, text, None, frames, guidance_scale, guidance_rescale,
+                         ddim_steps, eta, random_seed, self.device, solver=solver)
+        pred = pred.cpu().numpy()
+        outs = []
+        for i, r in enumerate(reqs):
+            out = r['output_audio']
+            out[r['lo']:r['hi']] = pred[i, 0, :round(r['chunk_length'] * sr)]
+            outs.append(out)
+        return sr, outs
 
 
 class EzAudio_ControlNet(EzAudio):

@@ -337,7 +337,8 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
     Extension: ``audio_frames`` may be a list with one latent length per prompt (mixed-length batch).  gt / gt_mask are then padded to
     max(audio_frames) frames; a prompt WITHOUT a reference clip in a batch that has some carries gt_mask all ones (that is the
     reference's no-gt input, src/models/conditioners.py:173-176).  The VAE decodes every sample at its own length (its convolutions have
-    boundaries too); the result is [N, 1, Tmax], zero beyond each sample's own duration.
+    boundaries too) -- in one ragged call when the autoencoder is this package's ``Autoencoder``, one by one through an injected callable; the
+    result is [N, 1, Tmax], zero beyond each sample's own duration.
 
     Extension: all of this with a ControlNet too.  ``condition`` is then [N or 1, cond_in, 2 * max(audio_frames)], padded (what lies behind a
     sample's own 2 * audio_frames[i] frames is ignored), or a list of N tensors [1, cond_in, 2 * audio_frames[i]], which is padded here;
@@ -417,7 +418,10 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
         pred = torch.where(keep, gt.to(pred.device, pred.dtype).expand_as(pred), pred)
     if not ragged:
         return autoencoder(embedding=pred)
-    wavs = [autoencoder(embedding=pred[i:i + 1, :, :li]) for i, li in enumerate(frames)]   # each sample at its own length
+    from .vae import Autoencoder
+    if isinstance(autoencoder, Autoencoder):   # one ragged decode: every sample at its own length, stacked with zero gaps (ezaudio_amd/vae.py)
+        return autoencoder(embedding=pred, lengths=frames)
+    wavs = [autoencoder(embedding=pred[i:i + 1, :, :li]) for i, li in enumerate(frames)]   # an injected callable with the reference's surface: one by one
     out = torch.zeros(n_prompts, wavs[0].shape[1], max(w.shape[-1] for w in wavs), dtype=wavs[0].dtype, device=wavs[0].device)
     for i, w in enumerate(wavs):
         out[i:i + 1, :, :w.shape[-1]] = w

@@ -322,6 +322,25 @@ int ezvae_conv_in1(const float* dev_wav, const float* dev_w, const float* dev_bi
  * [latent][L] (caller's randn; NULL = return the mean) -> z fp32 [latent][L] = noise * (softplus(scale) + 1e-4) + mean */
 int ezvae_sample(const float* dev_enc, const float* dev_noise, float* dev_z, int L, int latent_dim, ezdit_stream stream);
 
+/* ---- segment forms of the four ops: B samples stacked along the token axis, zero rows between them, so that every conv of a ragged batch stays ONE ezvae_gemm ------
+ * Sample b lies on rows [b * stride, b * stride + len_b) of a level; len_b = dev_lens[b] * mul / div (integer division; dev_lens: one int32 [B] device table per call --
+ * the decoder multiplies by its strides so far, the encoder divides, and a chain of floors equals one floor by the product).  Values outside an interior (padding,
+ * the rows a GEMM computed inside a gap) are never read, so they may be NaN.  EZDIT_E_INVALID for rows, W, Lmax, C, B, mul, div or a stride <= 0, a NULL table, C not a
+ * multiple of 4 (8 for conv_out1), or more blocks than one launch holds. */
+/* every row r < rows of the launch is written: bf16(snake(x[b * stride_in + l])) with b = r / stride_out, l = r % stride_out where b < B and l < len_b, ZERO elsewhere
+ * (the gap rows are written, not assumed: a cached buffer may hold an earlier call's interiors there).  stride_in != stride_out: the first layer reads the un-gapped input. */
+int ezvae_snake_bf16_seg(const float* dev_x, int ldx, const float* dev_alpha, const float* dev_inv_beta, void* dev_out, int ldo, long rows, int C,
+                         const int32_t* dev_lens, int B, long mul, long div, long stride_in, long stride_out, ezdit_stream stream);
+/* ezvae_conv_out1 on the stacked haloed sequence (row b * stride_in = sample b's position -3): out fp32 [B][W], out[b][l] for l < len_b, zero up to W */
+int ezvae_conv_out1_seg(const void* dev_xb, int ldx, const float* dev_w, float* dev_out, long W, int C, const int32_t* dev_lens, int B, long mul, long div,
+                        long stride_in, ezdit_stream stream);
+/* ezvae_conv_in1 on wav fp32 [B][Tmax] with sample b's own bound dev_lens[b]: out fp32 [rows][C] stacked with stride_out rows per sample, zero rows in the gaps */
+int ezvae_conv_in1_seg(const float* dev_wav, const float* dev_w, const float* dev_bias, float* dev_out, long rows, int C, const int32_t* dev_lens, int B,
+                       long Tmax, long stride_out, ezdit_stream stream);
+/* ezvae_sample on enc stacked (frame l of sample b = row b * stride_enc + l), noise (or NULL) and z fp32 [B][latent][Lmax]; z is zero beyond len_b */
+int ezvae_sample_seg(const float* dev_enc, const float* dev_noise, float* dev_z, int Lmax, int latent_dim, const int32_t* dev_lens, int B, long mul, long div,
+                     long stride_enc, ezdit_stream stream);
+
 /* ---- unit-test hooks: one kernel family each, same code the forward uses ---------------------- */
 int ezdit_test_gemm(ezdit_handle* h, int variant, const void* dev_a_bf16, int lda, const void* dev_w_bf16, int ldw,
                     const float* dev_bias, void* dev_out, int ldo, int M, int N, int K, int splitk,
