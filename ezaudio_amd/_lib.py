@@ -31,6 +31,19 @@ class EzditDdimCoef(C.Structure):
                 ('sigma', C.c_float)]
 
 
+class EzditTestRowArgs(C.Structure):
+    """ezdit_test_row_args (include/ezdit.h): the fields of the row operator's argument struct (csrc/common.h RowArgs) and the slot count of its tables."""
+    _fields_ = [('h_in', C.c_void_p), ('h_out', C.c_void_p),
+                ('part', C.c_void_p), ('nsplit', C.c_int32), ('ld_part', C.c_int32), ('part_stride', C.c_int64), ('part_bf16', C.c_int32), ('mode', C.c_int32),
+                ('bias', C.c_void_p), ('gate', C.c_void_p), ('gate_slot_stride', C.c_int64),
+                ('ln_g', C.c_void_p), ('ln_c', C.c_void_p), ('ln_slot_stride', C.c_int64),
+                ('skip', C.c_void_p), ('cn', C.c_void_p), ('cn_tab', C.c_void_p), ('cn_scale', C.c_float), ('ld_u', C.c_int32),
+                ('u', C.c_void_p),
+                ('M', C.c_int32), ('D', C.c_int32), ('L', C.c_int32), ('n_slots', C.c_int32),
+                ('cur_step', C.c_void_p), ('row_slot', C.c_void_p),
+                ('wt', C.c_int32), ('variant', C.c_int32), ('affine', C.c_int32), ('reserved', C.c_int32)]
+
+
 P_F32, P_BF16 = 0, 1
 T_NONE, T_GEGLU8, T_QKROPE = 0, 1, 2
 
@@ -110,6 +123,11 @@ PROTOTYPES = {
                                               C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'ezdit_test_final_conv': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                         C.c_void_p, C.c_void_p]),
+    'ezdit_test_row': (C.c_int, [C.POINTER(EzditTestRowArgs), C.c_void_p]),
+    'ezdit_test_headnorm': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    'ezdit_test_assemble': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_void_p, C.c_void_p]),
     'ezdit_debug_buffer': (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     'ezdit_last_launch_count': (C.c_int, [C.c_void_p]),
     'ezdit_debug_stop_after': (C.c_int, [C.c_void_p, C.c_int]),

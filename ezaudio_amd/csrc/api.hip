@@ -1977,6 +1977,115 @@ int ezdit_test_final_conv(const float* y, int ldy, const float* w, const float* 
     return hook_launch("k_final_conv", "", [&] { launch_final_conv(fc, (hipStream_t)stream); return 0; });
 }
 
+// the row operator (launch_row: k_row / k_row_w) on a caller-described RowArgs.  Everything that bounds an address is checked here, before the first HIP call: the kernels
+// themselves check nothing (k_row would drop the columns beyond 2048 and the slabs beyond 8 without a word)
+int ezdit_test_row(const ezdit_test_row_args* t, ezdit_stream stream) {
+    if (!t) return fail(EZDIT_E_INVALID, "null argument");
+    if (t->M <= 0 || t->D <= 0 || t->L <= 0) return fail(EZDIT_E_INVALID, "bad shape M=%d D=%d L=%d", t->M, t->D, t->L);
+    if (t->nsplit < 0) return fail(EZDIT_E_INVALID, "nsplit = %d", t->nsplit);
+    if (t->mode < 0 || t->mode > 2) return fail(EZDIT_E_INVALID, "mode = %d (0 COPY, 1 RES, 2 SET)", t->mode);
+    if ((t->wt | t->variant | t->affine | t->part_bf16) & ~1) return fail(EZDIT_E_INVALID, "wt, variant, affine and part_bf16 are 0 or 1");
+    if (t->D % 4) return fail(EZDIT_E_UNSUPPORTED, "D = %d is not a multiple of 4 (16-byte chunks)", t->D);
+    if (t->D > 2048) return fail(EZDIT_E_UNSUPPORTED, "D = %d is beyond the 2048 columns of the workgroup-per-row form", t->D);
+    if (t->nsplit > 8) return fail(EZDIT_E_UNSUPPORTED, "nsplit = %d is beyond the 8 slabs of the workgroup-per-row form", t->nsplit);
+    auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
+    const int width = t->skip ? 2 * t->D : t->D;
+    if (t->mode != 2 && !t->h_in) return fail(EZDIT_E_INVALID, "mode %d reads h_in", t->mode);
+    if (t->mode != 0 && t->nsplit > 0) {
+        if (!t->part) return fail(EZDIT_E_INVALID, "mode %d with %d slabs reads part", t->mode, t->nsplit);
+        if (t->ld_part < t->D || t->ld_part % 4 || t->part_stride % 4 || (t->nsplit > 1 && t->part_stride <= 0))
+            return fail(EZDIT_E_INVALID, "bad slab layout ld_part=%d part_stride=%ld", t->ld_part, (long)t->part_stride);
+    }
+    if (t->gate && (t->gate_slot_stride < 0 || t->gate_slot_stride % 4)) return fail(EZDIT_E_INVALID, "gate_slot_stride = %ld", (long)t->gate_slot_stride);
+    if (t->cn && !t->skip) return fail(EZDIT_E_INVALID, "cn without skip");
+    if (t->skip && !t->u) return fail(EZDIT_E_INVALID, "skip without u: the concatenation exists for the LayerNorm only");
+    if (t->u) {
+        if (!t->ln_g || !t->ln_c) return fail(EZDIT_E_INVALID, "u without ln_g / ln_c");
+        if (t->ln_slot_stride < 0 || t->ln_slot_stride % 4) return fail(EZDIT_E_INVALID, "ln_slot_stride = %ld", (long)t->ln_slot_stride);
+        if (t->ld_u < width || t->ld_u % 4) return fail(EZDIT_E_INVALID, "ld_u = %d: below the written width %d or not a multiple of 4", t->ld_u, width);
+    }
+    if (misaligned(t->h_in, 16) || misaligned(t->h_out, 16) || misaligned(t->part, t->part_bf16 ? 8 : 16) || misaligned(t->bias, 16) || misaligned(t->gate, 16) ||
+        misaligned(t->ln_g, 16) || misaligned(t->ln_c, 16) || misaligned(t->skip, 16) || misaligned(t->cn, 16) || misaligned(t->u, 8))
+        return fail(EZDIT_E_INVALID, "a pointer breaks the alignment of the 16-byte (bf16: 8-byte) accesses");
+    const bool slotted = (t->gate && t->mode != 0) || t->u;
+    if (slotted) {
+        if (t->n_slots < 1) return fail(EZDIT_E_INVALID, "n_slots = %d", t->n_slots);
+        // a test hook may wait: the slots bound what the kernel reads of the gate / LayerNorm tables
+        const int B = (t->M + t->L - 1) / t->L;
+        int cur = 0;
+        std::vector<int> rs((size_t)B, 0);
+        if (t->cur_step || t->row_slot) HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+        if (t->cur_step) HIPCHK(hipMemcpy(&cur, t->cur_step, sizeof(int), hipMemcpyDeviceToHost));
+        if (t->row_slot) HIPCHK(hipMemcpy(rs.data(), t->row_slot, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; ++b)
+            if (cur + rs[b] < 0 || cur + rs[b] >= t->n_slots)
+                return fail(EZDIT_E_INVALID, "slot %d + %d of batch element %d outside [0, n_slots = %d)", cur, rs[b], b, t->n_slots);
+    }
+    RowArgs r;
+    memset(&r, 0, sizeof r);
+    r.h_in = t->h_in; r.h_out = t->h_out;
+    r.part = (const float*)t->part; r.nsplit = t->nsplit; r.part_stride = (long)t->part_stride; r.ld_part = t->ld_part; r.part_bf16 = t->part_bf16;
+    r.bias = t->bias; r.gate = t->gate; r.gate_slot_stride = (long)t->gate_slot_stride; r.mode = t->mode;
+    r.ln_g = t->ln_g; r.ln_c = t->ln_c; r.ln_slot_stride = (long)t->ln_slot_stride;
+    r.cn_scale = t->cn_scale; r.cn_tab = t->cn_tab; r.skip = t->skip; r.cn = t->cn;
+    r.u = (bf16_t*)t->u; r.ld_u = t->ld_u;
+    r.M = t->M; r.D = t->D; r.L = t->L;
+    r.cur_step = t->cur_step; r.row_slot = t->row_slot;
+    r.wt = t->wt; r.variant = t->variant; r.affine = t->affine;
+    return hook_launch("k_row", "", [&] { launch_row(r, (hipStream_t)stream); return 0; });
+}
+
+// per-head LayerNorm (+ RoPE) of q / k and the cast of v into the attention layouts (launch_headnorm: k_headnorm), the un-fused form of the fused QKV epilogue
+int ezdit_test_headnorm(const float* x, int ldx, int q_col, int k_col, int v_col, const float* qn_w, const float* qn_b, const float* kn_w, const float* kn_b,
+                        const float* rope_cos, const float* rope_sin, void* q, void* k, void* v, int B, int H, int L, int Lp, int dh, ezdit_stream stream) {
+    if (B <= 0 || H <= 0 || L <= 0 || Lp < L) return fail(EZDIT_E_INVALID, "bad shape B=%d H=%d L=%d Lp=%d", B, H, L, Lp);
+    if (dh != 64 && dh != 72) return fail(EZDIT_E_UNSUPPORTED, "head_dim %d (64 and 72 are built)", dh);
+    if (q_col < -1 || k_col < -1 || v_col < -1 || (q_col < 0 && k_col < 0 && v_col < 0)) return fail(EZDIT_E_INVALID, "no part to build");
+    const int cols[3] = {q_col, k_col, v_col};
+    for (int i = 0; i < 3; ++i)
+        if (cols[i] >= 0 && (long)cols[i] + (long)H * dh > ldx) return fail(EZDIT_E_INVALID, "columns [%d, %d + H dh) do not fit ldx = %d", cols[i], cols[i], ldx);
+    // q / k rows are read with 8-byte loads, v rows with 16-byte loads
+    if (ldx % 2 || (q_col >= 0 && q_col % 2) || (k_col >= 0 && k_col % 2)) return fail(EZDIT_E_INVALID, "ldx = %d or a q / k column offset breaks the 8-byte loads", ldx);
+    if (v_col >= 0 && (ldx % 4 || v_col % 4)) return fail(EZDIT_E_INVALID, "ldx = %d or v_col = %d breaks the 16-byte loads", ldx, v_col);
+    if (!x) return fail(EZDIT_E_INVALID, "null x");
+    if (q_col >= 0 && (!q || !qn_w || !qn_b)) return fail(EZDIT_E_INVALID, "q is present: q, qn_w and qn_b are needed");
+    if (k_col >= 0 && (!k || !kn_w || !kn_b)) return fail(EZDIT_E_INVALID, "k is present: k, kn_w and kn_b are needed");
+    if (v_col >= 0 && !v) return fail(EZDIT_E_INVALID, "v is present: v is needed");
+    if (!rope_cos != !rope_sin) return fail(EZDIT_E_INVALID, "rope_cos and rope_sin come together");
+    auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
+    if (misaligned(x, v_col >= 0 ? 16 : 8) || misaligned(q, 4) || misaligned(k, 4) || misaligned(v, 16))
+        return fail(EZDIT_E_INVALID, "a pointer breaks the alignment of the vector accesses");
+    HeadNormArgs hn;
+    memset(&hn, 0, sizeof hn);
+    hn.x = x; hn.ldx = ldx; hn.q_col = q_col; hn.k_col = k_col; hn.v_col = v_col;
+    hn.qn_w = qn_w; hn.qn_b = qn_b; hn.kn_w = kn_w; hn.kn_b = kn_b; hn.rope_cos = rope_cos; hn.rope_sin = rope_sin;
+    hn.q = (bf16_t*)q; hn.k = (bf16_t*)k; hn.v = (bf16_t*)v;
+    hn.B = B; hn.H = H; hn.L = L; hn.Lp = Lp; hn.dh = dh;
+    return hook_launch("k_headnorm", "", [&] { launch_headnorm(hn, (hipStream_t)stream); return 0; });
+}
+
+// the input assembly of a forward (launch_assemble: k_assemble)
+int ezdit_test_assemble(const float* x, int x_rows, int in_ch, const float* gt, const uint8_t* gt_mask, const float* mask_embed, void* out, int ldo,
+                        int B, int C, int L, const int32_t* dev_lens, ezdit_stream stream) {
+    if (B <= 0 || C <= 0 || L <= 0) return fail(EZDIT_E_INVALID, "bad shape B=%d C=%d L=%d", B, C, L);
+    if (in_ch != C && in_ch != 2 * C + 1) return fail(EZDIT_E_INVALID, "in_ch = %d is neither C = %d nor 2 C + 1", in_ch, C);
+    if (x_rows <= 0 || B % x_rows) return fail(EZDIT_E_INVALID, "x_rows %d does not divide B %d", x_rows, B);
+    if (!gt != !gt_mask) return fail(EZDIT_E_INVALID, "gt and gt_mask come together");
+    if (ldo < 2 * C + 1) return fail(EZDIT_E_INVALID, "ldo = %d is below the 2 C + 1 = %d assembled channels", ldo, 2 * C + 1);
+    if (!x || !out || (in_ch == C && !mask_embed)) return fail(EZDIT_E_INVALID, "null argument");
+    if (dev_lens) {
+        std::vector<int> ln((size_t)B);
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+        HIPCHK(hipMemcpy(ln.data(), dev_lens, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
+        for (int i = 0; i < B; ++i)
+            if (ln[i] < 1 || ln[i] > L) return fail(EZDIT_E_INVALID, "lens[%d] = %d outside [1, L = %d]", i, ln[i], L);
+    }
+    AssembleArgs as;
+    as.x = x; as.x_rows = x_rows; as.in_ch = in_ch; as.gt = gt; as.gt_mask = gt_mask; as.mask_embed = mask_embed;
+    as.out = (bf16_t*)out; as.ldo = ldo; as.B = B; as.C = C; as.L = L; as.lens = dev_lens;
+    return hook_launch("k_assemble", "", [&] { launch_assemble(as, (hipStream_t)stream); return 0; });
+}
+
 int ezdit_debug_buffer(ezdit_handle* h, const char* name, void** ptr, size_t* bytes) {
     if (!h || !h->ws || !name) return fail(EZDIT_E_STATE, "bind workspace first");
     auto it = h->bufs.find(name);

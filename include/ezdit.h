@@ -407,6 +407,39 @@ int ezdit_test_attention_varlen(ezdit_handle* h, const void* dev_q, const void* 
  * dev_lens int32 [B] on the DEVICE or NULL: inputs at frames >= lens[b] read as zero, outputs at frames >= lens[b] are written as zero (checked as above). */
 int ezdit_test_final_conv(const float* dev_y, int ldy, const float* dev_w, const float* dev_b, float* dev_out, int B, int C, int L,
                           const int32_t* dev_lens, ezdit_stream stream);
+/* unit-test hook of the row operator (csrc/rowops.hip k_row, csrc/rowbody.h k_row_w; the fields are those of csrc/common.h RowArgs, one for one):
+ *   h_new = h_in (mode 0) | h_in + gate[slot] * (sum of nsplit slabs + bias) (mode 1) | sum of nsplit slabs + bias (mode 2)        fp32 [M][D] -> h_out (NULL: not stored)
+ *   u = LN(h_new) ln_g[slot] + ln_c[slot], or with skip: LN over [h_new | skip + s cn] (width 2 D, ln_g / ln_c of length 2 D)      bf16 [M][ld_u], zero up to ld_u
+ * slot = *cur_step + row_slot[row / L] (either NULL = 0), s = cn_tab[row / L] or cn_scale.  Slabs: fp32 or bf16 (part_bf16) [nsplit][part_stride] with rows of ld_part.
+ * variant 1 asks for the wave-per-row form (taken up to D = 1280, 4 bf16 slabs or 1 fp32 slab; otherwise the workgroup-per-row form runs), affine its XCD row map.
+ * n_slots = the slots the gate / LayerNorm tables hold.  Checked before anything is launched -- EZDIT_E_UNSUPPORTED: D % 4, D > 2048, nsplit > 8; EZDIT_E_INVALID: nsplit < 0,
+ * a pointer the mode needs is NULL, ld_u below the written width, ld_u or a stride not a multiple of 4, M / D / L <= 0, cn without skip, skip without u, u without ln_g / ln_c,
+ * a misaligned pointer, and (the hook waits for `stream` and reads cur_step / row_slot back) a slot outside [0, n_slots). */
+typedef struct ezdit_test_row_args {
+    const float* h_in; float* h_out;
+    const void* part; int32_t nsplit; int32_t ld_part; int64_t part_stride; int32_t part_bf16; int32_t mode;
+    const float* bias; const float* gate; int64_t gate_slot_stride;
+    const float* ln_g; const float* ln_c; int64_t ln_slot_stride;
+    const float* skip; const float* cn; const float* cn_tab; float cn_scale; int32_t ld_u;
+    void* u;
+    int32_t M, D, L, n_slots;
+    const int32_t* cur_step; const int32_t* row_slot;
+    int32_t wt, variant, affine, reserved;
+} ezdit_test_row_args;
+int ezdit_test_row(const ezdit_test_row_args* args, ezdit_stream stream);
+/* unit-test hook of k_headnorm (csrc/rowops.hip): x fp32 [B L][ldx] holds the parts at the columns q_col / k_col / v_col + head * dh (-1 = absent); q, k = per-head
+ * LayerNorm with the q / k affine [dh], then the half-split RoPE at position row % L (rope_cos / rope_sin fp32 [>= L][dh / 2], both NULL = no RoPE) -> bf16 [B][H][Lp][DQK];
+ * v = bf16(x) -> [B][H][Lp][DV] (DQK / DV = 64 / 64 or 80 / 96).  Only rows < L and channels < dh are written.  EZDIT_E_UNSUPPORTED: dh other than 64 / 72;
+ * EZDIT_E_INVALID: Lp < L, ldx or a column offset that breaks the 8-byte (q / k) or 16-byte (v) loads or does not hold H dh columns, a present part whose pointers are NULL. */
+int ezdit_test_headnorm(const float* dev_x, int ldx, int q_col, int k_col, int v_col, const float* dev_qn_w, const float* dev_qn_b, const float* dev_kn_w,
+                        const float* dev_kn_b, const float* dev_rope_cos, const float* dev_rope_sin, void* dev_q, void* dev_k, void* dev_v,
+                        int B, int H, int L, int Lp, int dh, ezdit_stream stream);
+/* unit-test hook of k_assemble (csrc/rowops.hip): in_ch = C: out bf16 [B L][ldo] = [x[b % x_rows] | gt where gt_mask == 0, else mask_embed | gt_mask channel 0, or 1 without
+ * gt | zeros] from x fp32 [x_rows][C][L], gt fp32 / gt_mask uint8 [x_rows][C][L] (both or neither), mask_embed fp32 [C]; in_ch = 2 C + 1: x fp32 [B][in_ch][L] is already
+ * assembled (transpose + cast).  dev_lens int32 [B] on the DEVICE or NULL: frames >= lens[b] become zero rows.  EZDIT_E_INVALID: another in_ch, x_rows that does not divide
+ * B, gt without gt_mask or the reverse, ldo < 2 C + 1, lens outside [1, L] (read back as above). */
+int ezdit_test_assemble(const float* dev_x, int x_rows, int in_ch, const float* dev_gt, const uint8_t* dev_gt_mask, const float* dev_mask_embed, void* dev_out, int ldo,
+                        int B, int C, int L, const int32_t* dev_lens, ezdit_stream stream);
 /* copy an internal fp32/bf16 buffer (by name, e.g. "h", "u", "q", "k", "v", "mod") for debugging. */
 int ezdit_debug_buffer(ezdit_handle* h, const char* name, void** dev_ptr, size_t* bytes);
 /* number of kernel launches issued by the last ezdit_forward (host counter). */
