@@ -256,6 +256,80 @@ class EzAudio:
             outs.append(out)
         return sr, outs
 
+    def audio_to_audio(self, text, audio, strength=0.5, guidance_scale=5, guidance_rescale=0.75, ddim_steps=100, eta=1, random_seed=None,
+                       randomize_seed=False, solver='ddim'):
+        """Re-render a recording under a prompt, staying as close to it as `strength` says (not in the reference: the standard "start the sampler from the
+        noised clip" of image-to-image, SDEdit).  `audio` is a path or a 1-D numpy waveform at the model's sample rate, peak-normalised and encoded whole;
+        `strength` in (0, 1] is the share of the `ddim_steps` that are run (scheduler.start_step): 1 starts from pure noise, the plain generate_audio of the
+        clip's length, small values change little.  Returns (sr, waveform) of latent_frames * ratio samples.  `solver` as in generate_audio.
+
+        Batched extension: `text` may be a list of prompts, one request per entry in ONE ragged encode, ONE sampler call and ONE ragged decode; the result is
+        then (sr, [one 1-D array per request]).  `audio` is then a list of the same size, or one clip shared by all requests; `strength`, `guidance_scale`,
+        `guidance_rescale`, `eta` and `random_seed` may each be one value or a list with one entry per request; `ddim_steps` stays one value.  A prompt ''
+        inside a list runs without guidance; `randomize_seed` draws one seed per request.  The autoencoder must take `lengths=` and have `latent_lengths`
+        (this package's Autoencoder does).
+
+        Audio quality versus strength on the real checkpoints is unmeasured."""
+        check_solver(solver, eta)
+        if isinstance(ddim_steps, (list, tuple)):
+            raise ValueError('ddim_steps must be one value per call: per-prompt step counts are not supported')
+        sr = self.params['autoencoder']['sr']
+        ratio = sr // self.params['autoencoder']['latent_sr']
+        batched = not isinstance(text, str)
+        n = len(text) if batched else 1
+        for name, v in (('audio', audio), ('strength', strength), ('guidance_scale', guidance_scale), ('guidance_rescale', guidance_rescale), ('eta', eta),
+                        ('random_seed', random_seed)):
+            if isinstance(v, (list, tuple)) and (not batched or len(v) != n):
+                raise ValueError(f'a list of {name} needs a list of prompts of the same size')
+        if batched and n == 0:
+            raise ValueError('a list of prompts needs at least one prompt')
+        per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n   # noqa: E731
+        self.noise_scheduler.set_timesteps(ddim_steps)
+        for s in per(strength):
+            self.noise_scheduler.start_step(s)   # a strength outside (0, 1], or one that leaves no step to run, raises before anything is encoded
+        if batched and not hasattr(self.autoencoder, 'latent_lengths'):
+            raise NotImplementedError('a batched audio_to_audio needs an autoencoder that takes lengths= and has latent_lengths (ezaudio_amd.vae.Autoencoder)')
+        if isinstance(audio, (list, tuple)):
+            clips = [self._load_edit_clip(a) for a in audio]
+        else:
+            clips = [self._load_edit_clip(audio)] * n                          # one clip for every request: loaded once
+        # (the autoencoder's own samples-per-frame where it tells: an injected one need not have the ratio of the yml)
+        n_frames = self.autoencoder.latent_lengths if hasattr(self.autoencoder, 'latent_lengths') else (lambda ns: [v // ratio for v in ns])
+        for c in clips:
+            if n_frames([len(c)])[0] < 1:
+                raise ValueError(f'a clip of {len(c)} samples is shorter than one latent frame')
+        if not batched:
+            if text == '':
+                guidance_scale = None
+                print('empty input')
+            if randomize_seed:
+                random_seed = random.randint(0, MAX_SEED)
+            wav = torch.tensor(clips[0]).unsqueeze(0).unsqueeze(1).to(self.device)
+            latent = self.autoencoder(audio=wav)
+            L = latent.shape[-1]
+            pred = inference(self.autoencoder, self.unet, None, None, self.tokenizer, self.text_encoder, self.params, self.noise_scheduler, text, None, L,
+                             guidance_scale, guidance_rescale, ddim_steps, eta, random_seed, self.device, solver=solver, init_latents=latent,
+                             strength=strength)
+            return sr, pred.cpu().numpy().squeeze(0).squeeze(0)
+        text = list(text)
+        if '' in text:
+            guidance_scale = [None if t == '' else g for t, g in zip(text, per(guidance_scale))]
+            print('empty input')
+        if randomize_seed:
+            random_seed = [random.randint(0, MAX_SEED) for _ in text]
+        samples = [len(c) for c in clips]
+        wav = torch.zeros(n, 1, max(samples))
+        for i, c in enumerate(clips):
+            wav[i, 0, :samples[i]] = torch.from_numpy(c)
+        latent = self.autoencoder(audio=wav.to(self.device), lengths=samples)
+        frames = [int(v) for v in self.autoencoder.latent_lengths(samples)]
+        pred = inference(self.autoencoder, self.unet, None, None, self.tokenizer, self.text_encoder, self.params, self.noise_scheduler, text, None, frames,
+                         guidance_scale, guidance_rescale, ddim_steps, eta, random_seed, self.device, solver=solver, init_latents=latent,
+                         strength=per(strength))
+        pred = pred.cpu().numpy()
+        up = pred.shape[-1] // max(frames)                                     # samples per latent frame, as decoded
+        return sr, [pred[i, 0, :f * up] for i, f in enumerate(frames)]
+
 
 class EzAudio_ControlNet(EzAudio):
     """api/controlnet.py:31-160: EzAudio-L + energy ControlNet (``model_name='energy'``)."""

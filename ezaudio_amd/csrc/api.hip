@@ -60,6 +60,7 @@ struct WsPtrs {  // workspace regions used on the per-step path, resolved once a
     float2* zstat_skip; float* zt_skip; bf16_t* ucat_z;              // ... of the out-blocks' LN_2D([x | skip]) -> skip_linear: the skips' statistics (kept from the in-block to its out-block), static tables
     int* lens;   // [B] per-batch-element valid frames (ezdit_set_lengths); read by the kernels only while ezdit_handle::lens_on
     float *spg, *spc;   // per-sample sampler settings (ezdit_sampler_set_sample_params): [P][2] (guidance_scale, guidance_rescale) and [n_steps][P][8] DDIM coefficients; read only while sp_on
+    int* start;  // [P] first step of each sample (ezdit_sampler_set_start); read by k_cfg_stats / k_cfg_apply only while ezdit_handle::start_on
     float* cns;  // [B] per-batch-element conditioning_scale of the attached ControlNet (ezdit_sampler_set_cn_scales); read by the row kernel only while ezdit_handle::cns_on
     float* zd;   // [nblk][B][D] constant cross-attention-out vectors of the single-key batch elements (opt_xkey1)
 };
@@ -114,6 +115,11 @@ struct ezdit_handle {
     bool ms_on = false;
     float* ms_hist = nullptr;
     std::vector<float> coef_host;
+    // start table (ezdit_sampler_set_start), the contract of the sample table: the last two kernels of the step read the device table at run time, a captured
+    // step serves every set of values, switching it on or off changes the kernels and drops the graph.  start_min is the step the run begins at
+    bool start_on = false;
+    int start_min = 0;
+    std::vector<int> start_host;   // host mirror (the source of the asynchronous upload)
 
     int launches = 0;
     bool is_cn = false;          // ControlNet variant (cfg.controlnet)
@@ -489,6 +495,7 @@ size_t carve(const ezdit_handle* h, int B, int L, int Lc, int n_slots, std::map<
         add("spg", (size_t)ezdit_handle::sp_cap(B) * 2 * 4);        // per-sample sampler settings, at the very end (no existing buffer moves): at most
         add("spc", (size_t)ns * ezdit_handle::sp_cap(B) * 8 * 4);   // n_slots * (B / 2 + 1) * 32 bytes + 2 KB more workspace than without them
         add("cns", 256 * sizeof(float));   // per-batch-element conditioning_scale (B <= 240), behind `lens` and the sample tables for the same reason: no existing buffer moves
+        add("start", 256 * sizeof(int));   // per-sample first step (ezdit_sampler_set_start; P <= B <= 240), at the very end for the same reason: 1 KB
     }
     return off;
 }
@@ -669,7 +676,7 @@ void resolve_workspace(ezdit_handle* h) {
     p.ao = h->buf<bf16_t>("ao"); p.act = h->buf<bf16_t>("act"); p.part = h->buf<float>("part"); p.y = h->buf<float>("y");
     p.pred = h->buf<float>("pred"); p.kmask = h->buf<uint8_t>("kmask"); p.kc = h->buf<bf16_t>("kc"); p.vc = h->buf<bf16_t>("vc");
     p.mod = h->buf<float>("mod"); p.modf = h->buf<float>("modf");
-    p.zd = h->buf<float>("zd"); p.lens = h->buf<int>("lens"); p.spg = h->buf<float>("spg"); p.spc = h->buf<float>("spc"); p.cns = h->buf<float>("cns");
+    p.zd = h->buf<float>("zd"); p.lens = h->buf<int>("lens"); p.spg = h->buf<float>("spg"); p.spc = h->buf<float>("spc"); p.cns = h->buf<float>("cns"); p.start = h->buf<int>("start");
     p.zstat = h->buf<float2>("zstat"); p.zt_qkv = h->buf<float>("zt_qkv"); p.zt_geglu = h->buf<float>("zt_geglu"); p.zt_q2 = h->buf<float>("zt_q2");
     p.zstat_skip = h->buf<float2>("zstat_skip"); p.zt_skip = h->buf<float>("zt_skip"); p.ucat_z = h->buf<bf16_t>("ucat_z");
     if (h->is_cn) { p.cembed = h->buf<float>("cembed"); p.cnres = h->buf<float>("cnres"); p.skipbf = h->buf<bf16_t>("skipbf"); }
@@ -816,6 +823,7 @@ int ezdit_bind_workspace(ezdit_handle* h, void* ws, size_t bytes, int B, int L, 
     h->sp_on = false;
     h->cns_on = false;
     h->ms_on = false; h->ms_hist = nullptr; h->coef_host.clear();
+    h->start_on = false; h->start_min = 0;
     drop_graph(h);
     for (ezdit_handle* u : h->cn_users) drop_graph(u);   // a graph captured with this ControlNet attached points at its old buffers
     // zero everything once: all padding rows / columns / keys stay zero for the lifetime of the binding
@@ -1022,7 +1030,10 @@ int ezdit_prepare_timesteps(ezdit_handle* h, const int32_t* ts, int n, int per_r
 int ezdit_set_step(ezdit_handle* h, int step, ezdit_stream stream) {
     if (!h || !h->ws) return fail(EZDIT_E_STATE, "bind workspace first");
     if (step < 0 || step >= h->n_slots) return fail(EZDIT_E_INVALID, "step %d out of range", step);
-    if (h->ms_on && step != 0) return fail(EZDIT_E_STATE, "multistep solver: the history is not step %d's (only a rewind to step 0 keeps it right)", step - 1);
+    // start table: only a rewind to the run's own beginning (first-order for every sample active at it, so also with the multistep solver on)
+    if (h->start_on && step != h->start_min)
+        return fail(EZDIT_E_STATE, "start table: step %d is not the run's first step %d (only a rewind to it keeps every sample's trajectory)", step, h->start_min);
+    if (h->ms_on && !h->start_on && step != 0) return fail(EZDIT_E_STATE, "multistep solver: the history is not step %d's (only a rewind to step 0 keeps it right)", step - 1);
     launch_set_int(h->p.ints, step, 0, (hipStream_t)stream);
     h->steps_done = step;
     return EZDIT_OK;
@@ -1555,6 +1566,7 @@ int ezdit_sampler_begin(ezdit_handle* h, float* latents, int P, const float* noi
     h->gscale = guidance_scale; h->grescale = guidance_rescale;
     h->sp_on = false;   // per-sample settings belong to one sampler call (the graph is dropped below anyway)
     h->ms_on = false; h->ms_hist = nullptr;   // ... and so does the multistep solver
+    h->start_on = false; h->start_min = 0;    // ... and the start table
     h->s_gt = gt; h->s_gt_mask = gt_mask;
     if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
     if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
@@ -1605,6 +1617,7 @@ static int sampler_step(ezdit_handle* h, hipStream_t st) {
     a.lens = h->lens_dev(); a.L = h->L;
     a.sp_g = h->sp_on ? h->p.spg : nullptr; a.sp_c = h->sp_on ? h->p.spc : nullptr; a.sp_g_stride = 2;
     a.x0_hist = h->ms_on ? h->ms_hist : nullptr;
+    a.start = h->start_on ? h->p.start : nullptr;
     launch_cfg_ddim(a, h->p.cfgpart, st);   // its last kernel also advances the device step counter
     h->launches += (h->sp_on || (h->gscale > 0.f && h->grescale > 0.f)) ? 2 : 1;
     const hipError_t e = hipGetLastError();
@@ -1626,7 +1639,7 @@ int ezdit_cfg_ddim_step(const float* pred, float* latents, const float* noise, c
     a.step_inc = nullptr; a.done = nullptr;
     a.lens = nullptr; a.L = n;
     a.sp_g = nullptr; a.sp_c = nullptr; a.sp_g_stride = 0;
-    a.x0_hist = nullptr;
+    a.x0_hist = nullptr; a.start = nullptr;
     launch_cfg_ddim(a, scratch, (hipStream_t)stream);
     return EZDIT_OK;
 }
@@ -1646,7 +1659,7 @@ int ezdit_cfg_ddim_step_per_sample(const float* pred, float* latents, const floa
     a.step_inc = nullptr; a.done = nullptr;
     a.lens = lens; a.L = lens ? L : n;
     a.sp_g = params; a.sp_c = params + 2; a.sp_g_stride = 8;
-    a.x0_hist = nullptr;
+    a.x0_hist = nullptr; a.start = nullptr;
     return hook_launch("k_cfg_*", "", [&] { launch_cfg_ddim(a, scratch, (hipStream_t)stream); return 0; });
 }
 
@@ -1665,7 +1678,7 @@ int ezdit_cfg_multistep_step(const float* pred, float* latents, float* x0_hist, 
     a.step_inc = nullptr; a.done = nullptr;
     a.lens = lens; a.L = lens ? L : n;
     a.sp_g = params; a.sp_c = params + 2; a.sp_g_stride = 8;
-    a.x0_hist = x0_hist;
+    a.x0_hist = x0_hist; a.start = nullptr;
     return hook_launch("k_cfg_*", "", [&] { launch_cfg_ddim(a, scratch, (hipStream_t)stream); return 0; });
 }
 
@@ -1698,6 +1711,50 @@ int ezdit_sampler_set_multistep(ezdit_handle* h, const float* c_hist, int n_step
     if (on != h->ms_on || (on && x0_hist != h->ms_hist)) drop_graph(h);   // (another history buffer is another kernel argument)
     h->ms_on = on;
     h->ms_hist = on ? x0_hist : nullptr;
+    return EZDIT_OK;
+}
+
+int ezdit_add_noise(const float* clean, float* latents, const float* params, float scale, float shift, const int32_t* lens, int L, int P, int n,
+                    ezdit_stream stream) {
+    if (!clean || !latents || !params || P < 1 || n < 1) return fail(EZDIT_E_INVALID, "bad argument");
+    if (L < 1 || n % L) return fail(EZDIT_E_INVALID, "L = %d must divide n = %d", L, n);
+    AddNoiseArgs a;
+    a.clean = clean; a.latents = latents; a.params = params; a.scale = scale; a.shift = shift;
+    a.lens = lens; a.L = L; a.P = P; a.n = n;
+    return hook_launch("k_add_noise", "", [&] { launch_add_noise(a, (hipStream_t)stream); return 0; });
+}
+
+int ezdit_sampler_set_start(ezdit_handle* h, const int32_t* start_steps, int P, ezdit_stream stream) {
+    if (!h) return fail(EZDIT_E_INVALID, "null handle");
+    if (!h->ws || !h->latents) return fail(EZDIT_E_STATE, "ezdit_sampler_begin first");
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    if (cs != hipStreamCaptureStatusNone) return fail(EZDIT_E_STATE, "ezdit_sampler_set_start inside a stream capture (it uploads from host memory and waits)");
+    if ((int)h->coef_host.size() != h->n_steps * 8) return fail(EZDIT_E_STATE, "ezdit_sampler_begin first");
+    if (!start_steps || P == 0) {   // off: every sample runs from step 0 again
+        if (h->start_on) {   // (the run it belonged to began at start_min: the plain run begins at 0)
+            drop_graph(h);
+            launch_set_int(h->p.ints, 0, 0, st);
+            h->steps_done = 0;
+        }
+        h->start_on = false; h->start_min = 0;
+        return EZDIT_OK;
+    }
+    if (P != h->P) return fail(EZDIT_E_INVALID, "P = %d, the sampler was begun with P = %d", P, h->P);
+    int lo = h->n_steps;
+    for (int p = 0; p < P; ++p) {
+        if (start_steps[p] < 0 || start_steps[p] >= h->n_steps) return fail(EZDIT_E_INVALID, "start_steps[%d] = %d outside [0, n_steps = %d)", p, (int)start_steps[p], h->n_steps);
+        if (start_steps[p] < lo) lo = start_steps[p];
+    }
+    HIPCHK(hipStreamSynchronize(st));   // an earlier upload may still be reading the host mirror
+    h->start_host.assign(start_steps, start_steps + P);
+    HIPCHK(hipMemcpyAsync(h->p.start, h->start_host.data(), (size_t)P * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    launch_set_int(h->p.ints, lo, 0, st);
+    h->steps_done = lo;
+    if (!h->start_on) drop_graph(h);
+    h->start_on = true; h->start_min = lo;
     return EZDIT_OK;
 }
 

@@ -379,9 +379,22 @@ struct CfgDdimArgs {
     // of the CALL's row coef[step * 8 ..] in the fused sampler, the per-sample table on or off (it depends on the schedule only); in the stand-alone
     // operator it is slot 5 of the sample's row sp_c[p * 8 ..], or hc[5].  c_hist == 0: x0_hist is written, not read
     float* x0_hist;
+    // start table of the fused sampler (null = off: every sample runs every step, the kernels they have always been).  On: int [P], sample p is HELD while
+    // the device step < start[p]: k_cfg_stats returns for it, k_cfg_apply makes no read of pred / noise / x0_hist and no write of latents / x0_hist for it
+    // (its workgroups still arrive at `done`), and at step == start[p] its c_hist is 0 (its first step is first-order and does not read the history)
+    const int* start;
 };
 void launch_cfg_ddim(const CfgDdimArgs& a, float* partial /* [P][64][4] scratch */, hipStream_t st);
 void launch_set_int(int* p, int v, int add, hipStream_t st);  // *p = add ? *p + v : v
+struct AddNoiseArgs {  // latents[p][i] = sa_p * ((clean[p][i] + shift) * scale) + sb_p * latents[p][i]: a clean VAE latent noised to sample p's start step
+    const float* clean;   // [P][n] in VAE space (before scale_shift); row p is not read when params[p] is exactly (0, 1)
+    float* latents;       // [P][n] in/out: the init noise on entry; row p is not touched when params[p] is exactly (0, 1)
+    const float* params;  // [P][2] (sa, sb) on the device
+    float scale, shift;   // scale_shift: (x + shift) * scale
+    const int* lens; int L;   // padded batch (null = off): frames >= lens[p] are written as zero whatever clean / latents hold there (n = C * L)
+    int P, n;
+};
+void launch_add_noise(const AddNoiseArgs& a, hipStream_t st);
 struct Conv1dArgs {  // out[b][co][lo] = act(bias[co] + sum_{ci,k} w[co][ci][k] * x[b][ci][lo*stride + k - pad]); fp32
     const float* x; const float* w; const float* b; float* out;
     int B, Cin, Cout, Lin, Lout, ksize, stride, pad, act;  // act 1 = SiLU

@@ -475,12 +475,18 @@ __global__ void k_rope_table(float* cosT, float* sinT, int max_len, int dh) {
 //                 std(c)/std(g) with torch.std's unbiased normalisation, and updates its chunk of the latent.
 //                 MS (CfgDdimArgs.x0_hist given): the DPM-Solver++(2M) form of the update, prev += c_hist (x0 - x0 of the step before); MS = false is
 //                 the DDIM kernel as it was, instruction for instruction.
+//   ST (CfgDdimArgs.start given): sample p is HELD while step < start[p] -- no statistics, no update, no read of pred / noise / history, no write -- and its
+//                 first step (step == start[p]) is first-order.  ST = false is the source as it was.
 constexpr int CFG_NB = 64;
 
+template <bool ST>
 __global__ __launch_bounds__(256) void k_cfg_stats(CfgDdimArgs a, float* partial) {
     __shared__ float red[4];
     const int p = blockIdx.y, blk = blockIdx.x;
     const int n = a.n;
+    if constexpr (ST) {   // held sample (workgroup-uniform): k_cfg_apply does not read its partial sums
+        if ((a.cur_step ? *a.cur_step : 0) < a.start[p]) return;
+    }
     const float* pc = a.pred + (long)p * n;
     const float* pu = a.pred + (long)(a.P + p) * n;
     float gs = a.guidance_scale;
@@ -504,18 +510,22 @@ __global__ __launch_bounds__(256) void k_cfg_stats(CfgDdimArgs a, float* partial
     }
 }
 
-template <bool MS>
+template <bool MS, bool ST>
 __global__ __launch_bounds__(256) void k_cfg_apply(CfgDdimArgs a, const float* partial) {
     const int p = blockIdx.y, blk = blockIdx.x;
     const int n = a.n;
     const int step = a.cur_step ? *a.cur_step : 0;
+    // start table: a sample that has not begun yet is held (workgroup-uniform).  The workgroup still ARRIVES at the counter below: it branches around the
+    // element loop, it does not return
+    bool held = false, first = false;
+    if constexpr (ST) { const int s0 = a.start[p]; held = step < s0; first = step == s0; }
     // the seven settings of this sample: the call's scalars, or its row of the per-sample table (one arithmetic body below either way)
     const float* cf = a.sp_g ? a.sp_c + ((long)step * a.P + p) * 8 : a.cur_step ? a.coef + step * 8 : a.hc;
     const float sa = cf[0], sb = cf[1], cx0 = cf[2], cdir = cf[3], sigma = cf[4];
     const float gs = a.sp_g ? a.sp_g[(long)p * a.sp_g_stride] : a.guidance_scale;
     const float phi = a.sp_g ? a.sp_g[(long)p * a.sp_g_stride + 1] : a.guidance_rescale;
     const bool cfg = gs > 0.f;
-    const bool rescale = cfg && phi > 0.f;
+    const bool rescale = cfg && phi > 0.f && !held;
     float ratio = 1.f;
     if (rescale) {   // wave-uniform
         // the CFG_NB partial sums of this sample: one 16-byte load per thread into LDS, then every thread adds them up in the SAME order as before
@@ -548,7 +558,9 @@ __global__ __launch_bounds__(256) void k_cfg_apply(CfgDdimArgs a, const float* p
     if constexpr (MS) {
         ch = (a.cur_step ? a.coef + step * 8 : a.sp_g ? a.sp_c + (long)p * 8 : a.hc)[5];
         hist = a.x0_hist + (long)p * n;
+        if (first) ch = 0.f;   // the sample's own step 0: first-order, the history is not its
     }
+    if (!held)   // (the loop keeps its indentation: a held sample skips it whole and goes on to the arrival counter)
     for (int i = blk * 256 + threadIdx.x; i < n; i += CFG_NB * 256) {
         if (a.lens && i % a.L >= len) {   // padded frame: zero, whatever pred / noise / the latents hold there
             lat[i] = 0.f;
@@ -588,6 +600,40 @@ __global__ __launch_bounds__(256) void k_cfg_apply(CfgDdimArgs a, const float* p
 }
 
 __global__ void k_set_int(int* p, int v, int add) { *p = add ? *p + v : v; }
+
+// latents = sa_p * ((clean + shift) * scale) + sb_p * latents per sample (the forward `scale_shift` of the VAE latent, then the scheduler's add_noise at
+// the sample's start step), 16 bytes per access when n allows it.  A sample whose row is exactly (0, 1) keeps its latents: nothing of it is read or written.
+constexpr int ADD_NB = 16;
+
+__device__ __forceinline__ float add_noise_1(const AddNoiseArgs& a, float c, float x, float sa, float sb, int i, int len) {
+    if (a.lens && i % a.L >= len) return 0.f;   // padded frame: zero, whatever clean / latents hold there
+    return sa * ((c + a.shift) * a.scale) + sb * x;
+}
+
+__global__ __launch_bounds__(256) void k_add_noise(AddNoiseArgs a) {
+    const int p = blockIdx.y, blk = blockIdx.x;
+    const int n = a.n;
+    const float sa = a.params[2 * p], sb = a.params[2 * p + 1];
+    if (sa == 0.f && sb == 1.f) return;   // workgroup-uniform: the sample starts from its noise
+    const float* cl = a.clean + (long)p * n;
+    float* lat = a.latents + (long)p * n;
+    const int len = a.lens ? a.lens[p] : 0;
+    if ((n & 3) == 0 && ((reinterpret_cast<uintptr_t>(a.clean) | reinterpret_cast<uintptr_t>(a.latents)) & 15) == 0) {
+        const float4* c4 = reinterpret_cast<const float4*>(cl);
+        float4* l4 = reinterpret_cast<float4*>(lat);
+        for (int j = blk * 256 + threadIdx.x; j < n / 4; j += ADD_NB * 256) {
+            const float4 c = c4[j];
+            float4 x = l4[j];
+            x.x = add_noise_1(a, c.x, x.x, sa, sb, 4 * j + 0, len);
+            x.y = add_noise_1(a, c.y, x.y, sa, sb, 4 * j + 1, len);
+            x.z = add_noise_1(a, c.z, x.z, sa, sb, 4 * j + 2, len);
+            x.w = add_noise_1(a, c.w, x.w, sa, sb, 4 * j + 3, len);
+            l4[j] = x;
+        }
+        return;
+    }
+    for (int i = blk * 256 + threadIdx.x; i < n; i += ADD_NB * 256) lat[i] = add_noise_1(a, cl[i], lat[i], sa, sb, i, len);
+}
 
 // small direct Conv1d in fp32 for the ControlNet condition embed (controlnet.py:15-39,65-84): 4 tiny layers, once per call
 __global__ __launch_bounds__(256) void k_conv1d(Conv1dArgs a) {
@@ -684,10 +730,20 @@ void launch_rope_table(float* cosT, float* sinT, int max_len, int dh, hipStream_
 
 void launch_cfg_ddim(const CfgDdimArgs& a, float* partial, hipStream_t st) {
     // per-sample settings: always both launches (which samples rescale is a run-time value of the table)
-    if (a.sp_g || (a.guidance_scale > 0.f && a.guidance_rescale > 0.f))
-        hipLaunchKernelGGL(k_cfg_stats, dim3(CFG_NB, a.P), dim3(256), 0, st, a, partial);
-    if (a.x0_hist) hipLaunchKernelGGL(k_cfg_apply<true>, dim3(CFG_NB, a.P), dim3(256), 0, st, a, partial);
-    else hipLaunchKernelGGL(k_cfg_apply<false>, dim3(CFG_NB, a.P), dim3(256), 0, st, a, partial);
+    const dim3 grid(CFG_NB, a.P);
+    if (a.sp_g || (a.guidance_scale > 0.f && a.guidance_rescale > 0.f)) {
+        if (a.start) hipLaunchKernelGGL(k_cfg_stats<true>, grid, dim3(256), 0, st, a, partial);
+        else hipLaunchKernelGGL(k_cfg_stats<false>, grid, dim3(256), 0, st, a, partial);
+    }
+    if (a.start) {   // the start table: instantiations of their own, the ones without it keep their code
+        if (a.x0_hist) hipLaunchKernelGGL((k_cfg_apply<true, true>), grid, dim3(256), 0, st, a, partial);
+        else hipLaunchKernelGGL((k_cfg_apply<false, true>), grid, dim3(256), 0, st, a, partial);
+    } else if (a.x0_hist) hipLaunchKernelGGL((k_cfg_apply<true, false>), grid, dim3(256), 0, st, a, partial);
+    else hipLaunchKernelGGL((k_cfg_apply<false, false>), grid, dim3(256), 0, st, a, partial);
+}
+
+void launch_add_noise(const AddNoiseArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(k_add_noise, dim3(ADD_NB, a.P), dim3(256), 0, st, a);
 }
 
 // ---- LayerNorm algebra tables (common.h, GemmArgs.z*): G' = g W^T and C' = c W^T (+ bias) for every modulation slot.  The gain / shift

@@ -7,7 +7,8 @@ replicated, there is NO collective inside the denoising loop, and finished laten
 are gathered once with `all_gather` (backend "nccl" = RCCL over xGMI on ROCm; "gloo" on CPU for tests).
 Per-sample RNG streams (seed + global sample index, sampler.draw_noises) make results independent of the placement.
 Per-prompt settings (lists of guidance_scale / guidance_rescale / eta / random_seed, one entry per prompt) are sliced with the prompts; a list of
-seeds makes a prompt's noise independent of its index altogether.
+seeds makes a prompt's noise independent of its index altogether.  Audio-to-audio (`init_latents`, `strength`) is sliced the same way: the clips with the
+prompts (one shared clip is forwarded whole), a list of strengths per prompt.
 Mixed-length batches (sampler.inference with one latent length per prompt): the lengths are sliced with the prompts, every rank pads
 its decoded shard to the GLOBAL longest duration, so `gather_samples` sees equal shapes whatever a shard's own longest sample is.
 """

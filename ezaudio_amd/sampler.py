@@ -65,7 +65,7 @@ class LatentSampler:
 
     def prepare(self, text, text_mask, uncond_text, uncond_mask, init_noise, step_noises, guidance_scale,
                 guidance_rescale, ddim_steps, eta, gt=None, gt_mask=None, controlnet=None, condition=None,
-                conditioning_scale=1.0, lengths=None, solver='ddim'):
+                conditioning_scale=1.0, lengths=None, init_latents=None, start_steps=None, latent_scale=1.0, latent_shift=0.0, solver='ddim'):
         """``lengths`` (list of P ints): init_noise / step_noises / gt / gt_mask are padded to L = max(lengths) frames and sample p is valid on
         [0, lengths[p]) -- its final latent is what a call with that sample alone at its own length gives, zero beyond (include/ezdit.h
         ezdit_set_lengths).  With a ControlNet the table goes to the attached pair (ezdit_sampler_set_pair_lengths) and ``condition`` is
@@ -81,8 +81,16 @@ class LatentSampler:
 
         ``solver='dpmpp_2m'``: the second-order multistep update (scheduler.multistep_coefficients, include/ezdit.h ezdit_sampler_set_multistep)
         in place of DDIM's; eta must be 0.  The history of data predictions is allocated here and lives on the sampler, so run() may be
-        called in pieces.  'ddim' calls nothing new."""
+        called in pieces.  'ddim' calls nothing new.
+
+        ``init_latents`` with ``start_steps`` (audio-to-audio): init_latents is fp32 [P or 1, C, L] in VAE space (what the encoder returns; one row is
+        broadcast like gt), start_steps an int or a list of P steps in [0, ddim_steps).  Sample p then starts at step start_steps[p] from
+        sa (init_latents + latent_shift) latent_scale + sb init_noise with (sa, sb) of that step (ezdit_add_noise) and is held until the run reaches it
+        (ezdit_sampler_set_start); run() without n runs the ddim_steps - min(start_steps) steps that are left.  Every sample comes out as the call with
+        it alone, started there, gives it.  All starts 0 calls nothing new: the same bits as without the two arguments."""
         check_solver(solver, eta)
+        if (init_latents is None) != (start_steps is None):
+            raise ValueError('init_latents and start_steps must be given together')
         u = self.unet
         dev = u.device
         P, Cc, L = init_noise.shape
@@ -106,6 +114,17 @@ class LatentSampler:
                 conditioning_scale = max(cn_scales)   # what ezdit_sampler_attach_controlnet sees; the table set behind it holds every sample's value
             if condition is None or condition.dim() != 3 or condition.shape[0] not in (1, P) or condition.shape[2] != 2 * L:
                 raise ValueError(f'condition must be [1 or P={P}, cond_in, 2 L = {2 * L}], got {None if condition is None else tuple(condition.shape)}')
+        starts = None
+        if start_steps is not None:
+            starts = [int(v) for v in start_steps] if isinstance(start_steps, (list, tuple)) else [int(start_steps)] * P
+            if len(starts) != P:
+                raise ValueError(f'{len(starts)} start steps for P={P} samples')
+            if min(starts) < 0 or max(starts) >= ddim_steps:
+                raise ValueError(f'start_steps {starts} outside [0, ddim_steps = {ddim_steps})')
+            if init_latents.dim() != 3 or init_latents.shape[0] not in (1, P) or tuple(init_latents.shape[1:]) != (Cc, L):
+                raise ValueError(f'init_latents must be [1 or P={P}, {Cc}, {L}], got {tuple(init_latents.shape)}')
+            if max(starts) == 0:
+                starts = None   # every sample from pure noise: the plain call
         self.scheduler.set_timesteps(ddim_steps)
         ts = [int(t) for t in self.scheduler.timesteps]
         coefs = self.scheduler.ddim_coefficients(eta)
@@ -160,6 +179,18 @@ class LatentSampler:
         self.n_steps = ddim_steps
         self.P = P
         self.x0_hist = None
+        self.first_step = 0
+        if starts is not None:
+            with torch.cuda.stream(self.stream):
+                st = C.c_void_p(self.stream.cuda_stream)
+                # (sa, sb) do not depend on eta: the call's rows serve every sample
+                self._start_params = torch.tensor([[coefs[k][0], coefs[k][1]] for k in starts], dtype=torch.float32).to(dev)
+                self._start_clean = init_latents.to(dev, torch.float32).expand(P, Cc, L).contiguous()
+                self._start_lens = None if lengths is None else torch.tensor(lengths, dtype=torch.int32).to(dev)
+                _lib.check(u.lib.ezdit_add_noise(_ptr(self._start_clean), _ptr(self.latents), _ptr(self._start_params), float(latent_scale),
+                                                 float(latent_shift), _ptr(self._start_lens), L, P, Cc * L, st))
+                _lib.check(u.lib.ezdit_sampler_set_start(u._h, (C.c_int32 * P)(*starts), P, st))
+            self.first_step = min(starts)
         if table is not None:
             self.set_sample_params(*table)
         if cn_scales is not None:
@@ -204,7 +235,7 @@ class LatentSampler:
             _lib.check(u.lib.ezdit_sampler_set_cn_scales(u._h, (C.c_float * self.P)(*vals), self.P, st))
 
     def run(self, n=None, use_graph=True):
-        n = self.n_steps if n is None else n
+        n = self.n_steps - self.first_step if n is None else n
         with torch.cuda.stream(self.stream):
             _lib.check(self.unet.lib.ezdit_sampler_run(self.unet._h, n, 1 if use_graph else 0,
                                                        C.c_void_p(self.stream.cuda_stream)))
@@ -272,7 +303,7 @@ def pad_conditions(condition, frames, n_prompts):
     return condition
 
 
-def draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n_prompts=1, first_index=0):
+def draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n_prompts=1, first_index=0, start_steps=None):
     """Init noise + per-step DDIM noise in the order the reference draws them from ONE generator
     (src/inference.py:58-67 then one randn per scheduler.step, diffusers `randn_tensor`).  For several
     prompts each sample gets its own generator seeded seed + index, so results do not depend on how
@@ -283,7 +314,13 @@ def draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n
 
     ``eta`` may be a list with one value per prompt: sample i draws what a call with it alone draws -- nothing per step when eta_i <= 0; its
     slice of the step noise is then zero, and the whole tensor is None when no sample draws.  ``random_seed`` may be a list of seeds: sample
-    i seeds its generator with random_seed[i], as a single-prompt call with that seed does (a scalar seed keeps seed + first_index + i)."""
+    i seeds its generator with random_seed[i], as a single-prompt call with that seed does (a scalar seed keeps seed + first_index + i).
+
+    ``start_steps`` (audio-to-audio, one step per prompt): sample i draws its init noise, then ddim_steps - start_steps[i] step noises when its eta > 0 --
+    the numbers a call with that sample alone draws -- placed at the step indices start_steps[i] .. ddim_steps - 1 of the [K, P, C, L] tensor, which is
+    indexed by absolute step; the slices before are zero and never read."""
+    if start_steps is not None and len(start_steps) != n_prompts:
+        raise ValueError(f'{len(start_steps)} start steps for {n_prompts} prompts')
     lens = _frames_list(audio_frames, n_prompts)
     etas = _per_prompt(eta, n_prompts, 'eta') or [eta] * n_prompts
     etas = [e or 0 for e in etas]
@@ -302,7 +339,7 @@ def draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n
             g.seed()
         init[i:i + 1, :, :li] = torch.randn((1, codec_dim, li), generator=g, device=device)
         if etas[i] > 0:
-            for k in range(ddim_steps):
+            for k in range(int(start_steps[i]) if start_steps is not None else 0, ddim_steps):
                 step[k, i:i + 1, :, :li] = torch.randn((1, codec_dim, li), generator=g, device=device)
     return init, step
 
@@ -311,18 +348,20 @@ def draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n
 def inference_controlnet(autoencoder, unet, controlnet, gt, gt_mask, condition, tokenizer, text_encoder, params,
                          noise_scheduler, text_raw, neg_text=None, audio_frames=500, guidance_scale=3,
                          guidance_rescale=0.0, ddim_steps=50, eta=1, random_seed=2024, conditioning_scale=1.0,
-                         device='cuda', use_graph=True, solver='ddim'):
-    """Same signature and semantics as the reference's ControlNet ``inference`` (src/inference_controlnet.py:27-129); ``solver`` as in ``inference``."""
+                         device='cuda', use_graph=True, init_latents=None, strength=None, solver='ddim'):
+    """Same signature and semantics as the reference's ControlNet ``inference`` (src/inference_controlnet.py:27-129); ``solver``, ``init_latents`` and
+    ``strength`` as in ``inference``."""
     return inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, noise_scheduler, text_raw, neg_text,
                      audio_frames, guidance_scale, guidance_rescale, ddim_steps, eta, random_seed, device, use_graph,
-                     controlnet=controlnet, condition=condition, conditioning_scale=conditioning_scale, solver=solver)
+                     controlnet=controlnet, condition=condition, conditioning_scale=conditioning_scale, solver=solver,
+                     init_latents=init_latents, strength=strength)
 
 
 @torch.no_grad()
 def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, noise_scheduler, text_raw,
               neg_text=None, audio_frames=500, guidance_scale=3, guidance_rescale=0.0, ddim_steps=50, eta=1,
               random_seed=2024, device='cuda', use_graph=True, controlnet=None, condition=None, conditioning_scale=1.0,
-              first_index=None, solver='ddim'):
+              first_index=None, init_latents=None, strength=None, solver='ddim'):
     """Same signature and semantics as the reference's ``inference`` (src/inference.py:26-107).
 
     Extension: ``solver='dpmpp_2m'`` samples with DPM-Solver++(2M) instead of DDIM (deterministic: eta must be 0, the signature's
@@ -342,7 +381,14 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
 
     Extension: all of this with a ControlNet too.  ``condition`` is then [N or 1, cond_in, 2 * max(audio_frames)], padded (what lies behind a
     sample's own 2 * audio_frames[i] frames is ignored), or a list of N tensors [1, cond_in, 2 * audio_frames[i]], which is padded here;
-    ``conditioning_scale`` may be a list with one value per prompt."""
+    ``conditioning_scale`` may be a list with one value per prompt.
+
+    Extension (audio-to-audio): ``init_latents`` [N or 1, C, max(audio_frames)] in VAE space (the encoder's output, padded when ``audio_frames`` is a
+    list) with ``strength`` in (0, 1], one value or one per prompt: prompt i starts at step ``noise_scheduler.start_step(strength_i)`` from its clip
+    noised to that step instead of from pure noise, and runs the steps that are left.  strength 1 is the plain call, bit for bit.  The latent's
+    scale and shift come from ``params['autoencoder']``.  Audio quality versus strength on the real checkpoints is unmeasured."""
+    if (init_latents is None) != (strength is None):
+        raise ValueError('init_latents and strength must be given together')
     if neg_text is None:
         neg_text = [""]
     if isinstance(text_raw, str):
@@ -350,7 +396,7 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
     if isinstance(ddim_steps, (list, tuple)):
         raise ValueError('ddim_steps must be one value per call: per-prompt step counts are not supported (the prompts of a call share its timesteps)')
     for name, v in (('guidance_scale', guidance_scale), ('guidance_rescale', guidance_rescale), ('eta', eta), ('random_seed', random_seed),
-                    ('conditioning_scale', conditioning_scale)):
+                    ('conditioning_scale', conditioning_scale), ('strength', strength)):
         _per_prompt(v, len(text_raw), name)   # a list has one entry per prompt
     check_solver(solver, eta)
     import torch.distributed as dist
@@ -373,14 +419,16 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
             if frames is None:
                 return inference(autoencoder, unet, sl(gt), sl(gt_mask), tokenizer, text_encoder, params, noise_scheduler,
                                  list(text_raw[s:e]), neg_all[s:e], audio_frames, pp(guidance_scale), pp(guidance_rescale), ddim_steps, pp(eta),
-                                 pp(random_seed), device, use_graph, controlnet, sl(condition), pp(conditioning_scale), first_index=s, solver=solver)
+                                 pp(random_seed), device, use_graph, controlnet, sl(condition), pp(conditioning_scale), first_index=s, solver=solver,
+                                 init_latents=sl(init_latents), strength=pp(strength))
             # mixed lengths: the lengths are sliced with the prompts, per-prompt tensors additionally cut to the shard's own padded length
             lmax = max(frames[s:e])
             cut = lambda t: t if t is None else sl(t)[..., :lmax]   # noqa: E731
             cond = condition if condition is None else sl(condition)[..., :2 * lmax]   # (the control signal has two frames per latent frame)
             wav = inference(autoencoder, unet, cut(gt), cut(gt_mask), tokenizer, text_encoder, params, noise_scheduler,
                             list(text_raw[s:e]), neg_all[s:e], frames[s:e], pp(guidance_scale), pp(guidance_rescale), ddim_steps, pp(eta),
-                            pp(random_seed), device, use_graph, controlnet, cond, pp(conditioning_scale), first_index=s, solver=solver)
+                            pp(random_seed), device, use_graph, controlnet, cond, pp(conditioning_scale), first_index=s, solver=solver,
+                            init_latents=cut(init_latents), strength=pp(strength))
             out = torch.zeros(wav.shape[0], wav.shape[1], t_all, dtype=wav.dtype, device=wav.device)
             out[..., :wav.shape[-1]] = wav
             return out
@@ -400,7 +448,16 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
         raise NotImplementedError('tokenizer=None (unconditional model) is not a shipped configuration')
     codec_dim = params['model']['out_chans']
     unet.eval()
-    init, step_noises = draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n_prompts, first_index)
+    a2a = {}
+    if init_latents is not None:
+        noise_scheduler.set_timesteps(ddim_steps)
+        starts = [noise_scheduler.start_step(v) for v in (_per_prompt(strength, n_prompts, 'strength') or [strength] * n_prompts)]
+        lmax = max(frames) if frames is not None else audio_frames
+        if init_latents.dim() != 3 or init_latents.shape[0] not in (1, n_prompts) or tuple(init_latents.shape[1:]) != (codec_dim, lmax):
+            raise ValueError(f'init_latents must be [1 or {n_prompts}, {codec_dim}, {lmax}], got {tuple(init_latents.shape)}')
+        a2a = dict(init_latents=init_latents, start_steps=starts, latent_scale=params['autoencoder']['scale'], latent_shift=params['autoencoder']['shift'])
+    init, step_noises = draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n_prompts, first_index,
+                                    **(dict(start_steps=a2a['start_steps']) if a2a else {}))
     smp = LatentSampler(unet, noise_scheduler)
     # equal lengths are the unpadded batch (the same bits; include/ezdit.h ezdit_set_lengths): the length table is for ragged batches only
     ragged = frames is not None and len(set(frames)) > 1
@@ -409,7 +466,7 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
         kw['solver'] = solver
     smp.prepare(text.float(), text_mask, uncond_text.float(), uncond_mask, init, step_noises, guidance_scale,
                 guidance_rescale, ddim_steps, eta, gt=gt, gt_mask=gt_mask, controlnet=controlnet, condition=condition,
-                conditioning_scale=conditioning_scale, **kw)
+                conditioning_scale=conditioning_scale, **kw, **a2a)
     smp.run(use_graph=use_graph)
     latents = smp.finish()
     pred = scale_shift_re(latents, params['autoencoder']['scale'], params['autoencoder']['shift'])

@@ -99,6 +99,21 @@ class DDIMScheduler:
         """[(sa, sb, c_x0, c_dir, sigma)] per step, float32, for ezdit_sampler_begin / ezdit_cfg_ddim_step."""
         return [self._coef(t, eta) for t in self.timesteps]
 
+    def start_step(self, strength):
+        """First step of an audio-to-audio run of the current `num_inference_steps` = K at `strength` in (0, 1]: the run covers
+        n_run = min(K, int(K strength + 0.5)) steps -- rounded half up; int(K strength) alone turns 100 x 0.29 into 28 -- and starts at K - n_run.
+        strength 1 starts at 0 (pure noise with the zero-terminal-SNR schedule); a strength that leaves no step to run is refused."""
+        K = self.num_inference_steps
+        if K is None:
+            raise ValueError('set_timesteps first')
+        s = float(strength)
+        if not (0.0 < s <= 1.0):
+            raise ValueError(f'strength={strength!r} outside (0, 1]')
+        n_run = min(K, int(K * s + 0.5))
+        if n_run == 0:
+            raise ValueError(f'strength={strength!r} leaves none of the {K} steps to run')
+        return K - n_run
+
     def multistep_coefficients(self):
         """[c_hist_i] per step of the current timesteps: the one coefficient DPM-Solver++(2M) adds to the eta = 0 rows of `ddim_coefficients`
         (for v-prediction the DDIM update at eta = 0 is first-order DPM-Solver++; ezdit_sampler_set_multistep, ezdit_cfg_multistep_step):

@@ -11,11 +11,11 @@
  *     allocates or frees persistent device memory.  Weights live in one caller-owned blob laid out
  *     by ezdit_param_info(); all activations / tables live in one caller-owned workspace.
  *   - the PER-STEP entry points (ezdit_forward, ezdit_controlnet_forward, ezdit_sampler_run, ezdit_set_step,
- *     ezdit_cfg_ddim_step, ezdit_cfg_ddim_step_per_sample, ezdit_cfg_multistep_step, the ezvae_* ops) are ASYNCHRONOUS on their stream: no device sync, no host read of
+ *     ezdit_cfg_ddim_step, ezdit_cfg_ddim_step_per_sample, ezdit_cfg_multistep_step, ezdit_add_noise, the ezvae_* ops) are ASYNCHRONOUS on their stream: no device sync, no host read of
  *     device data (a sampler step is hipGraph-capturable).  The once-per-call SET-UP entry points synchronise the
  *     stream and must not be called inside a stream capture: ezdit_bind_workspace (diagnostic builds only),
  *     ezdit_prepare_context (reads the context mask back to find single-key batch elements when `xkey1` is on),
- *     ezdit_prepare_timesteps, ezdit_sampler_begin, ezdit_sampler_set_sample_params and ezdit_sampler_set_multistep (host staging
+ *     ezdit_prepare_timesteps, ezdit_sampler_begin, ezdit_sampler_set_sample_params, ezdit_sampler_set_multistep and ezdit_sampler_set_start (host staging
  *     buffers of the timestep / coefficient tables), ezdit_set_lengths, ezdit_sampler_set_pair_lengths and ezdit_sampler_set_cn_scales
  *     (host mirrors of the length / scale tables).
  *   - return 0 = OK, negative = error; ezdit_last_error() gives a thread-local message.  No C++
@@ -281,7 +281,8 @@ int ezdit_cfg_ddim_step_per_sample(const float* dev_pred, float* dev_latents, co
  * per-sample lengths, per-sample guidance and rescale, editing (gt / gt_mask) and an attached ControlNet work unchanged.
  * A set-up entry point like ezdit_set_lengths: it uploads from host memory and waits for `stream`; refused with EZDIT_E_STATE inside a
  * stream capture and before ezdit_sampler_begin.  While it is on, ezdit_set_step(k) with k != 0 is refused with EZDIT_E_STATE (the
- * history would not be step k - 1's; k = 0 is fine, c_hist_0 = 0).
+ * history would not be step k - 1's; k = 0 is fine, c_hist_0 = 0).  With a start table (ezdit_sampler_set_start) the one accepted k is min(start_steps)
+ * instead: that step is first-order for every sample active at it.
  * EZDIT_E_INVALID: n_steps is not the sampler's; a non-finite value; c_hist without dev_x0_hist; a sampler begun with noise, or a
  * per-sample table with any sigma != 0 (the solver is deterministic; ezdit_sampler_set_sample_params in turn refuses sigma != 0 while
  * the solver is on).  A refused call changes nothing. */
@@ -293,6 +294,39 @@ int ezdit_sampler_set_multistep(ezdit_handle* h, const float* c_hist, int n_step
  * not applied).  dev_scratch >= P*256 floats.  Asynchronous, no handle needed. */
 int ezdit_cfg_multistep_step(const float* dev_pred, float* dev_latents, float* dev_x0_hist, const float* dev_params,
                              const int32_t* dev_lens, int L, int P, int n, float* dev_scratch, ezdit_stream stream);
+
+/* ---- audio-to-audio: start the sampler from a noised clip, per sample ------------------------------------------------------------ */
+/* Noise a clean VAE latent into the model's space at each sample's start step, in place of the init noise:
+ *   dev_latents[p][i] = sa_p * ((dev_clean[p][i] + shift) * scale) + sb_p * dev_latents[p][i]
+ * dev_latents fp32 [P][n] holds the init noise on entry; dev_clean fp32 [P][n] is the encoder's output, `(x + shift) * scale` the
+ * reference's `scale_shift` (src/utils/utils.py:20-21) in that order; dev_params fp32 [P][2] ON THE DEVICE holds (sa, sb) =
+ * (sqrt(alpha_bar), sqrt(1 - alpha_bar)) of sample p's start step (the first two slots of its ezdit_ddim_coef row).  dev_lens
+ * (nullable, device, int32 [P]) as in ezdit_cfg_ddim_step_per_sample: frames >= dev_lens[p] of the L (n = C L) are written as exactly
+ * 0 whatever dev_clean and dev_latents hold there, NaN included.
+ *   (sa_p, sb_p) exactly (0, 1)   sample p is not touched and its dev_clean row is not read: start step 0 of a zero-terminal-SNR
+ *                                 schedule, the plain text-to-audio call bit for bit
+ * Asynchronous, no handle needed.  EZDIT_E_INVALID: dev_clean, dev_latents or dev_params NULL; P or n < 1; L < 1 or L not dividing n
+ * (with or without dev_lens). */
+int ezdit_add_noise(const float* dev_clean, float* dev_latents, const float* dev_params, float scale, float shift,
+                    const int32_t* dev_lens, int L, int P, int n, ezdit_stream stream);
+
+/* After ezdit_sampler_begin, sample p's first step is start_steps[p] (HOST array of P values in [0, n_steps)) instead of 0; the device
+ * step counter and the host's count of steps done are set to min(start_steps), so ezdit_sampler_run(n) is bounded by n_steps minus
+ * that.  While the step counter is below start_steps[p] sample p is HELD: the denoiser computes its rows (the batch keeps its shape,
+ * as padded frames are computed) and the last two kernels of the step skip it -- no read of its prediction, noise slice or history,
+ * no write of its latents or history: the latents keep their bits.  From start_steps[p] on it is updated as in a run that begins
+ * there alone; with the multistep solver on, step start_steps[p] is first-order for it (c_hist = 0, the history is written, not read).
+ * NULL or P = 0 clears the table (and, if it was on, puts the step counter back to 0), as ezdit_sampler_begin and ezdit_bind_workspace do.
+ * The table lives at the END of the workspace (ezdit_workspace_bytes grows by 1 KB) and is read at run time: new values keep the
+ * captured step graph, switching it on or off drops it.  Per-sample lengths (plain and pair), the per-sample settings table, the
+ * multistep solver (set in either order with it), gt / gt_mask and an attached ControlNet work unchanged; none of them is touched.
+ * While the table is on, ezdit_set_step(k) is accepted only for k == min(start_steps) -- a rewind to the run's own beginning, also with
+ * the multistep solver on (that step is first-order for every sample active at it); any other k is EZDIT_E_STATE.  With it off
+ * ezdit_set_step keeps its rules.
+ * A set-up entry point like ezdit_set_lengths: it uploads from host memory and waits for `stream`; EZDIT_E_STATE inside a stream
+ * capture and before ezdit_sampler_begin.  EZDIT_E_INVALID: P is not the P of ezdit_sampler_begin; a value outside [0, n_steps).
+ * A refused call changes nothing. */
+int ezdit_sampler_set_start(ezdit_handle* h, const int32_t* start_steps, int P, ezdit_stream stream);
 
 /* ---- Oobleck VAE decoder building blocks (src/modules/stable_vae/models/autoencoders.py:38-61,82-113,149-190) --------
  * Stateless ops on caller-owned device buffers; the layer sequence is host code (ezaudio_amd/vae.py), run once per call.
