@@ -1981,9 +1981,33 @@ int ezdit_test_cross_attention(const void* xu, int ldu, const void* xw, int ldw,
     return hook_launch("k_attn", "attention configuration", [&] { return launch_attention(a, (hipStream_t)stream); });
 }
 
+// what both plain-attention hooks refuse.  Everything that bounds an address comes before the first HIP call and before the handle is looked at (k_attn itself checks
+// nothing: it reads Lkp / 32 sub-tiles of whole 64-row query tiles); a fine description with no handle is refused last.  With a key mask the hook then waits for `stream`
+// and reads the mask back, as the varlen hook does for its lengths: a batch element without a valid key has no softmax (0 / 0), which is the caller's mistake and no
+// property of the kernel
+static int attn_hook_refusals(const ezdit_handle* h, const void* q, const void* k, const void* v, const uint8_t* kmask, const void* out, int B, int Lq, int Lk,
+                              int Lqp, int Lkp, hipStream_t stream) {
+    if (!q || !k || !v || !out) return fail(EZDIT_E_INVALID, "null q, k, v or out");
+    if (B <= 0 || Lq <= 0 || Lk <= 0) return fail(EZDIT_E_INVALID, "bad shape B=%d Lq=%d Lk=%d", B, Lq, Lk);
+    if (Lqp < Lq || Lkp < Lk) return fail(EZDIT_E_INVALID, "padded lengths Lqp=%d Lkp=%d below Lq=%d Lk=%d", Lqp, Lkp, Lq, Lk);
+    if (Lqp % 64 || Lkp % 64) return fail(EZDIT_E_INVALID, "padded lengths Lqp=%d Lkp=%d must be multiples of 64", Lqp, Lkp);
+    if (!h) return fail(EZDIT_E_INVALID, "null handle");
+    if (kmask) {
+        std::vector<uint8_t> km((size_t)B * Lk);
+        HIPCHK(hipStreamSynchronize(stream));
+        HIPCHK(hipMemcpy(km.data(), kmask, km.size(), hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; ++b) {
+            bool any = false;
+            for (int j = 0; j < Lk && !any; ++j) any = km[(size_t)b * Lk + j] != 0;
+            if (!any) return fail(EZDIT_E_INVALID, "kmask leaves batch element %d without a valid key", b);
+        }
+    }
+    return 0;
+}
+
 int ezdit_test_attention(ezdit_handle* h, const void* q, const void* k, const void* v, const uint8_t* kmask, void* out, int B,
                          int Lq, int Lk, int Lqp, int Lkp, ezdit_stream stream) {
-    if (!h) return fail(EZDIT_E_INVALID, "null handle");
+    if (int rc = attn_hook_refusals(h, q, k, v, kmask, out, B, Lq, Lk, Lqp, Lkp, (hipStream_t)stream)) return rc;
     AttnArgs a;
     memset(&a, 0, sizeof a);
     a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.kmask = kmask;
@@ -1996,10 +2020,9 @@ int ezdit_test_attention(ezdit_handle* h, const void* q, const void* k, const vo
 
 int ezdit_test_attention_varlen(ezdit_handle* h, const void* q, const void* k, const void* v, const uint8_t* kmask, void* out, int B,
                                 int Lq, int Lk, int Lqp, int Lkp, const int32_t* dev_klen, ezdit_stream stream) {
-    if (!h) return fail(EZDIT_E_INVALID, "null handle");
-    if (B <= 0 || Lq <= 0 || Lk <= 0 || Lqp < Lq || Lkp < Lk) return fail(EZDIT_E_INVALID, "bad shape");
+    if (dev_klen && Lq != Lk) return fail(EZDIT_E_INVALID, "per-batch-element lengths are a self-attention form: Lq %d != Lk %d", Lq, Lk);
+    if (int rc = attn_hook_refusals(h, q, k, v, kmask, out, B, Lq, Lk, Lqp, Lkp, (hipStream_t)stream)) return rc;
     if (dev_klen) {   // a test hook may wait: the lengths bound what the kernel reads and which rows it zeroes
-        if (Lq != Lk) return fail(EZDIT_E_INVALID, "per-batch-element lengths are a self-attention form: Lq %d != Lk %d", Lq, Lk);
         std::vector<int> kl((size_t)B);
         HIPCHK(hipStreamSynchronize((hipStream_t)stream));
         HIPCHK(hipMemcpy(kl.data(), dev_klen, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));

@@ -428,7 +428,10 @@ int ezdit_test_cross_attention(const void* dev_xu, int ldu, const void* dev_xw, 
  * start, K-loop end, kernel end, then epilogue internals) into dev_buf ([capacity_workgroups][8] uint64; NULL switches it off).  A launch
  * whose grid exceeds capacity_workgroups writes no stamps.  Un-register (NULL) before freeing the buffer. */
 int ezdit_debug_gemm_timestamps(void* dev_buf, long capacity_workgroups);
-/* q, k bf16 [B][H][L*p][DQK], v bf16 [B][H][Lkp][DV] (DQK / DV = 64 / 64 or 80 / 96 for head_dim 64 / 72; padding zero), out bf16 [B*Lq][ldD] */
+/* q, k bf16 [B][H][L*p][DQK], v bf16 [B][H][Lkp][DV] (DQK / DV = 64 / 64 or 80 / 96 for head_dim 64 / 72; q and k channels [dh, DQK) zero; rows beyond Lq / Lk and v channels
+ * [dh, DV) may hold anything finite), dev_kmask uint8 [B][Lk] or NULL, out bf16 [B*Lq][ldD] (columns [D, ldD) are not written).  Refused with EZDIT_E_INVALID before the
+ * first HIP call: a null q, k, v or out, B, Lq or Lk <= 0, Lqp < Lq, Lkp < Lk, Lqp or Lkp no multiple of 64 (the kernel reads whole 64-row query tiles and 32-key sub-tiles
+ * unchecked), then a null handle.  With dev_kmask the hook waits for `stream`, reads the mask back and refuses a batch element without a valid key (its softmax is 0 / 0). */
 int ezdit_test_attention(ezdit_handle* h, const void* dev_q, const void* dev_k, const void* dev_v,
                          const uint8_t* dev_kmask, void* dev_out, int B, int Lq, int Lk, int Lqp, int Lkp,
                          ezdit_stream stream);
