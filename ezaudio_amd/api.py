@@ -13,7 +13,7 @@ import torch
 
 from .config import configs, controlnet_configs, load_yaml_with_includes
 from .denoiser import MaskDiT
-from .sampler import check_solver, inference, inference_controlnet
+from .sampler import canvas_windows, check_solver, inference, inference_controlnet
 from .scheduler import DDIMScheduler
 
 MAX_SEED = np.iinfo(np.int32).max
@@ -127,6 +127,41 @@ class EzAudio:
             return self.params['autoencoder']['sr'], [pred[i, 0, :n * ratio] for i, n in enumerate(length)]
         pred = pred.squeeze(0).squeeze(0) if isinstance(text, str) or len(text) == 1 else pred.squeeze(1)
         return self.params['autoencoder']['sr'], pred
+
+    def generate_long_audio(self, text, length, window=10, overlap=2.5, guidance_scale=5, guidance_rescale=0.75, ddim_steps=100, eta=1,
+                            random_seed=None, randomize_seed=False, solver='ddim'):
+        """A clip of `length` seconds, longer than the `window` seconds the model was trained on: the latent canvas is covered by overlapping windows of
+        `window` seconds that share at least `overlap` seconds with their neighbours (sampler.canvas_windows chooses the fewest such windows, spread evenly),
+        all windows are denoised together as the prompts of ONE batched sampler call, the shared frames are cross-faded inside every step, and the canvas is
+        decoded in one call.  Returns (sr, waveform [T]) like generate_audio.
+        `text` is one prompt for the whole clip, or a list with one prompt per window -- a scene that changes over time.  The settings are scalars.
+        `length <= window` is generate_audio(text, length, ...): the same call, the same result.
+        Audio quality on the real checkpoints (seam audibility, the choice of overlap, the comparison with generate_audio(length=...) as one long row) is
+        unmeasured."""
+        latent_sr = self.params['autoencoder']['latent_sr']
+        if isinstance(length, (list, tuple)):
+            raise ValueError('generate_long_audio makes one clip: length is one duration in seconds')
+        offsets, frames = canvas_windows(int(round(length * latent_sr)), int(round(window * latent_sr)), int(round(overlap * latent_sr)))
+        n_win = len(offsets)
+        if not isinstance(text, str) and len(text) != n_win:
+            raise ValueError(f'{len(text)} prompts for {n_win} windows ({length} s in windows of {window} s that share {overlap} s): one prompt, or one per window')
+        if n_win == 1:
+            return self.generate_audio(text if isinstance(text, str) else text[0], length, guidance_scale, guidance_rescale, ddim_steps, eta, random_seed,
+                                       randomize_seed, solver=solver)
+        check_solver(solver, eta)
+        for name, v in (('guidance_scale', guidance_scale), ('guidance_rescale', guidance_rescale), ('eta', eta), ('random_seed', random_seed),
+                        ('ddim_steps', ddim_steps)):
+            if isinstance(v, (list, tuple)):
+                raise ValueError(f'generate_long_audio takes one {name} for the whole clip')
+        prompts = [text] * n_win if isinstance(text, str) else list(text)
+        if all(t == '' for t in prompts):
+            guidance_scale = None
+            print('empty input')
+        if randomize_seed:
+            random_seed = random.randint(0, MAX_SEED)
+        pred = inference(self.autoencoder, self.unet, None, None, self.tokenizer, self.text_encoder, self.params, self.noise_scheduler, prompts, None,
+                         frames, guidance_scale, guidance_rescale, ddim_steps, eta, random_seed, self.device, canvas_offsets=offsets, solver=solver)
+        return self.params['autoencoder']['sr'], pred.cpu().numpy().squeeze(0).squeeze(0)
 
     def _load_edit_clip(self, gt_file):
         """The recording of an edit, peak-normalised (api/ezaudio.py:143-144): a path (librosa) or a 1-D numpy waveform at the model's sample rate."""

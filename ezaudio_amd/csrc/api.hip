@@ -61,6 +61,7 @@ struct WsPtrs {  // workspace regions used on the per-step path, resolved once a
     int* lens;   // [B] per-batch-element valid frames (ezdit_set_lengths); read by the kernels only while ezdit_handle::lens_on
     float *spg, *spc;   // per-sample sampler settings (ezdit_sampler_set_sample_params): [P][2] (guidance_scale, guidance_rescale) and [n_steps][P][8] DDIM coefficients; read only while sp_on
     int* start;  // [P] first step of each sample (ezdit_sampler_set_start); read by k_cfg_stats / k_cfg_apply only while ezdit_handle::start_on
+    int* canvas; // [P] first canvas frame of each window (ezdit_sampler_set_canvas); read by k_canvas_blend only while ezdit_handle::canvas_on
     float* cns;  // [B] per-batch-element conditioning_scale of the attached ControlNet (ezdit_sampler_set_cn_scales); read by the row kernel only while ezdit_handle::cns_on
     float* zd;   // [nblk][B][D] constant cross-attention-out vectors of the single-key batch elements (opt_xkey1)
 };
@@ -120,6 +121,12 @@ struct ezdit_handle {
     bool start_on = false;
     int start_min = 0;
     std::vector<int> start_host;   // host mirror (the source of the asynchronous upload)
+    // long-form canvas (ezdit_sampler_set_canvas): the P windows of the call overlap on a canvas of canvas_T frames and k_canvas_blend, one more launch behind the
+    // update, averages the shared frames.  The kernel reads the device table at run time: new offsets keep the graph, switching it on or off (or another T / ramp,
+    // which are kernel arguments) drops it.  Off: the step issues the launches it has always issued
+    bool canvas_on = false;
+    int canvas_T = 0, canvas_ramp = 1;
+    std::vector<int> canvas_host;   // host mirror (the source of the asynchronous upload)
 
     int launches = 0;
     bool is_cn = false;          // ControlNet variant (cfg.controlnet)
@@ -496,6 +503,7 @@ size_t carve(const ezdit_handle* h, int B, int L, int Lc, int n_slots, std::map<
         add("spc", (size_t)ns * ezdit_handle::sp_cap(B) * 8 * 4);   // n_slots * (B / 2 + 1) * 32 bytes + 2 KB more workspace than without them
         add("cns", 256 * sizeof(float));   // per-batch-element conditioning_scale (B <= 240), behind `lens` and the sample tables for the same reason: no existing buffer moves
         add("start", 256 * sizeof(int));   // per-sample first step (ezdit_sampler_set_start; P <= B <= 240), at the very end for the same reason: 1 KB
+        add("canvas", 256 * sizeof(int));  // per-window first canvas frame (ezdit_sampler_set_canvas; P <= B <= 240), behind `start` for the same reason: 1 KB
     }
     return off;
 }
@@ -676,7 +684,7 @@ void resolve_workspace(ezdit_handle* h) {
     p.ao = h->buf<bf16_t>("ao"); p.act = h->buf<bf16_t>("act"); p.part = h->buf<float>("part"); p.y = h->buf<float>("y");
     p.pred = h->buf<float>("pred"); p.kmask = h->buf<uint8_t>("kmask"); p.kc = h->buf<bf16_t>("kc"); p.vc = h->buf<bf16_t>("vc");
     p.mod = h->buf<float>("mod"); p.modf = h->buf<float>("modf");
-    p.zd = h->buf<float>("zd"); p.lens = h->buf<int>("lens"); p.spg = h->buf<float>("spg"); p.spc = h->buf<float>("spc"); p.cns = h->buf<float>("cns"); p.start = h->buf<int>("start");
+    p.zd = h->buf<float>("zd"); p.lens = h->buf<int>("lens"); p.spg = h->buf<float>("spg"); p.spc = h->buf<float>("spc"); p.cns = h->buf<float>("cns"); p.start = h->buf<int>("start"); p.canvas = h->buf<int>("canvas");
     p.zstat = h->buf<float2>("zstat"); p.zt_qkv = h->buf<float>("zt_qkv"); p.zt_geglu = h->buf<float>("zt_geglu"); p.zt_q2 = h->buf<float>("zt_q2");
     p.zstat_skip = h->buf<float2>("zstat_skip"); p.zt_skip = h->buf<float>("zt_skip"); p.ucat_z = h->buf<bf16_t>("ucat_z");
     if (h->is_cn) { p.cembed = h->buf<float>("cembed"); p.cnres = h->buf<float>("cnres"); p.skipbf = h->buf<bf16_t>("skipbf"); }
@@ -824,6 +832,7 @@ int ezdit_bind_workspace(ezdit_handle* h, void* ws, size_t bytes, int B, int L, 
     h->cns_on = false;
     h->ms_on = false; h->ms_hist = nullptr; h->coef_host.clear();
     h->start_on = false; h->start_min = 0;
+    h->canvas_on = false;
     drop_graph(h);
     for (ezdit_handle* u : h->cn_users) drop_graph(u);   // a graph captured with this ControlNet attached points at its old buffers
     // zero everything once: all padding rows / columns / keys stay zero for the lifetime of the binding
@@ -1055,6 +1064,7 @@ int ezdit_set_lengths(ezdit_handle* h, const int32_t* lengths, int n, ezdit_stre
     // one handle's call can set only one of the two tables of an attached pair, and they must agree: the pair has its own call
     if (h->is_cn) return fail(EZDIT_E_UNSUPPORTED, "per-sample lengths on a ControlNet handle (its condition embed is computed from the table: ezdit_sampler_set_pair_lengths on the backbone it is attached to)");
     if (h->cn) return fail(EZDIT_E_UNSUPPORTED, "per-sample lengths with a ControlNet attached: ezdit_sampler_set_pair_lengths sets both tables");
+    if (h->canvas_on) return fail(EZDIT_E_UNSUPPORTED, "per-sample lengths while the canvas is on (ezdit_sampler_set_canvas): its windows have one length");
     if (n < 0 || n > h->B || h->B % n) return fail(EZDIT_E_INVALID, "%d lengths do not divide B = %d", n, h->B);
     for (int i = 0; i < n; ++i)
         if (lengths[i] < 1 || lengths[i] > h->L) return fail(EZDIT_E_INVALID, "lengths[%d] = %d outside [1, L = %d]", i, (int)lengths[i], h->L);
@@ -1512,6 +1522,7 @@ int ezdit_controlnet_residuals(ezdit_handle* h, const float** out, int n) {
 int ezdit_sampler_attach_controlnet(ezdit_handle* h, ezdit_handle* cn, float conditioning_scale) {
     if (!h || h->is_cn) return fail(EZDIT_E_INVALID, "first argument must be a backbone handle");
     if (cn && !cn->is_cn) return fail(EZDIT_E_INVALID, "second argument must be a ControlNet handle");
+    if (cn && h->canvas_on) return fail(EZDIT_E_UNSUPPORTED, "a ControlNet while the canvas is on (ezdit_sampler_set_canvas)");
     if (h->cn && h->cn != cn) {
         auto& v = h->cn->cn_users;
         for (size_t i = 0; i < v.size(); ++i) if (v[i] == h) { v.erase(v.begin() + i); break; }
@@ -1567,6 +1578,7 @@ int ezdit_sampler_begin(ezdit_handle* h, float* latents, int P, const float* noi
     h->sp_on = false;   // per-sample settings belong to one sampler call (the graph is dropped below anyway)
     h->ms_on = false; h->ms_hist = nullptr;   // ... and so does the multistep solver
     h->start_on = false; h->start_min = 0;    // ... and the start table
+    h->canvas_on = false;                     // ... and the canvas table
     h->s_gt = gt; h->s_gt_mask = gt_mask;
     if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
     if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
@@ -1620,6 +1632,12 @@ static int sampler_step(ezdit_handle* h, hipStream_t st) {
     a.start = h->start_on ? h->p.start : nullptr;
     launch_cfg_ddim(a, h->p.cfgpart, st);   // its last kernel also advances the device step counter
     h->launches += (h->sp_on || (h->gscale > 0.f && h->grescale > 0.f)) ? 2 : 1;
+    if (h->canvas_on) {   // long-form canvas: the windows' shared frames are averaged on the updated latents (x0_hist stays per window)
+        CanvasBlendArgs cb;
+        cb.latents = h->latents; cb.off = h->p.canvas; cb.P = h->P; cb.C = h->C; cb.L = h->L; cb.T = h->canvas_T; cb.ramp = h->canvas_ramp;
+        launch_canvas_blend(cb, st);
+        h->launches += 1;
+    }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of k_cfg_* failed: %s", hipGetErrorString(e));
     return EZDIT_OK;
@@ -1741,6 +1759,7 @@ int ezdit_sampler_set_start(ezdit_handle* h, const int32_t* start_steps, int P, 
         h->start_on = false; h->start_min = 0;
         return EZDIT_OK;
     }
+    if (h->canvas_on) return fail(EZDIT_E_UNSUPPORTED, "a start table while the canvas is on (ezdit_sampler_set_canvas): its windows run every step together");
     if (P != h->P) return fail(EZDIT_E_INVALID, "P = %d, the sampler was begun with P = %d", P, h->P);
     int lo = h->n_steps;
     for (int p = 0; p < P; ++p) {
@@ -1755,6 +1774,53 @@ int ezdit_sampler_set_start(ezdit_handle* h, const int32_t* start_steps, int P, 
     h->steps_done = lo;
     if (!h->start_on) drop_graph(h);
     h->start_on = true; h->start_min = lo;
+    return EZDIT_OK;
+}
+
+int ezdit_canvas_blend(float* latents, const int32_t* offsets, int P, int C, int L, int T, int ramp, ezdit_stream stream) {
+    if (!latents || !offsets) return fail(EZDIT_E_INVALID, "null argument");
+    if (P < 1 || C < 1 || L < 1 || C > 65535) return fail(EZDIT_E_INVALID, "P = %d, C = %d, L = %d", P, C, L);
+    if (ramp < 1) return fail(EZDIT_E_INVALID, "ramp = %d: at least 1 (the plain mean)", ramp);
+    // the table is on the device and this call does not wait for it: T is checked against what any valid table gives
+    if (T < L || (long)T > (long)P * L) return fail(EZDIT_E_INVALID, "T = %d: %d windows of %d frames cover between %d and %ld frames", T, P, L, L, (long)P * L);
+    CanvasBlendArgs a;
+    a.latents = latents; a.off = offsets; a.P = P; a.C = C; a.L = L; a.T = T; a.ramp = ramp;
+    return hook_launch("k_canvas_blend", "", [&] { launch_canvas_blend(a, (hipStream_t)stream); return 0; });
+}
+
+int ezdit_sampler_set_canvas(ezdit_handle* h, const int32_t* offsets, int P, int T, int ramp, ezdit_stream stream) {
+    if (!h) return fail(EZDIT_E_INVALID, "null handle");
+    if (!h->ws || !h->latents) return fail(EZDIT_E_STATE, "ezdit_sampler_begin first");
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    if (cs != hipStreamCaptureStatusNone) return fail(EZDIT_E_STATE, "ezdit_sampler_set_canvas inside a stream capture (it uploads from host memory and waits)");
+    if ((int)h->coef_host.size() != h->n_steps * 8) return fail(EZDIT_E_STATE, "ezdit_sampler_begin first");
+    if (!offsets || P == 0) {   // off: independent windows again
+        if (h->canvas_on) drop_graph(h);
+        h->canvas_on = false;
+        return EZDIT_OK;
+    }
+    const int L = h->L;
+    if (P != h->P) return fail(EZDIT_E_INVALID, "P = %d, the sampler was begun with P = %d", P, h->P);
+    if (ramp < 1) return fail(EZDIT_E_INVALID, "ramp = %d: at least 1 (the plain mean)", ramp);
+    if (offsets[0] != 0) return fail(EZDIT_E_INVALID, "offsets[0] = %d: the first window starts the canvas", (int)offsets[0]);
+    for (int i = 0; i + 1 < P; ++i) {
+        if (offsets[i + 1] <= offsets[i]) return fail(EZDIT_E_INVALID, "offsets[%d] = %d is not above offsets[%d] = %d", i + 1, (int)offsets[i + 1], i, (int)offsets[i]);
+        if ((long)offsets[i + 1] > (long)offsets[i] + L)
+            return fail(EZDIT_E_INVALID, "offsets[%d] = %d leaves a gap behind window %d, which ends at frame %ld", i + 1, (int)offsets[i + 1], i, (long)offsets[i] + L);
+    }
+    if ((long)offsets[P - 1] + L != (long)T) return fail(EZDIT_E_INVALID, "T = %d, the last window ends at frame %ld", T, (long)offsets[P - 1] + L);
+    if (h->lens_on) return fail(EZDIT_E_UNSUPPORTED, "a canvas with per-sample lengths (ezdit_set_lengths): its windows have one length");
+    if (h->start_on) return fail(EZDIT_E_UNSUPPORTED, "a canvas with a start table (ezdit_sampler_set_start)");
+    if (h->s_gt) return fail(EZDIT_E_UNSUPPORTED, "a canvas with gt / gt_mask: long edits are not implemented");
+    if (h->cn) return fail(EZDIT_E_UNSUPPORTED, "a canvas with a ControlNet attached");
+    HIPCHK(hipStreamSynchronize(st));   // an earlier upload may still be reading the host mirror
+    h->canvas_host.assign(offsets, offsets + P);
+    HIPCHK(hipMemcpyAsync(h->p.canvas, h->canvas_host.data(), (size_t)P * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (!h->canvas_on || T != h->canvas_T || ramp != h->canvas_ramp) drop_graph(h);   // (T and the ramp are kernel arguments)
+    h->canvas_on = true; h->canvas_T = T; h->canvas_ramp = ramp;
     return EZDIT_OK;
 }
 

@@ -395,6 +395,13 @@ struct AddNoiseArgs {  // latents[p][i] = sa_p * ((clean[p][i] + shift) * scale)
     int P, n;
 };
 void launch_add_noise(const AddNoiseArgs& a, hipStream_t st);
+struct CanvasBlendArgs {  // long-form canvas: the P windows of one call are overlapping views of a canvas of T frames; the frames they share are averaged in place
+    float* latents;       // [P][C][L] in/out: window p's local frame r is canvas frame off[p] + r
+    const int* off;       // [P] on the device: first canvas frame of each window, ascending, off[0] = 0, off[p + 1] <= off[p] + L, off[P - 1] + L = T
+    int P, C, L, T;
+    int ramp;             // weight of local frame r: min(r + 1, L - r, ramp) -- 1: the plain mean; the overlap: a linear cross-fade
+};
+void launch_canvas_blend(const CanvasBlendArgs& a, hipStream_t st);
 struct Conv1dArgs {  // out[b][co][lo] = act(bias[co] + sum_{ci,k} w[co][ci][k] * x[b][ci][lo*stride + k - pad]); fp32
     const float* x; const float* w; const float* b; float* out;
     int B, Cin, Cout, Lin, Lout, ksize, stride, pad, act;  // act 1 = SiLU

@@ -635,6 +635,36 @@ __global__ __launch_bounds__(256) void k_add_noise(AddNoiseArgs a) {
     for (int i = blk * 256 + threadIdx.x; i < n; i += ADD_NB * 256) lat[i] = add_noise_1(a, cl[i], lat[i], sa, sb, i, len);
 }
 
+// Long-form canvas: canvas frame j is held by every window p with off[p] <= j < off[p] + L.  One thread owns ALL aliases of one (c, j): it reads them in
+// ascending p, forms v = sum(w_p x_p) / sum(w_p) in fp32 (w = min(r + 1, L - r, ramp) at the local frame r) and stores the same v into each -- in place without
+// a race, deterministic, the aliases bit-identical afterwards.  An element held by one window is neither read nor written.  The thread index runs along j, so
+// the accesses of a wave are consecutive floats of one window row; window offsets are arbitrary, hence scalar (4-byte) accesses.  The offsets ascend, so the
+// holders of j are one contiguous range of windows.
+__global__ __launch_bounds__(256) void k_canvas_blend(CanvasBlendArgs a) {
+    const int j = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
+    if (j >= a.T) return;
+    int lo = a.P, hi = -1;
+    for (int p = 0; p < a.P; ++p) {
+        const int r = j - a.off[p];
+        if (r >= 0 && r < a.L) { if (p < lo) lo = p; hi = p; }
+    }
+    if (hi <= lo) return;   // one holder, or none
+    // (the range test is repeated below: whatever a caller's device table holds, every access stays inside window p's row)
+    float num = 0.f, den = 0.f;
+    for (int p = lo; p <= hi; ++p) {
+        const int r = j - a.off[p];
+        if (r < 0 || r >= a.L) continue;
+        const float w = (float)min(min(r + 1, a.L - r), a.ramp);
+        num += w * a.latents[((long)p * a.C + c) * a.L + r];
+        den += w;
+    }
+    const float v = num / den;
+    for (int p = lo; p <= hi; ++p) {
+        const int r = j - a.off[p];
+        if (r >= 0 && r < a.L) a.latents[((long)p * a.C + c) * a.L + r] = v;
+    }
+}
+
 // small direct Conv1d in fp32 for the ControlNet condition embed (controlnet.py:15-39,65-84): 4 tiny layers, once per call
 __global__ __launch_bounds__(256) void k_conv1d(Conv1dArgs a) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -744,6 +774,10 @@ void launch_cfg_ddim(const CfgDdimArgs& a, float* partial, hipStream_t st) {
 
 void launch_add_noise(const AddNoiseArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(k_add_noise, dim3(ADD_NB, a.P), dim3(256), 0, st, a);
+}
+
+void launch_canvas_blend(const CanvasBlendArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(k_canvas_blend, dim3((a.T + 255) / 256, a.C), dim3(256), 0, st, a);
 }
 
 // ---- LayerNorm algebra tables (common.h, GemmArgs.z*): G' = g W^T and C' = c W^T (+ bias) for every modulation slot.  The gain / shift

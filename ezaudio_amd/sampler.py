@@ -65,7 +65,8 @@ class LatentSampler:
 
     def prepare(self, text, text_mask, uncond_text, uncond_mask, init_noise, step_noises, guidance_scale,
                 guidance_rescale, ddim_steps, eta, gt=None, gt_mask=None, controlnet=None, condition=None,
-                conditioning_scale=1.0, lengths=None, init_latents=None, start_steps=None, latent_scale=1.0, latent_shift=0.0, solver='ddim'):
+                conditioning_scale=1.0, lengths=None, init_latents=None, start_steps=None, latent_scale=1.0, latent_shift=0.0, canvas=None,
+                solver='ddim'):
         """``lengths`` (list of P ints): init_noise / step_noises / gt / gt_mask are padded to L = max(lengths) frames and sample p is valid on
         [0, lengths[p]) -- its final latent is what a call with that sample alone at its own length gives, zero beyond (include/ezdit.h
         ezdit_set_lengths).  With a ControlNet the table goes to the attached pair (ezdit_sampler_set_pair_lengths) and ``condition`` is
@@ -87,7 +88,13 @@ class LatentSampler:
         broadcast like gt), start_steps an int or a list of P steps in [0, ddim_steps).  Sample p then starts at step start_steps[p] from
         sa (init_latents + latent_shift) latent_scale + sb init_noise with (sa, sb) of that step (ezdit_add_noise) and is held until the run reaches it
         (ezdit_sampler_set_start); run() without n runs the ddim_steps - min(start_steps) steps that are left.  Every sample comes out as the call with
-        it alone, started there, gives it.  All starts 0 calls nothing new: the same bits as without the two arguments."""
+        it alone, started there, gives it.  All starts 0 calls nothing new: the same bits as without the two arguments.
+
+        ``canvas=(offsets, T, ramp)`` (long-form generation): the P samples are windows of one canvas of T latent frames, window p holding the frames
+        [offsets[p], offsets[p] + L) (canvas_windows() chooses such offsets; draw_noises(canvas_offsets=) slices one canvas noise for them).  Every step then
+        ends by averaging the frames that windows share, with the weights min(r + 1, L - r, ramp) of the local frame r (ezdit_sampler_set_canvas), and
+        canvas_latents() reads the [1, C, T] canvas off the windows after finish().  Not with lengths, gt / gt_mask, a ControlNet or init_latents.  A canvas of
+        one window, or one whose windows do not overlap, calls nothing new: the same bits as without the argument."""
         check_solver(solver, eta)
         if (init_latents is None) != (start_steps is None):
             raise ValueError('init_latents and start_steps must be given together')
@@ -125,6 +132,15 @@ class LatentSampler:
                 raise ValueError(f'init_latents must be [1 or P={P}, {Cc}, {L}], got {tuple(init_latents.shape)}')
             if max(starts) == 0:
                 starts = None   # every sample from pure noise: the plain call
+        self.canvas = None
+        if canvas is not None:
+            offs, T, ramp = [int(v) for v in canvas[0]], int(canvas[1]), int(canvas[2])
+            check_canvas(offs, L, T, ramp)
+            if len(offs) != P:
+                raise ValueError(f'{len(offs)} canvas offsets for P={P} windows')
+            if lengths is not None or gt is not None or controlnet is not None or init_latents is not None:
+                raise ValueError('a canvas does not combine with lengths, gt / gt_mask, a ControlNet or init_latents')
+            self.canvas = (offs, T, ramp)
         self.scheduler.set_timesteps(ddim_steps)
         ts = [int(t) for t in self.scheduler.timesteps]
         coefs = self.scheduler.ddim_coefficients(eta)
@@ -151,6 +167,11 @@ class LatentSampler:
         cur = torch.cuda.current_stream(dev)
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
+            if getattr(u, '_canvas_on', False):   # the handle outlives the call: an earlier call's canvas goes before this call's tables are set
+                rc = u.lib.ezdit_sampler_set_canvas(u._h, None, 0, 0, 1, C.c_void_p(self.stream.cuda_stream))
+                if rc != -3:   # (EZDIT_E_STATE: the workspace was bound again since, which cleared the table)
+                    _lib.check(rc)
+                u._canvas_on = False
             u.bind(B, L, ctx.shape[1], ddim_steps)
             u.prepare_context(ctx, msk)
             u.prepare_timesteps(ts, per_row=False)
@@ -191,6 +212,8 @@ class LatentSampler:
                                                  float(latent_shift), _ptr(self._start_lens), L, P, Cc * L, st))
                 _lib.check(u.lib.ezdit_sampler_set_start(u._h, (C.c_int32 * P)(*starts), P, st))
             self.first_step = min(starts)
+        if self.canvas is not None and any(b < a + L for a, b in zip(self.canvas[0], self.canvas[0][1:])):   # windows that share frames
+            self.set_canvas(*self.canvas)
         if table is not None:
             self.set_sample_params(*table)
         if cn_scales is not None:
@@ -219,6 +242,33 @@ class LatentSampler:
             gs, gr = (C.c_float * P)(*vals[0]), (C.c_float * P)(*vals[1])
             arr = (_lib.EzditDdimCoef * (n * P))(*[_lib.EzditDdimCoef(*rows[p][i]) for i in range(n) for p in range(P)])
             _lib.check(u.lib.ezdit_sampler_set_sample_params(u._h, gs, gr, arr, P, st))
+
+    def set_canvas(self, offsets=None, T=0, ramp=1):
+        """The canvas table of the call prepare() began: P window offsets, the canvas length and the ramp, or no argument to switch the blend off (independent
+        windows).  The captured step reads the offsets at run time: new offsets of the same T and ramp need no re-capture."""
+        u = self.unet
+        st = C.c_void_p(self.stream.cuda_stream)
+        with torch.cuda.stream(self.stream):
+            if offsets is None:
+                _lib.check(u.lib.ezdit_sampler_set_canvas(u._h, None, 0, 0, 1, st))
+                u._canvas_on = False
+                return
+            offs = [int(v) for v in offsets]
+            _lib.check(u.lib.ezdit_sampler_set_canvas(u._h, (C.c_int32 * len(offs))(*offs), len(offs), int(T), int(ramp), st))
+            u._canvas_on = True
+            self.canvas = (offs, int(T), int(ramp))
+
+    def canvas_latents(self):
+        """The [1, C, T] canvas of a call prepared with ``canvas=``, assembled from the windows after finish().  With the blend on the windows agree bit for bit
+        on the frames they share; the lowest window is the one copied."""
+        if self.canvas is None:
+            raise ValueError('prepare(canvas=...) first')
+        offs, T, _ = self.canvas
+        P, Cc, L = self.latents.shape
+        out = torch.empty((1, Cc, T), dtype=self.latents.dtype, device=self.latents.device)
+        for p in reversed(range(P)):
+            out[0, :, offs[p]:offs[p] + L] = self.latents[p]
+        return out
 
     def set_cn_scales(self, scales=None):
         """conditioning_scale per sample of the call prepare() began with a ControlNet: a list of P values, or None to go back to the call's scalar.
@@ -257,6 +307,33 @@ class LatentSampler:
         else:
             torch.cuda.current_stream(self.latents.device).wait_stream(self.stream)
         return self.latents
+
+
+def check_canvas(offsets, L, T, ramp):
+    """The rules of ezdit_sampler_set_canvas, on the host: first offset 0, strictly ascending, no uncovered frame, the last window ends the canvas."""
+    if not offsets or offsets[0] != 0:
+        raise ValueError(f'canvas offsets {offsets}: the first window starts at frame 0')
+    for a, b in zip(offsets, offsets[1:]):
+        if b <= a or b > a + L:
+            raise ValueError(f'canvas offsets {offsets}: each window starts behind the one before and no later than its end (window length {L})')
+    if offsets[-1] + L != T:
+        raise ValueError(f'canvas of {T} frames: the last window ends at frame {offsets[-1] + L}')
+    if ramp < 1:
+        raise ValueError(f'canvas ramp {ramp}: at least 1')
+
+
+def canvas_windows(total_frames, window_frames, min_overlap):
+    """(offsets, L): the fewest windows of L <= window_frames latent frames that cover total_frames with at least min_overlap frames shared between
+    neighbours, spread evenly (integer arithmetic).  A canvas that fits one window is ([0], total_frames): the plain call."""
+    T, L, O = int(total_frames), int(window_frames), int(min_overlap)
+    if T < 1 or L < 1:
+        raise ValueError(f'total_frames={total_frames}, window_frames={window_frames}: both must be positive')
+    if O < 0 or 2 * O > L:
+        raise ValueError(f'min_overlap={min_overlap} outside [0, window_frames / 2 = {L / 2:g}]')
+    if T <= L:
+        return [0], T
+    n = -(-(T - O) // (L - O))
+    return [(i * (T - L) + (n - 1) // 2) // (n - 1) for i in range(n)], L
 
 
 def sample_coefficients(scheduler, etas):
@@ -303,7 +380,7 @@ def pad_conditions(condition, frames, n_prompts):
     return condition
 
 
-def draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n_prompts=1, first_index=0, start_steps=None):
+def draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n_prompts=1, first_index=0, start_steps=None, canvas_offsets=None):
     """Init noise + per-step DDIM noise in the order the reference draws them from ONE generator
     (src/inference.py:58-67 then one randn per scheduler.step, diffusers `randn_tensor`).  For several
     prompts each sample gets its own generator seeded seed + index, so results do not depend on how
@@ -318,7 +395,27 @@ def draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n
 
     ``start_steps`` (audio-to-audio, one step per prompt): sample i draws its init noise, then ddim_steps - start_steps[i] step noises when its eta > 0 --
     the numbers a call with that sample alone draws -- placed at the step indices start_steps[i] .. ddim_steps - 1 of the [K, P, C, L] tensor, which is
-    indexed by absolute step; the slices before are zero and never read."""
+    indexed by absolute step; the slices before are zero and never read.
+
+    ``canvas_offsets`` (long-form canvas, one offset per window; ``audio_frames`` is the window length L): ONE generator, seeded like the single prompt's,
+    draws the init noise (1, C, T) of the canvas of T = canvas_offsets[-1] + L frames and then, when eta > 0, one (1, C, T) per step; window i receives the
+    slice [canvas_offsets[i], canvas_offsets[i] + L), so the windows share their noise where they share frames.  One window draws what the plain call draws."""
+    if canvas_offsets is not None:
+        offs = [int(v) for v in canvas_offsets]
+        if isinstance(audio_frames, (list, tuple)) or isinstance(eta, (list, tuple)) or isinstance(random_seed, (list, tuple)) or start_steps is not None:
+            raise ValueError('a canvas takes one window length, one eta and one seed, and no start steps')
+        L = int(audio_frames)
+        T = offs[-1] + L
+        g = torch.Generator(device=device)
+        if random_seed is not None:
+            g.manual_seed(random_seed + first_index)
+        else:
+            g.seed()
+        cut = lambda t: torch.cat([t[:, :, o:o + L] for o in offs], dim=0)   # noqa: E731
+        init = cut(torch.randn((1, codec_dim, T), generator=g, device=device))
+        if not (eta or 0) > 0:
+            return init, None
+        return init, torch.stack([cut(torch.randn((1, codec_dim, T), generator=g, device=device)) for _ in range(ddim_steps)])
     if start_steps is not None and len(start_steps) != n_prompts:
         raise ValueError(f'{len(start_steps)} start steps for {n_prompts} prompts')
     lens = _frames_list(audio_frames, n_prompts)
@@ -361,7 +458,7 @@ def inference_controlnet(autoencoder, unet, controlnet, gt, gt_mask, condition, 
 def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, noise_scheduler, text_raw,
               neg_text=None, audio_frames=500, guidance_scale=3, guidance_rescale=0.0, ddim_steps=50, eta=1,
               random_seed=2024, device='cuda', use_graph=True, controlnet=None, condition=None, conditioning_scale=1.0,
-              first_index=None, init_latents=None, strength=None, solver='ddim'):
+              first_index=None, init_latents=None, strength=None, canvas_offsets=None, canvas_ramp=None, solver='ddim'):
     """Same signature and semantics as the reference's ``inference`` (src/inference.py:26-107).
 
     Extension: ``solver='dpmpp_2m'`` samples with DPM-Solver++(2M) instead of DDIM (deterministic: eta must be 0, the signature's
@@ -386,11 +483,40 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
     Extension (audio-to-audio): ``init_latents`` [N or 1, C, max(audio_frames)] in VAE space (the encoder's output, padded when ``audio_frames`` is a
     list) with ``strength`` in (0, 1], one value or one per prompt: prompt i starts at step ``noise_scheduler.start_step(strength_i)`` from its clip
     noised to that step instead of from pure noise, and runs the steps that are left.  strength 1 is the plain call, bit for bit.  The latent's
-    scale and shift come from ``params['autoencoder']``.  Audio quality versus strength on the real checkpoints is unmeasured."""
+    scale and shift come from ``params['autoencoder']``.  Audio quality versus strength on the real checkpoints is unmeasured.
+
+    Extension (long-form generation): ``canvas_offsets`` (canvas_windows() chooses them) makes the call ONE clip of canvas_offsets[-1] + audio_frames latent
+    frames, sampled as overlapping windows of ``audio_frames`` frames whose shared frames are averaged inside every step with the ramp ``canvas_ramp``
+    (None: the smallest overlap between neighbours, a linear cross-fade; 1: the plain mean).  ``text_raw`` is one prompt for every window or a list with one
+    prompt per window (a scene that changes over time); the settings are scalars; no gt, ControlNet or init_latents.  The canvas is decoded in one call:
+    the result is [1, 1, T * ratio].  The windows are coupled, so the call is never sharded over ranks.  One window is the plain call.  Audio quality on the
+    real checkpoints -- seam audibility, the choice of overlap and ramp, the comparison with one long row -- is unmeasured."""
     if (init_latents is None) != (strength is None):
         raise ValueError('init_latents and strength must be given together')
     if neg_text is None:
         neg_text = [""]
+    if canvas_offsets is not None:
+        canvas_offsets = [int(v) for v in canvas_offsets]
+        n_win = len(canvas_offsets)
+        if isinstance(text_raw, str):
+            text_raw = [text_raw] * n_win
+        elif len(text_raw) == 1:
+            text_raw = list(text_raw) * n_win
+        if len(text_raw) != n_win:
+            raise ValueError(f'{len(text_raw)} prompts for a canvas of {n_win} windows: one prompt, or one per window')
+        if isinstance(audio_frames, (list, tuple)) or (torch.is_tensor(audio_frames) and audio_frames.dim() > 0):
+            raise ValueError('a canvas takes one window length (audio_frames)')
+        for name, v in (('guidance_scale', guidance_scale), ('guidance_rescale', guidance_rescale), ('eta', eta), ('random_seed', random_seed)):
+            if isinstance(v, (list, tuple)) or (torch.is_tensor(v) and v.dim() > 0):
+                raise ValueError(f'a canvas takes one {name}, not one per window')
+        if gt is not None or gt_mask is not None or controlnet is not None or init_latents is not None:
+            raise ValueError('a canvas does not combine with gt / gt_mask, a ControlNet or init_latents')
+        overlaps = [a + audio_frames - b for a, b in zip(canvas_offsets, canvas_offsets[1:])]
+        if canvas_ramp is None:
+            canvas_ramp = max(1, min(overlaps)) if overlaps else 1
+        check_canvas(canvas_offsets, audio_frames, canvas_offsets[-1] + audio_frames, canvas_ramp)
+    elif canvas_ramp is not None:
+        raise ValueError('canvas_ramp without canvas_offsets')
     if isinstance(text_raw, str):
         text_raw = [text_raw]
     if isinstance(ddim_steps, (list, tuple)):
@@ -403,7 +529,7 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
     frames = _frames_list(audio_frames, len(text_raw))
     if controlnet is not None:
         condition = pad_conditions(condition, frames if frames is not None else audio_frames, len(text_raw))
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and len(text_raw) > 1 and first_index is None:
+    if canvas_offsets is None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and len(text_raw) > 1 and first_index is None:
         from .dist import sample_sharded
         n_all = len(text_raw)
         ratio_ = params['autoencoder']['sr'] // params['autoencoder']['latent_sr']
@@ -456,19 +582,24 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
         if init_latents.dim() != 3 or init_latents.shape[0] not in (1, n_prompts) or tuple(init_latents.shape[1:]) != (codec_dim, lmax):
             raise ValueError(f'init_latents must be [1 or {n_prompts}, {codec_dim}, {lmax}], got {tuple(init_latents.shape)}')
         a2a = dict(init_latents=init_latents, start_steps=starts, latent_scale=params['autoencoder']['scale'], latent_shift=params['autoencoder']['shift'])
+    long_form = canvas_offsets is not None and len(canvas_offsets) > 1   # (one window is the plain call, through the plain code)
     init, step_noises = draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n_prompts, first_index,
-                                    **(dict(start_steps=a2a['start_steps']) if a2a else {}))
+                                    **(dict(start_steps=a2a['start_steps']) if a2a else {}), **(dict(canvas_offsets=canvas_offsets) if long_form else {}))
     smp = LatentSampler(unet, noise_scheduler)
     # equal lengths are the unpadded batch (the same bits; include/ezdit.h ezdit_set_lengths): the length table is for ragged batches only
     ragged = frames is not None and len(set(frames)) > 1
     kw = dict(lengths=frames) if ragged else {}
     if solver != 'ddim':
         kw['solver'] = solver
+    if long_form:
+        kw['canvas'] = (canvas_offsets, canvas_offsets[-1] + audio_frames, canvas_ramp)
     smp.prepare(text.float(), text_mask, uncond_text.float(), uncond_mask, init, step_noises, guidance_scale,
                 guidance_rescale, ddim_steps, eta, gt=gt, gt_mask=gt_mask, controlnet=controlnet, condition=condition,
                 conditioning_scale=conditioning_scale, **kw, **a2a)
     smp.run(use_graph=use_graph)
     latents = smp.finish()
+    if long_form:   # one decode of the whole canvas
+        return autoencoder(embedding=scale_shift_re(smp.canvas_latents(), params['autoencoder']['scale'], params['autoencoder']['shift']))
     pred = scale_shift_re(latents, params['autoencoder']['scale'], params['autoencoder']['shift'])
     if gt is not None:   # src/inference.py:103-104, with a shared [1, C, L] reference broadcast over the prompts
         keep = ~gt_mask.to(pred.device).expand_as(pred)

@@ -11,11 +11,11 @@
  *     allocates or frees persistent device memory.  Weights live in one caller-owned blob laid out
  *     by ezdit_param_info(); all activations / tables live in one caller-owned workspace.
  *   - the PER-STEP entry points (ezdit_forward, ezdit_controlnet_forward, ezdit_sampler_run, ezdit_set_step,
- *     ezdit_cfg_ddim_step, ezdit_cfg_ddim_step_per_sample, ezdit_cfg_multistep_step, ezdit_add_noise, the ezvae_* ops) are ASYNCHRONOUS on their stream: no device sync, no host read of
+ *     ezdit_cfg_ddim_step, ezdit_cfg_ddim_step_per_sample, ezdit_cfg_multistep_step, ezdit_add_noise, ezdit_canvas_blend, the ezvae_* ops) are ASYNCHRONOUS on their stream: no device sync, no host read of
  *     device data (a sampler step is hipGraph-capturable).  The once-per-call SET-UP entry points synchronise the
  *     stream and must not be called inside a stream capture: ezdit_bind_workspace (diagnostic builds only),
  *     ezdit_prepare_context (reads the context mask back to find single-key batch elements when `xkey1` is on),
- *     ezdit_prepare_timesteps, ezdit_sampler_begin, ezdit_sampler_set_sample_params, ezdit_sampler_set_multistep and ezdit_sampler_set_start (host staging
+ *     ezdit_prepare_timesteps, ezdit_sampler_begin, ezdit_sampler_set_sample_params, ezdit_sampler_set_multistep, ezdit_sampler_set_start and ezdit_sampler_set_canvas (host staging
  *     buffers of the timestep / coefficient tables), ezdit_set_lengths, ezdit_sampler_set_pair_lengths and ezdit_sampler_set_cn_scales
  *     (host mirrors of the length / scale tables).
  *   - return 0 = OK, negative = error; ezdit_last_error() gives a thread-local message.  No C++
@@ -327,6 +327,34 @@ int ezdit_add_noise(const float* dev_clean, float* dev_latents, const float* dev
  * capture and before ezdit_sampler_begin.  EZDIT_E_INVALID: P is not the P of ezdit_sampler_begin; a value outside [0, n_steps).
  * A refused call changes nothing. */
 int ezdit_sampler_set_start(ezdit_handle* h, const int32_t* start_steps, int P, ezdit_stream stream);
+
+/* ---- long-form canvas: the P samples of one call are overlapping windows of one long latent, blended inside the step ------------------- */
+/* MultiDiffusion-style sampling of a clip longer than the trained length: a canvas of T frames is covered by P windows of L frames, window p
+ * holding the canvas frames [dev_offsets[p], dev_offsets[p] + L).  The operator averages, in place, every canvas frame that two or more
+ * windows hold:   v = sum_p w_p x_p / sum_p w_p,   w_p = min(r + 1, L - r, ramp) at window p's local frame r = j - dev_offsets[p],
+ * in fp32 over the holders in ascending p, and stores the same v into every holder: the aliases are bit-identical afterwards and the result
+ * does not depend on scheduling.  ramp 1 is the plain mean, ramp = the overlap a linear cross-fade.  An element held by ONE window is neither
+ * read nor written (it may hold NaN); a table without overlap leaves the buffer bitwise untouched.
+ * dev_latents fp32 [P][C][L], dev_offsets int32 [P] ON THE DEVICE (ascending, first 0, no gap, last + L == T: the caller's to guarantee -- no
+ * value makes the kernel touch memory outside the P * C * L elements).  Asynchronous, no handle needed.
+ * EZDIT_E_INVALID: a NULL pointer; P, C or L < 1; ramp < 1; T outside [L, P * L] (what no table can give). */
+int ezdit_canvas_blend(float* dev_latents, const int32_t* dev_offsets, int P, int C, int L, int T, int ramp, ezdit_stream stream);
+
+/* After ezdit_sampler_begin, the P samples of the call are the windows of a canvas of T frames: `offsets` is a HOST array of P first frames.
+ * While the table is on, every step ends with ezdit_canvas_blend on the updated latents (one more kernel behind the update, on the same
+ * stream: one more node of the captured step), so the windows agree on their shared frames after every step and the canvas can be read off
+ * the windows when the run ends.  NULL or P = 0 switches it off, as ezdit_sampler_begin and ezdit_bind_workspace do; while off the step
+ * issues exactly the launches it issues without this call.  The table lives at the END of the workspace (ezdit_workspace_bytes grows by
+ * 1 KB) and is read at run time: new offsets keep the captured step graph; switching on or off, another T or another ramp drops it.
+ * The per-sample settings table and the multistep solver work with it (the blend acts on the updated latents; the history of data
+ * predictions stays per window and is not blended).
+ * A set-up entry point like ezdit_set_lengths: it uploads from host memory and waits for `stream`; EZDIT_E_STATE inside a stream capture
+ * and before ezdit_sampler_begin.  EZDIT_E_INVALID unless P is the P of ezdit_sampler_begin, offsets[0] == 0, the offsets ascend strictly,
+ * offsets[i + 1] <= offsets[i] + L (no uncovered frame), offsets[P - 1] + L == T and ramp >= 1.  EZDIT_E_UNSUPPORTED with a length table
+ * (ezdit_set_lengths), a start table, gt / gt_mask or an attached ControlNet -- long edits, long audio-to-audio and long ControlNet runs
+ * are not implemented; while the canvas is on, ezdit_set_lengths, ezdit_sampler_set_start and ezdit_sampler_attach_controlnet (with a
+ * ControlNet) are refused the same way.  A refused call changes nothing and launches nothing. */
+int ezdit_sampler_set_canvas(ezdit_handle* h, const int32_t* offsets, int P, int T, int ramp, ezdit_stream stream);
 
 /* ---- Oobleck VAE decoder building blocks (src/modules/stable_vae/models/autoencoders.py:38-61,82-113,149-190) --------
  * Stateless ops on caller-owned device buffers; the layer sequence is host code (ezaudio_amd/vae.py), run once per call.
