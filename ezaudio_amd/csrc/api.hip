@@ -58,12 +58,25 @@ struct WsPtrs {  // workspace regions used on the per-step path, resolved once a
     float *cembed, *cnres; bf16_t* skipbf;   // ControlNet only
     float2* zstat; float *zt_qkv, *zt_geglu, *zt_q2;   // LayerNorm algebra: partial row statistics, G' / C' tables
     float2* zstat_skip; float* zt_skip; bf16_t* ucat_z;              // ... of the out-blocks' LN_2D([x | skip]) -> skip_linear: the skips' statistics (kept from the in-block to its out-block), static tables
-    int* lens;   // [B] per-batch-element valid frames (ezdit_set_lengths); read by the kernels only while ezdit_handle::lens_on
-    float *spg, *spc;   // per-sample sampler settings (ezdit_sampler_set_sample_params): [P][2] (guidance_scale, guidance_rescale) and [n_steps][P][8] DDIM coefficients; read only while sp_on
-    int* start;  // [P] first step of each sample (ezdit_sampler_set_start); read by k_cfg_stats / k_cfg_apply only while ezdit_handle::start_on
-    int* canvas; // [P] first canvas frame of each window (ezdit_sampler_set_canvas); read by k_canvas_blend only while ezdit_handle::canvas_on
-    float* cns;  // [B] per-batch-element conditioning_scale of the attached ControlNet (ezdit_sampler_set_cn_scales); read by the row kernel only while ezdit_handle::cns_on
+    float* spc;  // [n_steps][P][8] DDIM coefficients per sample: the second device array of the table ezdit_handle::sp
     float* zd;   // [nblk][B][D] constant cross-attention-out vectors of the single-key batch elements (opt_xkey1)
+};
+
+static void drop_graph(ezdit_handle* h);
+
+// A run-time table of the step (include/ezdit.h, "Run-time tables of the step"): a small device array that the kernels of the captured step read at run time, so
+// one captured step serves every set of values.  Only switching a table on or off changes kernel arguments (null <-> table, or another kernel) and drops the
+// graph; so does a kernel argument that rides with the table (`rearm`: the multistep history pointer, the canvas' T and ramp).  The kernels are given read().
+template <typename T>
+struct Table {
+    bool on = false;
+    std::vector<T> host;   // host mirror: the source of the asynchronous upload, which it must outlive (upload_table)
+    T* dev = nullptr;      // workspace region (resolve_workspace)
+    const T* read() const { return on ? dev : nullptr; }
+    void set(ezdit_handle* owner, bool to, bool rearm = false) {
+        if (to != on || (to && rearm)) drop_graph(owner);
+        on = to;
+    }
 };
 
 static unsigned long long* g_gemm_ts = nullptr;   // ezdit_debug_gemm_timestamps: device buffer for in-kernel cycle stamps (gemm_pp.h, gemm_ks.h, attn.hip)
@@ -101,32 +114,25 @@ struct ezdit_handle {
     hipGraphExec_t graph_exec = nullptr;
     hipGraph_t graph = nullptr;
 
-    // padded batch (ezdit_set_lengths): batch element b is valid on frames [0, lens[b]).  The kernels read the device table at run time, so a captured step serves every
-    // set of lengths; only switching the feature on or off changes kernel arguments (null <-> table) and drops the graph
-    bool lens_on = false;
-    std::vector<int> lens;       // host mirror, expanded to B entries (the source of the asynchronous upload: must outlive it)
-    const int* lens_dev() const { return lens_on ? p.lens : nullptr; }
-    // per-sample sampler settings (ezdit_sampler_set_sample_params), the same contract: k_cfg_stats / k_cfg_apply read the device table at run time, a captured step serves
-    // every set of values, switching the table on or off changes kernel arguments and drops the graph.  Room for sp_cap(B) samples: the B / 2 of a CFG batch
-    bool sp_on = false;
-    std::vector<float> sp_host;   // host mirror: [P][2] then [n_steps][P][8] (the source of the asynchronous upload)
+    // ---- run-time tables of the step (struct Table).  Bind-scoped: cleared by reset_bind_state ----
+    Table<int> lens;     // [B] padded batch (ezdit_set_lengths, ezdit_sampler_set_pair_lengths): batch element b is valid on frames [0, lens[b])
+    const int* lens_dev() const { return lens.read(); }
+    Table<float> cns;    // [B] conditioning_scale per batch element of the attached ControlNet (ezdit_sampler_set_cn_scales), read by the row kernel
+    // ---- call-scoped: they belong to one sampler call and are cleared by reset_call_state ----
+    // per-sample sampler settings (ezdit_sampler_set_sample_params), read by k_cfg_stats / k_cfg_apply: the mirror is [P][2] (guidance_scale, guidance_rescale),
+    // which goes to `dev`, then [n_steps][P][8] DDIM coefficients, which go to p.spc.  Room for sp_cap(B) samples: the B / 2 of a CFG batch
+    Table<float> sp;
     static int sp_cap(int B) { return B / 2 + 1; }
-    // multistep solver (ezdit_sampler_set_multistep): c_hist lives in slot 5 of the `coef` rows (coef_host is their host mirror and the source of the
-    // asynchronous upload), the history of data predictions is the caller's; switching it on or off changes the kernel and drops the graph
-    bool ms_on = false;
+    // the call's coefficient rows [n_steps][8] (ezdit_sampler_begin uploads them; the step always reads them).  `on` is the multistep solver
+    // (ezdit_sampler_set_multistep): c_hist lives in slot 5 of the rows, the history of data predictions ms_hist is the caller's and a kernel argument
+    Table<float> coef;
     float* ms_hist = nullptr;
-    std::vector<float> coef_host;
-    // start table (ezdit_sampler_set_start), the contract of the sample table: the last two kernels of the step read the device table at run time, a captured
-    // step serves every set of values, switching it on or off changes the kernels and drops the graph.  start_min is the step the run begins at
-    bool start_on = false;
+    Table<int> start;    // [P] first step of each sample (ezdit_sampler_set_start), read by the last two kernels of the step.  start_min is the step the run begins at
     int start_min = 0;
-    std::vector<int> start_host;   // host mirror (the source of the asynchronous upload)
-    // long-form canvas (ezdit_sampler_set_canvas): the P windows of the call overlap on a canvas of canvas_T frames and k_canvas_blend, one more launch behind the
-    // update, averages the shared frames.  The kernel reads the device table at run time: new offsets keep the graph, switching it on or off (or another T / ramp,
-    // which are kernel arguments) drops it.  Off: the step issues the launches it has always issued
-    bool canvas_on = false;
+    // [P] first canvas frame of each window (ezdit_sampler_set_canvas): the P windows of the call overlap on a canvas of canvas_T frames and k_canvas_blend, one more
+    // launch behind the update, averages the shared frames (T and the ramp are its arguments).  Off: the step issues the launches it has always issued
+    Table<int> canvas;
     int canvas_T = 0, canvas_ramp = 1;
-    std::vector<int> canvas_host;   // host mirror (the source of the asynchronous upload)
 
     int launches = 0;
     bool is_cn = false;          // ControlNet variant (cfg.controlnet)
@@ -134,10 +140,6 @@ struct ezdit_handle {
     ezdit_handle* cn = nullptr;  // ControlNet attached to this backbone's sampler
     float cn_scale = 1.0f;       // conditioning_scale of the ATTACHED ControlNet (fused sampler only)
     float fwd_cn_scale = 1.0f;   // scale ezdit_forward applies to caller-provided residuals (ezdit_set_cn_scale; default 1)
-    // per-sample conditioning_scale (ezdit_sampler_set_cn_scales), the contract of `lens`: the row kernel reads the device table at run time, a captured step serves every
-    // set of values, switching between the scalar and the table changes a kernel argument and drops the graph
-    bool cns_on = false;
-    std::vector<float> cns_host;   // host mirror, expanded to B entries (the source of the asynchronous upload)
     std::vector<ezdit_handle*> cn_users;  // backbones whose sampler has this ControlNet attached (cleared on destroy)
     const float* ext_mask_embed = nullptr;
     // ---- fixed tile / split-K choices (measured on MI355X in rounds 1-4; the per-shape override options they used to be
@@ -280,6 +282,13 @@ struct ezdit_handle {
         return reinterpret_cast<T*>(ws + bufs.at(name).off);
     }
 };
+
+// the captured step of `h` goes, and that of every backbone that has `h` attached as its ControlNet: their step embeds its kernels, arguments and buffers
+static void drop_graph(ezdit_handle* h) {
+    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
+    if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
+    for (ezdit_handle* u : h->cn_users) drop_graph(u);
+}
 
 namespace {
 
@@ -684,7 +693,9 @@ void resolve_workspace(ezdit_handle* h) {
     p.ao = h->buf<bf16_t>("ao"); p.act = h->buf<bf16_t>("act"); p.part = h->buf<float>("part"); p.y = h->buf<float>("y");
     p.pred = h->buf<float>("pred"); p.kmask = h->buf<uint8_t>("kmask"); p.kc = h->buf<bf16_t>("kc"); p.vc = h->buf<bf16_t>("vc");
     p.mod = h->buf<float>("mod"); p.modf = h->buf<float>("modf");
-    p.zd = h->buf<float>("zd"); p.lens = h->buf<int>("lens"); p.spg = h->buf<float>("spg"); p.spc = h->buf<float>("spc"); p.cns = h->buf<float>("cns"); p.start = h->buf<int>("start"); p.canvas = h->buf<int>("canvas");
+    p.zd = h->buf<float>("zd"); p.spc = h->buf<float>("spc");
+    h->lens.dev = h->buf<int>("lens"); h->cns.dev = h->buf<float>("cns"); h->sp.dev = h->buf<float>("spg"); h->coef.dev = p.coef;
+    h->start.dev = h->buf<int>("start"); h->canvas.dev = h->buf<int>("canvas");
     p.zstat = h->buf<float2>("zstat"); p.zt_qkv = h->buf<float>("zt_qkv"); p.zt_geglu = h->buf<float>("zt_geglu"); p.zt_q2 = h->buf<float>("zt_q2");
     p.zstat_skip = h->buf<float2>("zstat_skip"); p.zt_skip = h->buf<float>("zt_skip"); p.ucat_z = h->buf<bf16_t>("ucat_z");
     if (h->is_cn) { p.cembed = h->buf<float>("cembed"); p.cnres = h->buf<float>("cnres"); p.skipbf = h->buf<bf16_t>("skipbf"); }
@@ -698,6 +709,89 @@ int hook_launch(const char* kernel, const char* config, Launch launch) {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of %s failed: %s", kernel, hipGetErrorString(e));
     return EZDIT_OK;
+}
+
+// what the three stand-alone forms of the update share: one step on the caller's tensors, no device step counter, the whole row when there are no lengths
+CfgDdimArgs standalone_step(const float* pred, float* latents, const float* noise, int P, int n, const int32_t* lens = nullptr, int L = 0) {
+    CfgDdimArgs a;
+    a.pred = pred; a.latents = latents; a.noise = noise;
+    a.P = P; a.n = n;
+    a.lens = lens; a.L = lens ? L : n;
+    return a;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// run-time tables of the step: what every setter shares
+// ------------------------------------------------------------------------------------------------------
+enum class Needs { Bound, BoundBackbone, Begun };   // a bound workspace (on a backbone handle), or a sampler call begun on it
+
+// The checks every table setter `fn` begins with: a handle, the state the table lives in and a stream that is not being captured
+int setter_checks(const ezdit_handle* h, const char* fn, Needs needs, hipStream_t st) {
+    if (!h) return fail(EZDIT_E_INVALID, "null handle");
+    if (needs == Needs::BoundBackbone && h->is_cn) return fail(EZDIT_E_INVALID, "first argument must be a backbone handle");
+    if (needs == Needs::Begun ? !h->latents : !h->ws) return fail(EZDIT_E_STATE, needs == Needs::Begun ? "ezdit_sampler_begin first" : "bind workspace first");
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    if (cs != hipStreamCaptureStatusNone) return fail(EZDIT_E_STATE, "%s inside a stream capture (it uploads from host memory and waits)", fn);
+    return EZDIT_OK;
+}
+
+// New values `v` of a table: they become its host mirror and go to the device.  The copy is asynchronous and reads the mirror, so the stream is drained on both
+// sides: an earlier upload may still be reading the mirror that is replaced, and the next one may replace it right after this call.  With `tail` given the
+// first `head` elements go to t.dev and the rest to `tail` (the sample table's two device arrays)
+template <typename T>
+int upload_table(Table<T>& t, std::vector<T> v, hipStream_t st, size_t head = 0, T* tail = nullptr) {
+    HIPCHK(hipStreamSynchronize(st));
+    t.host.swap(v);
+    if (!tail) head = t.host.size();
+    HIPCHK(hipMemcpyAsync(t.dev, t.host.data(), head * sizeof(T), hipMemcpyHostToDevice, st));
+    if (tail) HIPCHK(hipMemcpyAsync(tail, t.host.data() + head, (t.host.size() - head) * sizeof(T), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return EZDIT_OK;
+}
+
+// n values for B batch rows: row b takes src[b % n], the rule by which batch row b reads latent row b % x_rows (a CFG pair shares its value)
+template <typename T>
+std::vector<T> per_row(const T* src, int n, int B) {
+    std::vector<T> v((size_t)B);
+    for (int b = 0; b < B; ++b) v[b] = src[b % n];
+    return v;
+}
+
+// the per-sample lengths of a call expanded to the B rows of the bound batch, or the refusal of a table that does not fit it
+int expand_lengths(const ezdit_handle* h, const int32_t* lengths, int n, std::vector<int>* v) {
+    if (n < 0 || n > h->B || h->B % n) return fail(EZDIT_E_INVALID, "%d lengths do not divide B = %d", n, h->B);
+    for (int i = 0; i < n; ++i)
+        if (lengths[i] < 1 || lengths[i] > h->L) return fail(EZDIT_E_INVALID, "lengths[%d] = %d outside [1, L = %d]", i, (int)lengths[i], h->L);
+    *v = per_row<int>(lengths, n, h->B);
+    return EZDIT_OK;
+}
+
+// A ControlNet handle carries a length table only as half of an attached pair (ezdit_sampler_set_pair_lengths): when the pair ends -- detach, or the
+// backbone is destroyed -- the table goes, and with it the condition embed that was computed from it.  The backbone keeps its own table.
+void clear_cn_lengths(ezdit_handle* cn) {
+    if (cn->lens.on) cn->cond_ready = false;
+    cn->lens.set(cn, false);
+    cn->lens.host.clear();
+}
+
+// ---- the lifetime of the tables.  Call-scoped ones belong to one sampler call: ezdit_sampler_begin starts without them
+void reset_call_state(ezdit_handle* h) {
+    h->sp.set(h, false);
+    h->coef.set(h, false); h->ms_hist = nullptr;
+    h->start.set(h, false); h->start_min = 0;
+    h->canvas.set(h, false);
+}
+
+// ... bind-scoped ones, and the sampler call itself, belong to one binding of the workspace: a new one zeroes the device arrays and may have another shape, so
+// nothing that was set or begun on the old one holds ("ezdit_sampler_begin first" rests on `latents`)
+void reset_bind_state(ezdit_handle* h) {
+    h->lens.set(h, false); h->lens.host.clear();
+    h->cns.set(h, false);
+    h->coef.host.clear();
+    h->latents = nullptr; h->noise = nullptr; h->s_gt = nullptr; h->s_gt_mask = nullptr;
+    h->P = 0; h->n_steps = 0;
+    drop_graph(h);   // (whatever the tables were: the captured step points at the old buffers)
 }
 
 }  // namespace
@@ -756,31 +850,16 @@ int ezdit_create(const ezdit_config* cfg, ezdit_handle** out) {
     return EZDIT_OK;
 }
 
-static void drop_graph(ezdit_handle* h) {
-    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
-    if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
-}
-
-// A ControlNet handle carries a length table only as half of an attached pair (ezdit_sampler_set_pair_lengths): when the pair ends -- detach, or the
-// backbone is destroyed -- the table goes, and with it the condition embed that was computed from it.  The backbone keeps its own table.
-static void clear_cn_lengths(ezdit_handle* cn) {
-    if (!cn->lens_on) return;
-    cn->lens_on = false; cn->lens.clear();
-    cn->cond_ready = false;
-    for (ezdit_handle* u : cn->cn_users) drop_graph(u);
-}
-
 int ezdit_destroy(ezdit_handle* h) {
     if (!h) return EZDIT_OK;
+    drop_graph(h);
     for (ezdit_handle* u : h->cn_users)   // a backbone must not keep a dangling pointer to this ControlNet
-        if (u->cn == h) { u->cn = nullptr; u->cn_scale = 1.0f; u->cns_on = false; drop_graph(u); }
+        if (u->cn == h) { u->cn = nullptr; u->cn_scale = 1.0f; u->cns.set(u, false); }
     if (h->cn) {
         auto& v = h->cn->cn_users;
         for (size_t i = 0; i < v.size(); ++i) if (v[i] == h) { v.erase(v.begin() + i); break; }
         clear_cn_lengths(h->cn);
     }
-    if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
-    if (h->graph) (void)hipGraphDestroy(h->graph);
     if (h->cn_fork) (void)hipEventDestroy(h->cn_fork);
     if (h->cn_join) (void)hipEventDestroy(h->cn_join);
     if (h->cn_stream) (void)hipStreamDestroy(h->cn_stream);
@@ -827,14 +906,8 @@ int ezdit_bind_workspace(ezdit_handle* h, void* ws, size_t bytes, int B, int L, 
     resolve_workspace(h);
     h->steps_done = 0;
     h->ctx_ready = h->ts_ready = h->cond_ready = false;
-    h->lens_on = false; h->lens.clear();
-    h->sp_on = false;
-    h->cns_on = false;
-    h->ms_on = false; h->ms_hist = nullptr; h->coef_host.clear();
-    h->start_on = false; h->start_min = 0;
-    h->canvas_on = false;
-    drop_graph(h);
-    for (ezdit_handle* u : h->cn_users) drop_graph(u);   // a graph captured with this ControlNet attached points at its old buffers
+    reset_call_state(h);
+    reset_bind_state(h);
     // zero everything once: all padding rows / columns / keys stay zero for the lifetime of the binding
     HIPCHK(hipMemsetAsync(ws, 0, need, st));
     launch_rope_table(h->buf<float>("rope_cos"), h->buf<float>("rope_sin"), h->cfg.max_len, h->dh, st);
@@ -889,10 +962,7 @@ int ezdit_prepare_context(ezdit_handle* h, const float* ctx, const uint8_t* mask
     }
     // the captured step bakes (xkey1, act_b0, act_b1) into its launch structure (DUAL attention-out, cross-attention over a batch sub-range):
     // a context with another single-key pattern must not replay the old graph -- nor may a backbone that captured this ControlNet's kernels
-    if (h->xkey1 != old_x1 || h->act_b0 != old_b0 || h->act_b1 != old_b1) {
-        drop_graph(h);
-        for (ezdit_handle* u : h->cn_users) drop_graph(u);
-    }
+    if (h->xkey1 != old_x1 || h->act_b0 != old_b0 || h->act_b1 != old_b1) drop_graph(h);
     // context_embed: Linear -> SiLU -> Linear  (udit.py:94-97)
     launch_cast_bf16(ctx, h->Cctx, h->buf<bf16_t>("ctx_bf"), h->ldCtx, Mc, h->Cctx, 0, c.st);
     gemm(c, h->buf<bf16_t>("ctx_bf"), h->ldCtx, h->wref("ce.w1"), h->w<float>("ce.b1"), h->buf<float>("c1"), D, Mc, D, EPI_F32, tile_for(h, Mc, false));
@@ -1040,109 +1110,71 @@ int ezdit_set_step(ezdit_handle* h, int step, ezdit_stream stream) {
     if (!h || !h->ws) return fail(EZDIT_E_STATE, "bind workspace first");
     if (step < 0 || step >= h->n_slots) return fail(EZDIT_E_INVALID, "step %d out of range", step);
     // start table: only a rewind to the run's own beginning (first-order for every sample active at it, so also with the multistep solver on)
-    if (h->start_on && step != h->start_min)
+    if (h->start.on && step != h->start_min)
         return fail(EZDIT_E_STATE, "start table: step %d is not the run's first step %d (only a rewind to it keeps every sample's trajectory)", step, h->start_min);
-    if (h->ms_on && !h->start_on && step != 0) return fail(EZDIT_E_STATE, "multistep solver: the history is not step %d's (only a rewind to step 0 keeps it right)", step - 1);
+    if (h->coef.on && !h->start.on && step != 0) return fail(EZDIT_E_STATE, "multistep solver: the history is not step %d's (only a rewind to step 0 keeps it right)", step - 1);
     launch_set_int(h->p.ints, step, 0, (hipStream_t)stream);
     h->steps_done = step;
     return EZDIT_OK;
 }
 
 int ezdit_set_lengths(ezdit_handle* h, const int32_t* lengths, int n, ezdit_stream stream) {
-    if (!h) return fail(EZDIT_E_INVALID, "null handle");
-    if (!h->ws) return fail(EZDIT_E_STATE, "bind workspace first");
     hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-    if (cs != hipStreamCaptureStatusNone) return fail(EZDIT_E_STATE, "ezdit_set_lengths inside a stream capture (it uploads from host memory and waits)");
+    if (int rc = setter_checks(h, "ezdit_set_lengths", Needs::Bound, st)) return rc;
     if (!lengths || n == 0) {
-        if (h->is_cn) { clear_cn_lengths(h); return EZDIT_OK; }   // (a table the pair call left on a ControlNet: its embed goes with it)
-        if (h->lens_on) drop_graph(h);
-        h->lens_on = false; h->lens.clear();
+        if (h->is_cn) clear_cn_lengths(h);   // (a table the pair call left on a ControlNet: its embed goes with it)
+        else { h->lens.set(h, false); h->lens.host.clear(); }
         return EZDIT_OK;
     }
     // one handle's call can set only one of the two tables of an attached pair, and they must agree: the pair has its own call
     if (h->is_cn) return fail(EZDIT_E_UNSUPPORTED, "per-sample lengths on a ControlNet handle (its condition embed is computed from the table: ezdit_sampler_set_pair_lengths on the backbone it is attached to)");
     if (h->cn) return fail(EZDIT_E_UNSUPPORTED, "per-sample lengths with a ControlNet attached: ezdit_sampler_set_pair_lengths sets both tables");
-    if (h->canvas_on) return fail(EZDIT_E_UNSUPPORTED, "per-sample lengths while the canvas is on (ezdit_sampler_set_canvas): its windows have one length");
-    if (n < 0 || n > h->B || h->B % n) return fail(EZDIT_E_INVALID, "%d lengths do not divide B = %d", n, h->B);
-    for (int i = 0; i < n; ++i)
-        if (lengths[i] < 1 || lengths[i] > h->L) return fail(EZDIT_E_INVALID, "lengths[%d] = %d outside [1, L = %d]", i, (int)lengths[i], h->L);
-    std::vector<int> v((size_t)h->B);
-    for (int b = 0; b < h->B; ++b) v[b] = lengths[b % n];   // the rule by which batch row b reads latent row b % x_rows
-    HIPCHK(hipStreamSynchronize(st));   // an earlier upload may still be reading the host mirror
-    h->lens = v;
-    HIPCHK(hipMemcpyAsync(h->p.lens, h->lens.data(), (size_t)h->B * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (!h->lens_on) drop_graph(h);
-    h->lens_on = true;
+    if (h->canvas.on) return fail(EZDIT_E_UNSUPPORTED, "per-sample lengths while the canvas is on (ezdit_sampler_set_canvas): its windows have one length");
+    std::vector<int> v;
+    if (int rc = expand_lengths(h, lengths, n, &v)) return rc;
+    if (int rc = upload_table(h->lens, std::move(v), st)) return rc;
+    h->lens.set(h, true);
     return EZDIT_OK;
 }
 
 // The lengths of an attached pair: one table, uploaded to the backbone AND its ControlNet.  The ControlNet's condition embed is computed from the table
 // (ezdit_prepare_condition moves the convolution boundary to 2 len_b), so a new table invalidates it.
 int ezdit_sampler_set_pair_lengths(ezdit_handle* h, const int32_t* lengths, int n, ezdit_stream stream) {
-    if (!h) return fail(EZDIT_E_INVALID, "null handle");
-    if (h->is_cn) return fail(EZDIT_E_INVALID, "first argument must be a backbone handle");
-    if (!h->ws) return fail(EZDIT_E_STATE, "bind workspace first");
     hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-    if (cs != hipStreamCaptureStatusNone) return fail(EZDIT_E_STATE, "ezdit_sampler_set_pair_lengths inside a stream capture (it uploads from host memory and waits)");
+    if (int rc = setter_checks(h, "ezdit_sampler_set_pair_lengths", Needs::BoundBackbone, st)) return rc;
     ezdit_handle* cn = h->cn;
     if (!cn) return fail(EZDIT_E_STATE, "no ControlNet attached (ezdit_sampler_attach_controlnet first; a backbone alone takes ezdit_set_lengths)");
     if (!cn->ws || cn->B != h->B || cn->L != h->L)
         return fail(EZDIT_E_STATE, "the attached ControlNet is bound to (B, L) = (%d, %d), the backbone to (%d, %d)", cn->ws ? cn->B : 0, cn->ws ? cn->L : 0, h->B, h->L);
     if (!lengths || n == 0) {
-        if (h->lens_on) drop_graph(h);
-        h->lens_on = false; h->lens.clear();
+        h->lens.set(h, false); h->lens.host.clear();
         clear_cn_lengths(cn);
         return EZDIT_OK;
     }
-    if (n < 0 || n > h->B || h->B % n) return fail(EZDIT_E_INVALID, "%d lengths do not divide B = %d", n, h->B);
-    for (int i = 0; i < n; ++i)
-        if (lengths[i] < 1 || lengths[i] > h->L) return fail(EZDIT_E_INVALID, "lengths[%d] = %d outside [1, L = %d]", i, (int)lengths[i], h->L);
-    std::vector<int> v((size_t)h->B);
-    for (int b = 0; b < h->B; ++b) v[b] = lengths[b % n];
-    HIPCHK(hipStreamSynchronize(st));   // an earlier upload may still be reading the host mirrors
-    const bool cn_changed = !cn->lens_on || cn->lens != v;
-    h->lens = v; cn->lens = v;
-    HIPCHK(hipMemcpyAsync(h->p.lens, h->lens.data(), (size_t)h->B * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(cn->p.lens, cn->lens.data(), (size_t)h->B * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (!cn->lens_on) for (ezdit_handle* u : cn->cn_users) drop_graph(u);   // null <-> table in the ControlNet's kernels, which the backbone's step captured
-    if (!h->lens_on) drop_graph(h);
-    h->lens_on = true; cn->lens_on = true;
-    if (cn_changed) cn->cond_ready = false;   // the embed of the old table: ezdit_prepare_condition again
+    std::vector<int> v;
+    if (int rc = expand_lengths(h, lengths, n, &v)) return rc;
+    if (!cn->lens.on || cn->lens.host != v) cn->cond_ready = false;   // the embed of the old table: ezdit_prepare_condition again
+    if (int rc = upload_table(h->lens, v, st)) return rc;
+    if (int rc = upload_table(cn->lens, std::move(v), st)) return rc;
+    h->lens.set(h, true);
+    cn->lens.set(cn, true);   // (null <-> table in the ControlNet's kernels, which the backbone's step captured: drop_graph reaches its users)
     return EZDIT_OK;
 }
 
 // conditioning_scale per batch element of the fused sampler's ControlNet residuals (row b: scales[b % n], the rule of the lengths: a CFG pair shares its scale)
 int ezdit_sampler_set_cn_scales(ezdit_handle* h, const float* scales, int n, ezdit_stream stream) {
-    if (!h) return fail(EZDIT_E_INVALID, "null handle");
-    if (h->is_cn) return fail(EZDIT_E_INVALID, "first argument must be a backbone handle");
-    if (!h->ws) return fail(EZDIT_E_STATE, "bind workspace first");
     hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-    if (cs != hipStreamCaptureStatusNone) return fail(EZDIT_E_STATE, "ezdit_sampler_set_cn_scales inside a stream capture (it uploads from host memory and waits)");
+    if (int rc = setter_checks(h, "ezdit_sampler_set_cn_scales", Needs::BoundBackbone, st)) return rc;
     if (!h->cn) return fail(EZDIT_E_STATE, "no ControlNet attached (ezdit_sampler_attach_controlnet first)");
     if (!scales || n == 0) {
-        if (h->cns_on) drop_graph(h);
-        h->cns_on = false;
+        h->cns.set(h, false);
         return EZDIT_OK;
     }
     if (n < 0 || n > h->B || h->B % n) return fail(EZDIT_E_INVALID, "%d scales do not divide B = %d", n, h->B);
     for (int i = 0; i < n; ++i)
         if (!std::isfinite(scales[i])) return fail(EZDIT_E_INVALID, "non-finite conditioning scale of sample %d", i);
-    std::vector<float> v((size_t)h->B);
-    for (int b = 0; b < h->B; ++b) v[b] = scales[b % n];
-    HIPCHK(hipStreamSynchronize(st));   // an earlier upload may still be reading the host mirror
-    h->cns_host.swap(v);
-    HIPCHK(hipMemcpyAsync(h->p.cns, h->cns_host.data(), (size_t)h->B * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (!h->cns_on) drop_graph(h);
-    h->cns_on = true;
+    if (int rc = upload_table(h->cns, per_row<float>(scales, n, h->B), st)) return rc;
+    h->cns.set(h, true);
     return EZDIT_OK;
 }
 
@@ -1457,7 +1489,7 @@ int ezdit_forward(ezdit_handle* h, const float* x, int in_ch, int x_rows, const 
     if (in_ch == h->C && (x_rows <= 0 || h->B % x_rows)) return fail(EZDIT_E_INVALID, "x_rows %d does not divide B %d", x_rows, h->B);
     if ((gt == nullptr) != (gt_mask == nullptr)) return fail(EZDIT_E_INVALID, "gt and gt_mask must be given together");
     if (n_cn != 0 && n_cn != h->nhalf) return fail(EZDIT_E_INVALID, "n_cn %d: expected 0 or %d", n_cn, h->nhalf);
-    if (n_cn != 0 && h->lens_on) return fail(EZDIT_E_UNSUPPORTED, "ControlNet residuals with per-sample lengths (ezdit_set_lengths)");
+    if (n_cn != 0 && h->lens.on) return fail(EZDIT_E_UNSUPPORTED, "ControlNet residuals with per-sample lengths (ezdit_set_lengths)");
     // the caller's residuals are already multiplied by conditioning_scale (DiTControlNet.forward returns them scaled,
     // controlnet.py:313); a scale left on the handle by the fused sampler must not be applied a second time
     return forward_impl(h, x, in_ch, x_rows, gt, gt_mask, cn_skips, n_cn, h->fwd_cn_scale, out, (hipStream_t)stream);
@@ -1522,7 +1554,7 @@ int ezdit_controlnet_residuals(ezdit_handle* h, const float** out, int n) {
 int ezdit_sampler_attach_controlnet(ezdit_handle* h, ezdit_handle* cn, float conditioning_scale) {
     if (!h || h->is_cn) return fail(EZDIT_E_INVALID, "first argument must be a backbone handle");
     if (cn && !cn->is_cn) return fail(EZDIT_E_INVALID, "second argument must be a ControlNet handle");
-    if (cn && h->canvas_on) return fail(EZDIT_E_UNSUPPORTED, "a ControlNet while the canvas is on (ezdit_sampler_set_canvas)");
+    if (cn && h->canvas.on) return fail(EZDIT_E_UNSUPPORTED, "a ControlNet while the canvas is on (ezdit_sampler_set_canvas)");
     if (h->cn && h->cn != cn) {
         auto& v = h->cn->cn_users;
         for (size_t i = 0; i < v.size(); ++i) if (v[i] == h) { v.erase(v.begin() + i); break; }
@@ -1531,14 +1563,13 @@ int ezdit_sampler_attach_controlnet(ezdit_handle* h, ezdit_handle* cn, float con
     if (cn && h->cn != cn) cn->cn_users.push_back(h);
     h->cn = cn;
     h->cn_scale = cn ? conditioning_scale : 1.0f;
-    h->cns_on = false;   // an attach gives every sample this scalar; ezdit_sampler_set_cn_scales comes after it
+    h->cns.set(h, false);   // an attach gives every sample this scalar; ezdit_sampler_set_cn_scales comes after it
     if (cn && !h->cn_stream) {   // side stream + fork / join events of the overlapped ControlNet branch: created here, never inside a stream capture
         HIPCHK(hipStreamCreateWithFlags(&h->cn_stream, hipStreamNonBlocking));
         HIPCHK(hipEventCreateWithFlags(&h->cn_fork, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&h->cn_join, hipEventDisableTiming));
     }
-    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
-    if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
+    drop_graph(h);
     return EZDIT_OK;
 }
 
@@ -1558,30 +1589,24 @@ int ezdit_sampler_begin(ezdit_handle* h, float* latents, int P, const float* noi
     const int needB = guidance_scale > 0.f ? 2 * P : P;
     if (P <= 0 || needB != h->B) return fail(EZDIT_E_INVALID, "P=%d with guidance %g needs B=%d, workspace has B=%d", P, (double)guidance_scale, needB, h->B);
     if ((gt == nullptr) != (gt_mask == nullptr)) return fail(EZDIT_E_INVALID, "gt and gt_mask must be given together");
-    if (h->lens_on && needB == 2 * P)
+    if (h->lens.on && needB == 2 * P)
         for (int p = 0; p < P; ++p)
-            if (h->lens[p] != h->lens[P + p]) return fail(EZDIT_E_INVALID, "lengths of the CFG pair of sample %d differ (%d, %d)", p, h->lens[p], h->lens[P + p]);
+            if (h->lens.host[p] != h->lens.host[P + p])
+                return fail(EZDIT_E_INVALID, "lengths of the CFG pair of sample %d differ (%d, %d)", p, h->lens.host[p], h->lens.host[P + p]);
     hipStream_t st = (hipStream_t)stream;
     std::vector<float> cf((size_t)n_steps * 8, 0.f);
     for (int i = 0; i < n_steps; ++i) {
         cf[i * 8 + 0] = coefs[i].sa; cf[i * 8 + 1] = coefs[i].sb; cf[i * 8 + 2] = coefs[i].c_x0;
         cf[i * 8 + 3] = coefs[i].c_dir; cf[i * 8 + 4] = coefs[i].sigma;
     }
-    HIPCHK(hipStreamSynchronize(st));   // an earlier upload may still be reading the host mirror
-    h->coef_host.swap(cf);
-    HIPCHK(hipMemcpyAsync(h->buf<float>("coef"), h->coef_host.data(), h->coef_host.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (int rc = upload_table(h->coef, std::move(cf), st)) return rc;
     launch_set_int(h->p.ints, 0, 0, st);
     h->steps_done = 0;
     h->latents = latents; h->noise = noise; h->P = P; h->n_steps = n_steps;
     h->gscale = guidance_scale; h->grescale = guidance_rescale;
-    h->sp_on = false;   // per-sample settings belong to one sampler call (the graph is dropped below anyway)
-    h->ms_on = false; h->ms_hist = nullptr;   // ... and so does the multistep solver
-    h->start_on = false; h->start_min = 0;    // ... and the start table
-    h->canvas_on = false;                     // ... and the canvas table
     h->s_gt = gt; h->s_gt_mask = gt_mask;
-    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
-    if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
+    reset_call_state(h);
+    drop_graph(h);   // (another latents pointer, other scalars: whatever the tables were)
     return EZDIT_OK;
 }
 
@@ -1616,25 +1641,24 @@ static int sampler_step(ezdit_handle* h, hipStream_t st) {
         for (int i = 0; i < n_cn; ++i) cnp[i] = cn->p.cnres + (size_t)i * cn->Mp * cn->D;
     }
     int rc = forward_impl(h, h->latents, h->C, h->P, h->s_gt, h->s_gt_mask, n_cn ? cnp : nullptr, n_cn, h->cn_scale, pred, st, cn_ready, nullptr,
-                          (n_cn && h->cns_on) ? h->p.cns : nullptr);
+                          n_cn ? h->cns.read() : nullptr);
     if (rc && cn_ready) (void)hipStreamWaitEvent(st, cn_ready, 0);
     if (rc) return rc;
     CfgDdimArgs a;
     a.pred = pred; a.latents = h->latents; a.noise = h->noise;
     a.coef = h->p.coef; a.cur_step = h->p.ints;
-    for (float& v : a.hc) v = 0.f;
     a.guidance_scale = h->gscale; a.guidance_rescale = h->grescale;
     a.P = h->P; a.n = h->C * h->L;
     a.step_inc = h->p.ints; a.done = reinterpret_cast<unsigned*>(h->p.ints + 8);
     a.lens = h->lens_dev(); a.L = h->L;
-    a.sp_g = h->sp_on ? h->p.spg : nullptr; a.sp_c = h->sp_on ? h->p.spc : nullptr; a.sp_g_stride = 2;
-    a.x0_hist = h->ms_on ? h->ms_hist : nullptr;
-    a.start = h->start_on ? h->p.start : nullptr;
+    a.sp_g = h->sp.read(); a.sp_c = h->sp.on ? h->p.spc : nullptr; a.sp_g_stride = 2;
+    a.x0_hist = h->coef.on ? h->ms_hist : nullptr;
+    a.start = h->start.read();
     launch_cfg_ddim(a, h->p.cfgpart, st);   // its last kernel also advances the device step counter
-    h->launches += (h->sp_on || (h->gscale > 0.f && h->grescale > 0.f)) ? 2 : 1;
-    if (h->canvas_on) {   // long-form canvas: the windows' shared frames are averaged on the updated latents (x0_hist stays per window)
+    h->launches += (h->sp.on || (h->gscale > 0.f && h->grescale > 0.f)) ? 2 : 1;
+    if (h->canvas.on) {   // long-form canvas: the windows' shared frames are averaged on the updated latents (x0_hist stays per window)
         CanvasBlendArgs cb;
-        cb.latents = h->latents; cb.off = h->p.canvas; cb.P = h->P; cb.C = h->C; cb.L = h->L; cb.T = h->canvas_T; cb.ramp = h->canvas_ramp;
+        cb.latents = h->latents; cb.off = h->canvas.dev; cb.P = h->P; cb.C = h->C; cb.L = h->L; cb.T = h->canvas_T; cb.ramp = h->canvas_ramp;
         launch_canvas_blend(cb, st);
         h->launches += 1;
     }
@@ -1649,15 +1673,9 @@ int ezdit_cfg_ddim_step(const float* pred, float* latents, const float* noise, c
                         float guidance_rescale, int P, int n, float* scratch, ezdit_stream stream) {
     if (!pred || !latents || !coef || P < 1 || n < 2) return fail(EZDIT_E_INVALID, "bad argument");
     if (guidance_scale > 0.f && guidance_rescale > 0.f && !scratch) return fail(EZDIT_E_INVALID, "guidance_rescale needs %d scratch floats", P * 256);
-    CfgDdimArgs a;
-    a.pred = pred; a.latents = latents; a.noise = noise; a.coef = nullptr; a.cur_step = nullptr;
-    a.hc[0] = coef->sa; a.hc[1] = coef->sb; a.hc[2] = coef->c_x0; a.hc[3] = coef->c_dir; a.hc[4] = coef->sigma; a.hc[5] = 0.f;
+    CfgDdimArgs a = standalone_step(pred, latents, noise, P, n);
+    a.hc[0] = coef->sa; a.hc[1] = coef->sb; a.hc[2] = coef->c_x0; a.hc[3] = coef->c_dir; a.hc[4] = coef->sigma;
     a.guidance_scale = guidance_scale; a.guidance_rescale = guidance_rescale;
-    a.P = P; a.n = n;
-    a.step_inc = nullptr; a.done = nullptr;
-    a.lens = nullptr; a.L = n;
-    a.sp_g = nullptr; a.sp_c = nullptr; a.sp_g_stride = 0;
-    a.x0_hist = nullptr; a.start = nullptr;
     launch_cfg_ddim(a, scratch, (hipStream_t)stream);
     return EZDIT_OK;
 }
@@ -1669,15 +1687,8 @@ int ezdit_cfg_ddim_step_per_sample(const float* pred, float* latents, const floa
     if (!pred || !latents || !params || P < 1 || n < 2) return fail(EZDIT_E_INVALID, "bad argument");
     if (!scratch) return fail(EZDIT_E_INVALID, "the per-sample step needs %d scratch floats", P * 256);
     if (lens && (L < 1 || n % L)) return fail(EZDIT_E_INVALID, "lens given: L = %d must divide n = %d", L, n);
-    CfgDdimArgs a;
-    a.pred = pred; a.latents = latents; a.noise = noise; a.coef = nullptr; a.cur_step = nullptr;
-    for (float& v : a.hc) v = 0.f;
-    a.guidance_scale = 0.f; a.guidance_rescale = 0.f;
-    a.P = P; a.n = n;
-    a.step_inc = nullptr; a.done = nullptr;
-    a.lens = lens; a.L = lens ? L : n;
+    CfgDdimArgs a = standalone_step(pred, latents, noise, P, n, lens, L);
     a.sp_g = params; a.sp_c = params + 2; a.sp_g_stride = 8;
-    a.x0_hist = nullptr; a.start = nullptr;
     return hook_launch("k_cfg_*", "", [&] { launch_cfg_ddim(a, scratch, (hipStream_t)stream); return 0; });
 }
 
@@ -1688,46 +1699,33 @@ int ezdit_cfg_multistep_step(const float* pred, float* latents, float* x0_hist, 
     if (!pred || !latents || !x0_hist || !params || P < 1 || n < 2) return fail(EZDIT_E_INVALID, "bad argument");
     if (!scratch) return fail(EZDIT_E_INVALID, "the multistep step needs %d scratch floats", P * 256);
     if (lens && (L < 1 || n % L)) return fail(EZDIT_E_INVALID, "lens given: L = %d must divide n = %d", L, n);
-    CfgDdimArgs a;
-    a.pred = pred; a.latents = latents; a.noise = nullptr; a.coef = nullptr; a.cur_step = nullptr;
-    for (float& v : a.hc) v = 0.f;
-    a.guidance_scale = 0.f; a.guidance_rescale = 0.f;
-    a.P = P; a.n = n;
-    a.step_inc = nullptr; a.done = nullptr;
-    a.lens = lens; a.L = lens ? L : n;
+    CfgDdimArgs a = standalone_step(pred, latents, nullptr, P, n, lens, L);
     a.sp_g = params; a.sp_c = params + 2; a.sp_g_stride = 8;
-    a.x0_hist = x0_hist; a.start = nullptr;
+    a.x0_hist = x0_hist;
     return hook_launch("k_cfg_*", "", [&] { launch_cfg_ddim(a, scratch, (hipStream_t)stream); return 0; });
 }
 
 int ezdit_sampler_set_multistep(ezdit_handle* h, const float* c_hist, int n_steps, float* x0_hist, ezdit_stream stream) {
-    if (!h) return fail(EZDIT_E_INVALID, "null handle");
-    if (!h->ws || !h->latents) return fail(EZDIT_E_STATE, "ezdit_sampler_begin first");
     hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-    if (cs != hipStreamCaptureStatusNone) return fail(EZDIT_E_STATE, "ezdit_sampler_set_multistep inside a stream capture (it uploads from host memory and waits)");
+    if (int rc = setter_checks(h, "ezdit_sampler_set_multistep", Needs::Begun, st)) return rc;
     const int ns = h->n_steps;
-    if ((int)h->coef_host.size() != ns * 8) return fail(EZDIT_E_STATE, "ezdit_sampler_begin first");
     if (c_hist) {
         if (n_steps != ns) return fail(EZDIT_E_INVALID, "n_steps = %d, the sampler was begun with %d", n_steps, ns);
         if (!x0_hist) return fail(EZDIT_E_INVALID, "c_hist given without a history buffer");
         for (int i = 0; i < ns; ++i)
             if (!std::isfinite(c_hist[i])) return fail(EZDIT_E_INVALID, "non-finite c_hist of step %d", i);
         if (h->noise) return fail(EZDIT_E_INVALID, "the multistep solver is deterministic: the sampler was begun with noise");
-        if (h->sp_on) {
-            const float* c = h->sp_host.data() + (size_t)h->P * 2;
+        if (h->sp.on) {
+            const float* c = h->sp.host.data() + (size_t)h->P * 2;
             for (long i = 0; i < (long)ns * h->P; ++i)
                 if (c[i * 8 + 4] != 0.f) return fail(EZDIT_E_INVALID, "the multistep solver is deterministic: sigma != 0 in the sample table (step %ld, sample %ld)", i / h->P, i % h->P);
         }
     }
-    HIPCHK(hipStreamSynchronize(st));   // an earlier upload may still be reading the host mirror
-    for (int i = 0; i < ns; ++i) h->coef_host[(size_t)i * 8 + 5] = c_hist ? c_hist[i] : 0.f;
-    HIPCHK(hipMemcpyAsync(h->p.coef, h->coef_host.data(), h->coef_host.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
+    std::vector<float> rows = h->coef.host;
+    for (int i = 0; i < ns; ++i) rows[(size_t)i * 8 + 5] = c_hist ? c_hist[i] : 0.f;
+    if (int rc = upload_table(h->coef, std::move(rows), st)) return rc;
     const bool on = c_hist != nullptr;
-    if (on != h->ms_on || (on && x0_hist != h->ms_hist)) drop_graph(h);   // (another history buffer is another kernel argument)
-    h->ms_on = on;
+    h->coef.set(h, on, x0_hist != h->ms_hist);   // (another history buffer is another kernel argument)
     h->ms_hist = on ? x0_hist : nullptr;
     return EZDIT_OK;
 }
@@ -1743,37 +1741,27 @@ int ezdit_add_noise(const float* clean, float* latents, const float* params, flo
 }
 
 int ezdit_sampler_set_start(ezdit_handle* h, const int32_t* start_steps, int P, ezdit_stream stream) {
-    if (!h) return fail(EZDIT_E_INVALID, "null handle");
-    if (!h->ws || !h->latents) return fail(EZDIT_E_STATE, "ezdit_sampler_begin first");
     hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-    if (cs != hipStreamCaptureStatusNone) return fail(EZDIT_E_STATE, "ezdit_sampler_set_start inside a stream capture (it uploads from host memory and waits)");
-    if ((int)h->coef_host.size() != h->n_steps * 8) return fail(EZDIT_E_STATE, "ezdit_sampler_begin first");
+    if (int rc = setter_checks(h, "ezdit_sampler_set_start", Needs::Begun, st)) return rc;
     if (!start_steps || P == 0) {   // off: every sample runs from step 0 again
-        if (h->start_on) {   // (the run it belonged to began at start_min: the plain run begins at 0)
-            drop_graph(h);
+        if (h->start.on) {   // (the run it belonged to began at start_min: the plain run begins at 0)
             launch_set_int(h->p.ints, 0, 0, st);
             h->steps_done = 0;
         }
-        h->start_on = false; h->start_min = 0;
+        h->start.set(h, false); h->start_min = 0;
         return EZDIT_OK;
     }
-    if (h->canvas_on) return fail(EZDIT_E_UNSUPPORTED, "a start table while the canvas is on (ezdit_sampler_set_canvas): its windows run every step together");
+    if (h->canvas.on) return fail(EZDIT_E_UNSUPPORTED, "a start table while the canvas is on (ezdit_sampler_set_canvas): its windows run every step together");
     if (P != h->P) return fail(EZDIT_E_INVALID, "P = %d, the sampler was begun with P = %d", P, h->P);
     int lo = h->n_steps;
     for (int p = 0; p < P; ++p) {
         if (start_steps[p] < 0 || start_steps[p] >= h->n_steps) return fail(EZDIT_E_INVALID, "start_steps[%d] = %d outside [0, n_steps = %d)", p, (int)start_steps[p], h->n_steps);
         if (start_steps[p] < lo) lo = start_steps[p];
     }
-    HIPCHK(hipStreamSynchronize(st));   // an earlier upload may still be reading the host mirror
-    h->start_host.assign(start_steps, start_steps + P);
-    HIPCHK(hipMemcpyAsync(h->p.start, h->start_host.data(), (size_t)P * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (int rc = upload_table(h->start, std::vector<int>(start_steps, start_steps + P), st)) return rc;
     launch_set_int(h->p.ints, lo, 0, st);
     h->steps_done = lo;
-    if (!h->start_on) drop_graph(h);
-    h->start_on = true; h->start_min = lo;
+    h->start.set(h, true); h->start_min = lo;
     return EZDIT_OK;
 }
 
@@ -1789,16 +1777,10 @@ int ezdit_canvas_blend(float* latents, const int32_t* offsets, int P, int C, int
 }
 
 int ezdit_sampler_set_canvas(ezdit_handle* h, const int32_t* offsets, int P, int T, int ramp, ezdit_stream stream) {
-    if (!h) return fail(EZDIT_E_INVALID, "null handle");
-    if (!h->ws || !h->latents) return fail(EZDIT_E_STATE, "ezdit_sampler_begin first");
     hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-    if (cs != hipStreamCaptureStatusNone) return fail(EZDIT_E_STATE, "ezdit_sampler_set_canvas inside a stream capture (it uploads from host memory and waits)");
-    if ((int)h->coef_host.size() != h->n_steps * 8) return fail(EZDIT_E_STATE, "ezdit_sampler_begin first");
+    if (int rc = setter_checks(h, "ezdit_sampler_set_canvas", Needs::Begun, st)) return rc;
     if (!offsets || P == 0) {   // off: independent windows again
-        if (h->canvas_on) drop_graph(h);
-        h->canvas_on = false;
+        h->canvas.set(h, false);
         return EZDIT_OK;
     }
     const int L = h->L;
@@ -1811,30 +1793,22 @@ int ezdit_sampler_set_canvas(ezdit_handle* h, const int32_t* offsets, int P, int
             return fail(EZDIT_E_INVALID, "offsets[%d] = %d leaves a gap behind window %d, which ends at frame %ld", i + 1, (int)offsets[i + 1], i, (long)offsets[i] + L);
     }
     if ((long)offsets[P - 1] + L != (long)T) return fail(EZDIT_E_INVALID, "T = %d, the last window ends at frame %ld", T, (long)offsets[P - 1] + L);
-    if (h->lens_on) return fail(EZDIT_E_UNSUPPORTED, "a canvas with per-sample lengths (ezdit_set_lengths): its windows have one length");
-    if (h->start_on) return fail(EZDIT_E_UNSUPPORTED, "a canvas with a start table (ezdit_sampler_set_start)");
+    if (h->lens.on) return fail(EZDIT_E_UNSUPPORTED, "a canvas with per-sample lengths (ezdit_set_lengths): its windows have one length");
+    if (h->start.on) return fail(EZDIT_E_UNSUPPORTED, "a canvas with a start table (ezdit_sampler_set_start)");
     if (h->s_gt) return fail(EZDIT_E_UNSUPPORTED, "a canvas with gt / gt_mask: long edits are not implemented");
     if (h->cn) return fail(EZDIT_E_UNSUPPORTED, "a canvas with a ControlNet attached");
-    HIPCHK(hipStreamSynchronize(st));   // an earlier upload may still be reading the host mirror
-    h->canvas_host.assign(offsets, offsets + P);
-    HIPCHK(hipMemcpyAsync(h->p.canvas, h->canvas_host.data(), (size_t)P * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (!h->canvas_on || T != h->canvas_T || ramp != h->canvas_ramp) drop_graph(h);   // (T and the ramp are kernel arguments)
-    h->canvas_on = true; h->canvas_T = T; h->canvas_ramp = ramp;
+    if (int rc = upload_table(h->canvas, std::vector<int>(offsets, offsets + P), st)) return rc;
+    h->canvas.set(h, true, T != h->canvas_T || ramp != h->canvas_ramp);   // (T and the ramp are kernel arguments)
+    h->canvas_T = T; h->canvas_ramp = ramp;
     return EZDIT_OK;
 }
 
 int ezdit_sampler_set_sample_params(ezdit_handle* h, const float* guidance_scale, const float* guidance_rescale, const ezdit_ddim_coef* coefs, int P,
                                     ezdit_stream stream) {
-    if (!h) return fail(EZDIT_E_INVALID, "null handle");
-    if (!h->ws || !h->latents) return fail(EZDIT_E_STATE, "ezdit_sampler_begin first");
     hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-    if (cs != hipStreamCaptureStatusNone) return fail(EZDIT_E_STATE, "ezdit_sampler_set_sample_params inside a stream capture (it uploads from host memory and waits)");
+    if (int rc = setter_checks(h, "ezdit_sampler_set_sample_params", Needs::Begun, st)) return rc;
     if ((!guidance_scale && !guidance_rescale && !coefs) || P == 0) {
-        if (h->sp_on) drop_graph(h);
-        h->sp_on = false;
+        h->sp.set(h, false);
         return EZDIT_OK;
     }
     if (!guidance_scale || !guidance_rescale || !coefs) return fail(EZDIT_E_INVALID, "guidance_scale, guidance_rescale and coefs must be given together");
@@ -1854,16 +1828,11 @@ int ezdit_sampler_set_sample_params(ezdit_handle* h, const float* guidance_scale
         if (!std::isfinite(k.sa) || !std::isfinite(k.sb) || !std::isfinite(k.c_x0) || !std::isfinite(k.c_dir) || !std::isfinite(k.sigma))
             return fail(EZDIT_E_INVALID, "non-finite coefficient of step %ld, sample %ld", i / P, i % P);
         if (k.sigma != 0.f && !h->noise) return fail(EZDIT_E_INVALID, "sigma != 0 (step %ld, sample %ld) on a sampler begun without noise", i / P, i % P);
-        if (k.sigma != 0.f && h->ms_on) return fail(EZDIT_E_INVALID, "sigma != 0 (step %ld, sample %ld) while the multistep solver is on (it is deterministic)", i / P, i % P);
+        if (k.sigma != 0.f && h->coef.on) return fail(EZDIT_E_INVALID, "sigma != 0 (step %ld, sample %ld) while the multistep solver is on (it is deterministic)", i / P, i % P);
         c[i * 8 + 0] = k.sa; c[i * 8 + 1] = k.sb; c[i * 8 + 2] = k.c_x0; c[i * 8 + 3] = k.c_dir; c[i * 8 + 4] = k.sigma;
     }
-    HIPCHK(hipStreamSynchronize(st));   // an earlier upload may still be reading the host mirror
-    h->sp_host.swap(v);
-    HIPCHK(hipMemcpyAsync(h->p.spg, h->sp_host.data(), (size_t)P * 2 * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(h->p.spc, h->sp_host.data() + (size_t)P * 2, (size_t)ns * P * 8 * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (!h->sp_on) drop_graph(h);
-    h->sp_on = true;
+    if (int rc = upload_table(h->sp, std::move(v), st, (size_t)P * 2, h->p.spc)) return rc;
+    h->sp.set(h, true);
     return EZDIT_OK;
 }
 
@@ -1880,13 +1849,14 @@ int ezdit_sampler_run(ezdit_handle* h, int n, int use_graph, ezdit_stream stream
         // an attached pair runs on ONE length table held twice (ezdit_sampler_set_pair_lengths) and on the condition embed computed from it.  Checked here, not in the
         // step: a replay of the captured graph reads the tables too
         const ezdit_handle* cn = h->cn;
-        if (h->lens_on != cn->lens_on)
-            return fail(EZDIT_E_STATE, "per-sample lengths are set on the %s only: an attached pair takes them through ezdit_sampler_set_pair_lengths", h->lens_on ? "backbone" : "ControlNet");
-        if (h->lens_on && h->lens != cn->lens) {
+        const std::vector<int>&hl = h->lens.host, &cl = cn->lens.host;
+        if (h->lens.on != cn->lens.on)
+            return fail(EZDIT_E_STATE, "per-sample lengths are set on the %s only: an attached pair takes them through ezdit_sampler_set_pair_lengths", h->lens.on ? "backbone" : "ControlNet");
+        if (h->lens.on && hl != cl) {
             size_t b = 0;
-            while (b < h->lens.size() && b < cn->lens.size() && h->lens[b] == cn->lens[b]) ++b;
+            while (b < hl.size() && b < cl.size() && hl[b] == cl[b]) ++b;
             return fail(EZDIT_E_STATE, "the length tables of the backbone and the attached ControlNet differ at batch row %zu (%d, %d)", b,
-                        b < h->lens.size() ? h->lens[b] : -1, b < cn->lens.size() ? cn->lens[b] : -1);
+                        b < hl.size() ? hl[b] : -1, b < cl.size() ? cl[b] : -1);
         }
         if (!cn->cond_ready) return fail(EZDIT_E_STATE, "the attached ControlNet has no condition embed for its current lengths: ezdit_prepare_condition first");
     }
@@ -2275,7 +2245,6 @@ int ezdit_set_option(ezdit_handle* h, const char* name, int value) {
 #endif
     else return fail(EZDIT_E_INVALID, "unknown option %s", name);
     drop_graph(h);
-    for (ezdit_handle* u : h->cn_users) drop_graph(u);   // a backbone's captured step embeds the attached ControlNet's kernels and arguments
     return EZDIT_OK;
 }
 

@@ -354,35 +354,35 @@ void launch_mod_finalize(const ModFinalizeArgs& a, hipStream_t st);
 
 void launch_rope_table(float* cosT, float* sinT, int max_len, int dh, hipStream_t st);
 
-struct CfgDdimArgs {
-    const float* pred;   // [B][C][L]; rows [0,P) cond, [P,2P) uncond (or B = P without CFG)
-    float* latents;      // [P][C][L] in/out
-    const float* noise;  // [n_steps][P][C][L] or null
-    const float* coef;   // [n_steps][8] (sa, sb, c_x0, c_dir, sigma, c_hist, 0,0)
-    const int* cur_step; // null: standalone step, coefficients in hc[], noise is this step's slice
-    float hc[6];         // (sa, sb, c_x0, c_dir, sigma, c_hist) when cur_step is null
-    float guidance_scale, guidance_rescale;  // guidance_scale <= 0: no CFG
-    int P, n;            // n = C*L elements per sample
+struct CfgDdimArgs {   // (the defaults are the stand-alone operator with everything optional off: a site sets what it uses)
+    const float* pred = nullptr;   // [B][C][L]; rows [0,P) cond, [P,2P) uncond (or B = P without CFG)
+    float* latents = nullptr;      // [P][C][L] in/out
+    const float* noise = nullptr;  // [n_steps][P][C][L] or null
+    const float* coef = nullptr;   // [n_steps][8] (sa, sb, c_x0, c_dir, sigma, c_hist, 0,0)
+    const int* cur_step = nullptr; // null: standalone step, coefficients in hc[], noise is this step's slice
+    float hc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // (sa, sb, c_x0, c_dir, sigma, c_hist) when cur_step is null
+    float guidance_scale = 0.f, guidance_rescale = 0.f;  // guidance_scale <= 0: no CFG
+    int P = 0, n = 0;              // n = C*L elements per sample
     // fused sampler: the LAST workgroup to finish (arrival counter `done`, zero between launches) advances the device step
     // counter, so the step needs no separate single-thread launch.  Both null: stand-alone operator.
-    int* step_inc; unsigned* done;
+    int* step_inc = nullptr; unsigned* done = nullptr;
     // padded batch (null lens = every sample has n elements): sample p is valid on frames [0, lens[p]) of its L (n = C * L): the rescale statistics run over
     // the C * lens[p] valid elements, frames >= lens[p] of the latents are written as zero whatever pred / noise / latents hold there
-    const int* lens; int L;
+    const int* lens = nullptr; int L = 0;   // (L = n when there is no lens)
     // per-sample settings (null sp_g = off: the scalar arguments above and coef / hc hold for every sample).  On: sample p takes (guidance_scale,
     // guidance_rescale) from sp_g[p * sp_g_stride + 0 / 1] and its (sa, sb, c_x0, c_dir, sigma) of the current step from sp_c[(step * P + p) * 8 ..]
     // (step = 0 for the stand-alone operator).  A sample with guidance_scale <= 0 does not read its unconditional row, one with sigma == 0 does not read
     // its noise slice; both kernels are launched whatever the values are, so a captured step serves every table
-    const float* sp_g; const float* sp_c; int sp_g_stride;
+    const float* sp_g = nullptr; const float* sp_c = nullptr; int sp_g_stride = 0;
     // multistep solver, DPM-Solver++(2M) (null x0_hist = off: the DDIM update, the kernel it has always been).  On: x0_hist fp32 [P][n] holds the data
     // prediction x0 of the step before; prev += c_hist * (x0 - x0_hist) after the DDIM expression, then x0_hist = x0 (0 on padded frames).  c_hist is slot 5
     // of the CALL's row coef[step * 8 ..] in the fused sampler, the per-sample table on or off (it depends on the schedule only); in the stand-alone
     // operator it is slot 5 of the sample's row sp_c[p * 8 ..], or hc[5].  c_hist == 0: x0_hist is written, not read
-    float* x0_hist;
+    float* x0_hist = nullptr;
     // start table of the fused sampler (null = off: every sample runs every step, the kernels they have always been).  On: int [P], sample p is HELD while
     // the device step < start[p]: k_cfg_stats returns for it, k_cfg_apply makes no read of pred / noise / x0_hist and no write of latents / x0_hist for it
     // (its workgroups still arrive at `done`), and at step == start[p] its c_hist is 0 (its first step is first-order and does not read the history)
-    const int* start;
+    const int* start = nullptr;
 };
 void launch_cfg_ddim(const CfgDdimArgs& a, float* partial /* [P][64][4] scratch */, hipStream_t st);
 void launch_set_int(int* p, int v, int add, hipStream_t st);  // *p = add ? *p + v : v

@@ -19,9 +19,14 @@ def scale_shift_re(x, scale, shift):
     return (x / scale) - shift
 
 
+def _is_seq(v):
+    """A per-prompt form of a setting (list, tuple, or a tensor with a dimension), not one value for the call."""
+    return isinstance(v, (list, tuple)) or (torch.is_tensor(v) and v.dim() > 0)
+
+
 def _per_prompt(value, n_prompts, name):
     """A per-request setting as one value per prompt (list), or None for the scalar form."""
-    if isinstance(value, (list, tuple)) or (torch.is_tensor(value) and value.dim() > 0):
+    if _is_seq(value):
         vals = [v.item() if torch.is_tensor(v) else v for v in value]
         if len(vals) != n_prompts:
             raise ValueError(f'{len(vals)} values of {name} for {n_prompts} prompts')
@@ -49,7 +54,7 @@ def check_solver(solver, eta):
     if solver not in SOLVERS:
         raise ValueError(f'solver={solver!r}: expected one of {SOLVERS}')
     if solver == 'dpmpp_2m':
-        etas = eta if isinstance(eta, (list, tuple)) or (torch.is_tensor(eta) and eta.dim() > 0) else [eta]
+        etas = eta if _is_seq(eta) else [eta]
         if any(float(e or 0.0) != 0.0 for e in etas):
             raise ValueError(f"solver='dpmpp_2m' is deterministic and takes no step noise: pass eta=0 (got eta={eta!r})")
 
@@ -168,9 +173,8 @@ class LatentSampler:
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
             if getattr(u, '_canvas_on', False):   # the handle outlives the call: an earlier call's canvas goes before this call's tables are set
-                rc = u.lib.ezdit_sampler_set_canvas(u._h, None, 0, 0, 1, C.c_void_p(self.stream.cuda_stream))
-                if rc != -3:   # (EZDIT_E_STATE: the workspace was bound again since, which cleared the table)
-                    _lib.check(rc)
+                # (-3, EZDIT_E_STATE: the workspace was bound again since, which cleared the table and ended the call it belonged to)
+                self._table_call(u.lib.ezdit_sampler_set_canvas, None, 0, 0, 1, ok=(-3,))
                 u._canvas_on = False
             u.bind(B, L, ctx.shape[1], ddim_steps)
             u.prepare_context(ctx, msk)
@@ -188,7 +192,7 @@ class LatentSampler:
                 u.set_lengths(lengths, st)
             else:  # the pair's table first, then the condition embed that is computed from it
                 arr = None if lengths is None else (C.c_int32 * P)(*lengths)
-                _lib.check(u.lib.ezdit_sampler_set_pair_lengths(u._h, arr, 0 if lengths is None else P, st))
+                self._table_call(u.lib.ezdit_sampler_set_pair_lengths, arr, 0 if lengths is None else P)
                 cond = condition.to(dev, torch.float32).expand(P, -1, -1)
                 cond = torch.cat([cond, cond], dim=0) if use_cfg else cond   # src/inference_controlnet.py:78-99: duplicated for the CFG pair
                 controlnet.prepare_condition(cond)
@@ -210,7 +214,7 @@ class LatentSampler:
                 self._start_lens = None if lengths is None else torch.tensor(lengths, dtype=torch.int32).to(dev)
                 _lib.check(u.lib.ezdit_add_noise(_ptr(self._start_clean), _ptr(self.latents), _ptr(self._start_params), float(latent_scale),
                                                  float(latent_shift), _ptr(self._start_lens), L, P, Cc * L, st))
-                _lib.check(u.lib.ezdit_sampler_set_start(u._h, (C.c_int32 * P)(*starts), P, st))
+            self._table_call(u.lib.ezdit_sampler_set_start, (C.c_int32 * P)(*starts), P)
             self.first_step = min(starts)
         if self.canvas is not None and any(b < a + L for a, b in zip(self.canvas[0], self.canvas[0][1:])):   # windows that share frames
             self.set_canvas(*self.canvas)
@@ -221,42 +225,45 @@ class LatentSampler:
         if solver == 'dpmpp_2m':   # after the sample table: the library checks the two against each other
             self.x0_hist = torch.zeros_like(self.latents)
             ch = self.scheduler.multistep_coefficients()
-            with torch.cuda.stream(self.stream):
-                _lib.check(u.lib.ezdit_sampler_set_multistep(u._h, (C.c_float * ddim_steps)(*ch), ddim_steps, _ptr(self.x0_hist),
-                                                             C.c_void_p(self.stream.cuda_stream)))
+            self._table_call(u.lib.ezdit_sampler_set_multistep, (C.c_float * ddim_steps)(*ch), ddim_steps, _ptr(self.x0_hist))
+
+    def _table_call(self, setter, *args, ok=()):
+        """One call of a table setter of the library (include/ezdit.h, "Run-time tables of the step") for this sampler's handle, on the sampler stream.  Its
+        code is checked; one listed in `ok` is handed back instead."""
+        with torch.cuda.stream(self.stream):
+            rc = setter(self.unet._h, *args, C.c_void_p(self.stream.cuda_stream))
+        if rc not in ok:
+            _lib.check(rc)
+        return rc
 
     def set_sample_params(self, guidance_scale=None, guidance_rescale=None, eta=None):
         """Per-sample settings of the call prepare() began: three lists of P values (eta enters as each sample's own DDIM coefficient rows),
         or no argument to go back to the call's scalars.  The captured step reads the table at run time: new values need no re-capture."""
-        u = self.unet
-        st = C.c_void_p(self.stream.cuda_stream)
-        with torch.cuda.stream(self.stream):
-            if guidance_scale is None and guidance_rescale is None and eta is None:
-                _lib.check(u.lib.ezdit_sampler_set_sample_params(u._h, None, None, None, 0, st))
-                return
-            P, n = self.P, self.n_steps
-            vals = [[float(v or 0.0) for v in l] for l in (guidance_scale, guidance_rescale, eta)]
-            if any(len(l) != P for l in vals):
-                raise ValueError(f'per-sample settings need {P} values each')
-            rows = sample_coefficients(self.scheduler, vals[2])
-            gs, gr = (C.c_float * P)(*vals[0]), (C.c_float * P)(*vals[1])
-            arr = (_lib.EzditDdimCoef * (n * P))(*[_lib.EzditDdimCoef(*rows[p][i]) for i in range(n) for p in range(P)])
-            _lib.check(u.lib.ezdit_sampler_set_sample_params(u._h, gs, gr, arr, P, st))
+        setter = self.unet.lib.ezdit_sampler_set_sample_params
+        if guidance_scale is None and guidance_rescale is None and eta is None:
+            self._table_call(setter, None, None, None, 0)
+            return
+        P, n = self.P, self.n_steps
+        vals = [[float(v or 0.0) for v in l] for l in (guidance_scale, guidance_rescale, eta)]
+        if any(len(l) != P for l in vals):
+            raise ValueError(f'per-sample settings need {P} values each')
+        rows = sample_coefficients(self.scheduler, vals[2])
+        gs, gr = (C.c_float * P)(*vals[0]), (C.c_float * P)(*vals[1])
+        arr = (_lib.EzditDdimCoef * (n * P))(*[_lib.EzditDdimCoef(*rows[p][i]) for i in range(n) for p in range(P)])
+        self._table_call(setter, gs, gr, arr, P)
 
     def set_canvas(self, offsets=None, T=0, ramp=1):
         """The canvas table of the call prepare() began: P window offsets, the canvas length and the ramp, or no argument to switch the blend off (independent
         windows).  The captured step reads the offsets at run time: new offsets of the same T and ramp need no re-capture."""
         u = self.unet
-        st = C.c_void_p(self.stream.cuda_stream)
-        with torch.cuda.stream(self.stream):
-            if offsets is None:
-                _lib.check(u.lib.ezdit_sampler_set_canvas(u._h, None, 0, 0, 1, st))
-                u._canvas_on = False
-                return
-            offs = [int(v) for v in offsets]
-            _lib.check(u.lib.ezdit_sampler_set_canvas(u._h, (C.c_int32 * len(offs))(*offs), len(offs), int(T), int(ramp), st))
-            u._canvas_on = True
-            self.canvas = (offs, int(T), int(ramp))
+        if offsets is None:
+            self._table_call(u.lib.ezdit_sampler_set_canvas, None, 0, 0, 1)
+            u._canvas_on = False
+            return
+        offs = [int(v) for v in offsets]
+        self._table_call(u.lib.ezdit_sampler_set_canvas, (C.c_int32 * len(offs))(*offs), len(offs), int(T), int(ramp))
+        u._canvas_on = True
+        self.canvas = (offs, int(T), int(ramp))
 
     def canvas_latents(self):
         """The [1, C, T] canvas of a call prepared with ``canvas=``, assembled from the windows after finish().  With the blend on the windows agree bit for bit
@@ -273,16 +280,14 @@ class LatentSampler:
     def set_cn_scales(self, scales=None):
         """conditioning_scale per sample of the call prepare() began with a ControlNet: a list of P values, or None to go back to the call's scalar.
         The captured step reads the table at run time: new values need no re-capture."""
-        u = self.unet
-        st = C.c_void_p(self.stream.cuda_stream)
-        with torch.cuda.stream(self.stream):
-            if scales is None:
-                _lib.check(u.lib.ezdit_sampler_set_cn_scales(u._h, None, 0, st))
-                return
-            vals = [float(v) for v in scales]
-            if len(vals) != self.P:
-                raise ValueError(f'{len(vals)} conditioning scales for P={self.P} samples')
-            _lib.check(u.lib.ezdit_sampler_set_cn_scales(u._h, (C.c_float * self.P)(*vals), self.P, st))
+        setter = self.unet.lib.ezdit_sampler_set_cn_scales
+        if scales is None:
+            self._table_call(setter, None, 0)
+            return
+        vals = [float(v) for v in scales]
+        if len(vals) != self.P:
+            raise ValueError(f'{len(vals)} conditioning scales for P={self.P} samples')
+        self._table_call(setter, (C.c_float * self.P)(*vals), self.P)
 
     def run(self, n=None, use_graph=True):
         n = self.n_steps - self.first_step if n is None else n
@@ -348,7 +353,7 @@ def sample_coefficients(scheduler, etas):
 
 def _frames_list(audio_frames, n_prompts):
     """audio_frames as one length per prompt, or None for the scalar form."""
-    if isinstance(audio_frames, (list, tuple)) or (torch.is_tensor(audio_frames) and audio_frames.dim() > 0):
+    if _is_seq(audio_frames):
         lens = [int(v) for v in audio_frames]
         if len(lens) != n_prompts:
             raise ValueError(f'{len(lens)} lengths for {n_prompts} prompts')
@@ -402,7 +407,7 @@ def draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n
     slice [canvas_offsets[i], canvas_offsets[i] + L), so the windows share their noise where they share frames.  One window draws what the plain call draws."""
     if canvas_offsets is not None:
         offs = [int(v) for v in canvas_offsets]
-        if isinstance(audio_frames, (list, tuple)) or isinstance(eta, (list, tuple)) or isinstance(random_seed, (list, tuple)) or start_steps is not None:
+        if _is_seq(audio_frames) or _is_seq(eta) or _is_seq(random_seed) or start_steps is not None:
             raise ValueError('a canvas takes one window length, one eta and one seed, and no start steps')
         L = int(audio_frames)
         T = offs[-1] + L
@@ -504,10 +509,10 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
             text_raw = list(text_raw) * n_win
         if len(text_raw) != n_win:
             raise ValueError(f'{len(text_raw)} prompts for a canvas of {n_win} windows: one prompt, or one per window')
-        if isinstance(audio_frames, (list, tuple)) or (torch.is_tensor(audio_frames) and audio_frames.dim() > 0):
+        if _is_seq(audio_frames):
             raise ValueError('a canvas takes one window length (audio_frames)')
         for name, v in (('guidance_scale', guidance_scale), ('guidance_rescale', guidance_rescale), ('eta', eta), ('random_seed', random_seed)):
-            if isinstance(v, (list, tuple)) or (torch.is_tensor(v) and v.dim() > 0):
+            if _is_seq(v):
                 raise ValueError(f'a canvas takes one {name}, not one per window')
         if gt is not None or gt_mask is not None or controlnet is not None or init_latents is not None:
             raise ValueError('a canvas does not combine with gt / gt_mask, a ControlNet or init_latents')
@@ -538,23 +543,19 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
 
         def local(s, e):
             if e == s:   # more ranks than prompts: contribute an empty shard of the common shape
-                ratio = params['autoencoder']['sr'] // params['autoencoder']['latent_sr']
-                return torch.zeros(0, 1, t_all if frames is not None else audio_frames * ratio, device=device)
+                return torch.zeros(0, 1, t_all, device=device)
             sl = lambda t: t if t is None or t.shape[0] == 1 else t[s:e]   # noqa: E731  per-prompt tensors are sliced
             pp = lambda v: list(v[s:e]) if _per_prompt(v, n_all, 'setting') is not None else v   # noqa: E731  ... and so are per-prompt settings
-            if frames is None:
-                return inference(autoencoder, unet, sl(gt), sl(gt_mask), tokenizer, text_encoder, params, noise_scheduler,
-                                 list(text_raw[s:e]), neg_all[s:e], audio_frames, pp(guidance_scale), pp(guidance_rescale), ddim_steps, pp(eta),
-                                 pp(random_seed), device, use_graph, controlnet, sl(condition), pp(conditioning_scale), first_index=s, solver=solver,
-                                 init_latents=sl(init_latents), strength=pp(strength))
-            # mixed lengths: the lengths are sliced with the prompts, per-prompt tensors additionally cut to the shard's own padded length
-            lmax = max(frames[s:e])
-            cut = lambda t: t if t is None else sl(t)[..., :lmax]   # noqa: E731
-            cond = condition if condition is None else sl(condition)[..., :2 * lmax]   # (the control signal has two frames per latent frame)
+            # mixed lengths: the lengths are sliced with the prompts, per-prompt tensors additionally cut to the shard's own padded length (the control
+            # signal has two frames per latent frame).  One length for all: nothing to cut, and the shard comes out at the global duration by itself
+            lmax = None if frames is None else max(frames[s:e])
+            cut = lambda t, per_frame=1: t if t is None else sl(t)[..., :None if lmax is None else per_frame * lmax]   # noqa: E731
             wav = inference(autoencoder, unet, cut(gt), cut(gt_mask), tokenizer, text_encoder, params, noise_scheduler,
-                            list(text_raw[s:e]), neg_all[s:e], frames[s:e], pp(guidance_scale), pp(guidance_rescale), ddim_steps, pp(eta),
-                            pp(random_seed), device, use_graph, controlnet, cond, pp(conditioning_scale), first_index=s, solver=solver,
-                            init_latents=cut(init_latents), strength=pp(strength))
+                            list(text_raw[s:e]), neg_all[s:e], audio_frames if frames is None else frames[s:e], pp(guidance_scale), pp(guidance_rescale),
+                            ddim_steps, pp(eta), pp(random_seed), device, use_graph, controlnet, cut(condition, 2), pp(conditioning_scale), first_index=s,
+                            solver=solver, init_latents=cut(init_latents), strength=pp(strength))
+            if frames is None:
+                return wav
             out = torch.zeros(wav.shape[0], wav.shape[1], t_all, dtype=wav.dtype, device=wav.device)
             out[..., :wav.shape[-1]] = wav
             return out

@@ -113,6 +113,33 @@ size_t ezdit_workspace_bytes(const ezdit_handle* h, int B, int L, int Lc, int n_
 int    ezdit_bind_workspace(ezdit_handle* h, void* dev_ws, size_t bytes, int B, int L, int Lc, int n_slots,
                             ezdit_stream stream);
 
+/* ---- Run-time tables of the step -------------------------------------------------------------- */
+/* Seven setters below hand the step a RUN-TIME TABLE: a small array in the workspace that the kernels of the step read at run time.  One
+ * contract holds for all seven; their own comments say only what is specific to each.
+ *   - A set-up entry point: the values are a HOST array, the call uploads them and waits for `stream`.  EZDIT_E_STATE inside a stream
+ *     capture and before the state the table lives in exists: a bound workspace, or, for a call-scoped table, a sampler call begun on
+ *     it ("ezdit_sampler_begin first").  NULL or a count of 0 switches the table off: bit for bit the call that never set it.
+ *   - A captured step graph serves every set of values: new values into a table that is on keep the graph.  Switching a table on or
+ *     off changes kernel arguments and drops it, and so does a kernel argument that rides with the table.
+ *   - A refused call changes nothing and launches nothing.
+ *   - Scope, and what else switches a table off:
+ *       table (setter)                            graph dropped when                  also cleared by
+ *       lengths (ezdit_set_lengths)               off <-> on                          ezdit_bind_workspace, ezdit_sampler_set_pair_lengths(NULL)
+ *       the ControlNet's half of pair lengths     off <-> on: the graph of every      ezdit_bind_workspace, detach, ezdit_destroy of the backbone,
+ *         (ezdit_sampler_set_pair_lengths)          backbone it is attached to; a       ezdit_set_lengths(NULL) on the ControlNet
+ *                                                   changed table also invalidates
+ *                                                   the condition embed
+ *       ControlNet scales (.._set_cn_scales)      off <-> on                          ezdit_bind_workspace, ezdit_sampler_attach_controlnet,
+ *                                                                                       ezdit_destroy of the ControlNet
+ *       sample settings (.._set_sample_params)    off <-> on                          ezdit_bind_workspace, ezdit_sampler_begin
+ *       multistep (.._set_multistep)              off <-> on, another history buffer  ezdit_bind_workspace, ezdit_sampler_begin
+ *       start (.._set_start)                      off <-> on (also moves the step     ezdit_bind_workspace, ezdit_sampler_begin
+ *                                                   counter: on, min(start_steps);
+ *                                                   off after on, 0)
+ *       canvas (.._set_canvas)                    off <-> on, another T or ramp       ezdit_bind_workspace, ezdit_sampler_begin
+ * ezdit_bind_workspace ends the sampler call as well: ezdit_sampler_run and the call-scoped setters (the last four) return EZDIT_E_STATE
+ * until the next ezdit_sampler_begin, whatever shape was bound. */
+
 /* ---- step-invariant work, hoisted (reference recomputes it every step) ----------------------- */
 /* context_embed + per-block norm_context + cross to_k/to_v + head LayerNorm(k):
  * src/models/udit.py:94-97,295-296; blocks.py:84-85,150; utils/attention.py:128-142.
@@ -136,9 +163,7 @@ int ezdit_set_step(ezdit_handle* h, int step, ezdit_stream stream);
  * `rescale_noise_cfg` takes mean / std over the C * len valid elements, and the input assembly substitutes zeros for padded frames:
  * what the caller leaves there -- NaN included -- is ignored.  Frames >= len of ezdit_forward's output and of the sampler's latents
  * are written as exactly 0.  Padded token rows are still computed (and discarded) by the per-row kernels.
- * The table lives in the workspace and is read by the kernels at run time: a captured step graph serves every set of lengths of the
- * bound (B, L).  A set-up entry point like ezdit_prepare_* / ezdit_sampler_begin: it uploads from host memory and waits for `stream`;
- * refused with EZDIT_E_STATE inside a stream capture and before a workspace is bound.  ezdit_bind_workspace clears the lengths.
+ * A run-time table of the step (contract above), bind-scoped.
  * EZDIT_E_INVALID: a length outside [1, L], n not dividing B.  EZDIT_E_UNSUPPORTED: a ControlNet handle, a backbone with a ControlNet
  * attached (this call can set one of the two tables that must agree: the pair has ezdit_sampler_set_pair_lengths below; clearing with
  * NULL is allowed on either handle); ezdit_forward with cn_skips refuses likewise while lengths are set (the caller's residuals come
@@ -190,20 +215,17 @@ int ezdit_set_cn_scale(ezdit_handle* h, float scale);
  * ezdit_sampler_run return EZDIT_E_STATE until ezdit_prepare_condition has run again.  ezdit_sampler_run also returns EZDIT_E_STATE,
  * naming the mismatch, when the two handles' tables differ (one of them cleared or re-bound behind the pair's back).
  * Detaching (ezdit_sampler_attach_controlnet(h, NULL, ..)) or destroying the backbone clears the ControlNet's table and leaves the
- * backbone's; destroying either handle leaves the other usable.  The captured step reads both tables at run time: new values keep
- * the graph, switching on or off drops it.
- * A set-up entry point: uploads from host memory and waits for `stream`; EZDIT_E_STATE inside a stream capture, before a workspace is
- * bound, without an attached ControlNet, or when the two handles are bound to different (B, L).  EZDIT_E_INVALID as ezdit_set_lengths.
- * A refused call changes nothing. */
+ * backbone's; destroying either handle leaves the other usable.
+ * Two run-time tables of the step (contract above), bind-scoped.  EZDIT_E_STATE also without an attached ControlNet, or when the two
+ * handles are bound to different (B, L).  EZDIT_E_INVALID as ezdit_set_lengths. */
 int ezdit_sampler_set_pair_lengths(ezdit_handle* h, const int32_t* lengths, int n, ezdit_stream stream);
 /* conditioning_scale per sample of the fused sampler: `scales` is a HOST array of n floats, n divides B, batch row b multiplies the
  * attached ControlNet's residuals by scales[b % n] (the rule of the lengths: the CFG pair of a sample shares its scale) instead of the
- * scalar of ezdit_sampler_attach_controlnet; NULL or n = 0 goes back to that scalar, as a later ezdit_sampler_attach_controlnet and
- * ezdit_bind_workspace do.  The table lives at the end of the workspace (ezdit_workspace_bytes grows by 1 KB) and is read by the row
- * kernel at run time, once per token row: new values keep the captured step graph, switching between scalar and table drops it.
- * ezdit_forward with caller-provided residuals never reads the table (ezdit_set_cn_scale is its scale).
- * A set-up entry point like the one above.  EZDIT_E_STATE: inside a stream capture, no workspace, no ControlNet attached.
- * EZDIT_E_INVALID: n not dividing B, a non-finite value.  A refused call changes nothing. */
+ * scalar of ezdit_sampler_attach_controlnet; NULL or n = 0 goes back to that scalar.  The table lives at the end of the workspace
+ * (ezdit_workspace_bytes grows by 1 KB) and is read by the row kernel once per token row.  ezdit_forward with caller-provided residuals
+ * never reads it (ezdit_set_cn_scale is its scale).
+ * A run-time table of the step (contract above), bind-scoped.  EZDIT_E_STATE also without an attached ControlNet.
+ * EZDIT_E_INVALID: n not dividing B, a non-finite value. */
 int ezdit_sampler_set_cn_scales(ezdit_handle* h, const float* scales, int n, ezdit_stream stream);
 
 /* ---- sampler: CFG + rescale + DDIM, src/inference.py:70-100 + diffusers DDIMScheduler.step ---- */
@@ -246,15 +268,13 @@ int ezdit_sampler_run(ezdit_handle* h, int n, int use_graph, ezdit_stream stream
  *   sigma == 0 at a step     sample p draws no noise at that step: its slice of dev_noise is not read (it may hold NaN).  dev_noise of
  *                            ezdit_sampler_begin is NULL only when every sample has eta <= 0
  * Per-sample lengths (ezdit_set_lengths) work together with the table.  The table lives at the END of the workspace and is read by the
- * last two kernels of the step at run time: a captured step graph serves every set of values; only switching the table on or off
- * drops the graph.  With the table on both kernels are launched whatever the values are.  A backbone with a ControlNet attached
- * accepts the table.  ezdit_workspace_bytes is at most n_slots * (B / 2 + 1) * 32 + 2048 bytes larger for it: room for B / 2 + 1
- * samples, the B / 2 of a CFG batch.
- * A set-up entry point like ezdit_set_lengths: it uploads from host memory and waits for `stream`; refused with EZDIT_E_STATE inside a
- * stream capture and before ezdit_sampler_begin, which clears the table (as ezdit_bind_workspace does).
+ * last two kernels of the step; with the table on both kernels are launched whatever the values are.  A backbone with a ControlNet
+ * attached accepts the table.  ezdit_workspace_bytes is at most n_slots * (B / 2 + 1) * 32 + 2048 bytes larger for it: room for
+ * B / 2 + 1 samples, the B / 2 of a CFG batch.
+ * A run-time table of the step (contract above), call-scoped.
  * EZDIT_E_INVALID: P is not the P of ezdit_sampler_begin; only some of the arrays given; a non-finite value; guidance_scale[p] > 0 on a
  * sampler begun without CFG rows (B == P); sigma != 0 on a sampler begun without noise.  EZDIT_E_UNSUPPORTED: P > B / 2 + 1 (a batch
- * begun without CFG rows of more than two samples).  A refused call changes nothing. */
+ * begun without CFG rows of more than two samples). */
 int ezdit_sampler_set_sample_params(ezdit_handle* h, const float* guidance_scale, const float* guidance_rescale,
                                     const ezdit_ddim_coef* coefs, int P, ezdit_stream stream);
 
@@ -269,23 +289,22 @@ int ezdit_cfg_ddim_step_per_sample(const float* dev_pred, float* dev_latents, co
 /* ---- multistep solver: DPM-Solver++(2M) in the fused sampler step ------------------------------------------------------------- */
 /* For v-prediction the DDIM update at eta = 0 is first-order DPM-Solver++; the 2M solver adds one term in the data prediction of the
  * step before:   x0_i = sa x - sb v,  eps_i = sa v + sb x  (as ezdit_ddim_coef),   x_next = c_x0 x0_i + c_dir eps_i + c_hist_i (x0_i - x0_{i-1}).
- * After ezdit_sampler_begin (which switches it off, as ezdit_bind_workspace does), c_hist is a HOST array of n_steps values (the n_steps of
+ * After ezdit_sampler_begin, c_hist is a HOST array of n_steps values (the n_steps of
  * ezdit_sampler_begin; ezaudio_amd/scheduler.py multistep_coefficients) and dev_x0_hist a caller-owned fp32 [P][C][L] device buffer that
  * must live as long as the sampler runs: the last kernel of every step reads x0_{i-1} from it and writes x0_i back (0 on the padded
  * frames of ezdit_set_lengths).  c_hist NULL switches it off: the DDIM step again, bit for bit.
  *   c_hist_i == 0     step i is first-order and does NOT read the history: the buffer may hold anything (NaN included) when the run
  *                     starts, c_hist_0 being 0 by construction.  The history is still written.
- * The values go into a spare slot of the coefficient rows already in the workspace (ezdit_workspace_bytes is unchanged) and are read
- * at run time: new values keep the captured step graph, switching the solver on or off (or another history buffer) drops it.  c_hist
+ * The values go into a spare slot of the coefficient rows already in the workspace (ezdit_workspace_bytes is unchanged); the history
+ * buffer is a kernel argument.  c_hist
  * depends on the schedule only, so with a per-sample table (ezdit_sampler_set_sample_params) every sample takes the call's c_hist_i;
  * per-sample lengths, per-sample guidance and rescale, editing (gt / gt_mask) and an attached ControlNet work unchanged.
- * A set-up entry point like ezdit_set_lengths: it uploads from host memory and waits for `stream`; refused with EZDIT_E_STATE inside a
- * stream capture and before ezdit_sampler_begin.  While it is on, ezdit_set_step(k) with k != 0 is refused with EZDIT_E_STATE (the
+ * A run-time table of the step (contract above), call-scoped.  While it is on, ezdit_set_step(k) with k != 0 is refused with EZDIT_E_STATE (the
  * history would not be step k - 1's; k = 0 is fine, c_hist_0 = 0).  With a start table (ezdit_sampler_set_start) the one accepted k is min(start_steps)
  * instead: that step is first-order for every sample active at it.
  * EZDIT_E_INVALID: n_steps is not the sampler's; a non-finite value; c_hist without dev_x0_hist; a sampler begun with noise, or a
  * per-sample table with any sigma != 0 (the solver is deterministic; ezdit_sampler_set_sample_params in turn refuses sigma != 0 while
- * the solver is on).  A refused call changes nothing. */
+ * the solver is on). */
 int ezdit_sampler_set_multistep(ezdit_handle* h, const float* c_hist, int n_steps, float* dev_x0_hist, ezdit_stream stream);
 
 /* The multistep form of ezdit_cfg_ddim_step_per_sample, for callers that keep their own loop: dev_params[p][7], the spare zero of that
@@ -316,16 +335,14 @@ int ezdit_add_noise(const float* dev_clean, float* dev_latents, const float* dev
  * as padded frames are computed) and the last two kernels of the step skip it -- no read of its prediction, noise slice or history,
  * no write of its latents or history: the latents keep their bits.  From start_steps[p] on it is updated as in a run that begins
  * there alone; with the multistep solver on, step start_steps[p] is first-order for it (c_hist = 0, the history is written, not read).
- * NULL or P = 0 clears the table (and, if it was on, puts the step counter back to 0), as ezdit_sampler_begin and ezdit_bind_workspace do.
- * The table lives at the END of the workspace (ezdit_workspace_bytes grows by 1 KB) and is read at run time: new values keep the
- * captured step graph, switching it on or off drops it.  Per-sample lengths (plain and pair), the per-sample settings table, the
+ * NULL or P = 0 clears the table (and, if it was on, puts the step counter back to 0).
+ * The table lives at the END of the workspace (ezdit_workspace_bytes grows by 1 KB).  Per-sample lengths (plain and pair), the per-sample settings table, the
  * multistep solver (set in either order with it), gt / gt_mask and an attached ControlNet work unchanged; none of them is touched.
  * While the table is on, ezdit_set_step(k) is accepted only for k == min(start_steps) -- a rewind to the run's own beginning, also with
  * the multistep solver on (that step is first-order for every sample active at it); any other k is EZDIT_E_STATE.  With it off
  * ezdit_set_step keeps its rules.
- * A set-up entry point like ezdit_set_lengths: it uploads from host memory and waits for `stream`; EZDIT_E_STATE inside a stream
- * capture and before ezdit_sampler_begin.  EZDIT_E_INVALID: P is not the P of ezdit_sampler_begin; a value outside [0, n_steps).
- * A refused call changes nothing. */
+ * A run-time table of the step (contract above), call-scoped.  EZDIT_E_INVALID: P is not the P of ezdit_sampler_begin; a value outside
+ * [0, n_steps). */
 int ezdit_sampler_set_start(ezdit_handle* h, const int32_t* start_steps, int P, ezdit_stream stream);
 
 /* ---- long-form canvas: the P samples of one call are overlapping windows of one long latent, blended inside the step ------------------- */
@@ -343,17 +360,15 @@ int ezdit_canvas_blend(float* dev_latents, const int32_t* dev_offsets, int P, in
 /* After ezdit_sampler_begin, the P samples of the call are the windows of a canvas of T frames: `offsets` is a HOST array of P first frames.
  * While the table is on, every step ends with ezdit_canvas_blend on the updated latents (one more kernel behind the update, on the same
  * stream: one more node of the captured step), so the windows agree on their shared frames after every step and the canvas can be read off
- * the windows when the run ends.  NULL or P = 0 switches it off, as ezdit_sampler_begin and ezdit_bind_workspace do; while off the step
- * issues exactly the launches it issues without this call.  The table lives at the END of the workspace (ezdit_workspace_bytes grows by
- * 1 KB) and is read at run time: new offsets keep the captured step graph; switching on or off, another T or another ramp drops it.
+ * the windows when the run ends.  While off the step issues exactly the launches it issues without this call.  The table lives at the
+ * END of the workspace (ezdit_workspace_bytes grows by 1 KB); T and the ramp are kernel arguments.
  * The per-sample settings table and the multistep solver work with it (the blend acts on the updated latents; the history of data
  * predictions stays per window and is not blended).
- * A set-up entry point like ezdit_set_lengths: it uploads from host memory and waits for `stream`; EZDIT_E_STATE inside a stream capture
- * and before ezdit_sampler_begin.  EZDIT_E_INVALID unless P is the P of ezdit_sampler_begin, offsets[0] == 0, the offsets ascend strictly,
+ * A run-time table of the step (contract above), call-scoped.  EZDIT_E_INVALID unless P is the P of ezdit_sampler_begin, offsets[0] == 0, the offsets ascend strictly,
  * offsets[i + 1] <= offsets[i] + L (no uncovered frame), offsets[P - 1] + L == T and ramp >= 1.  EZDIT_E_UNSUPPORTED with a length table
  * (ezdit_set_lengths), a start table, gt / gt_mask or an attached ControlNet -- long edits, long audio-to-audio and long ControlNet runs
  * are not implemented; while the canvas is on, ezdit_set_lengths, ezdit_sampler_set_start and ezdit_sampler_attach_controlnet (with a
- * ControlNet) are refused the same way.  A refused call changes nothing and launches nothing. */
+ * ControlNet) are refused the same way. */
 int ezdit_sampler_set_canvas(ezdit_handle* h, const int32_t* offsets, int P, int T, int ramp, ezdit_stream stream);
 
 /* ---- Oobleck VAE decoder building blocks (src/modules/stable_vae/models/autoencoders.py:38-61,82-113,149-190) --------
