@@ -13,7 +13,7 @@ import torch
 
 from .config import configs, controlnet_configs, load_yaml_with_includes
 from .denoiser import MaskDiT
-from .sampler import canvas_windows, check_solver, inference, inference_controlnet
+from .sampler import canvas_windows, check_solver, inference, inference_controlnet, loop_windows
 from .scheduler import DDIMScheduler
 
 MAX_SEED = np.iinfo(np.int32).max
@@ -161,6 +161,44 @@ class EzAudio:
             random_seed = random.randint(0, MAX_SEED)
         pred = inference(self.autoencoder, self.unet, None, None, self.tokenizer, self.text_encoder, self.params, self.noise_scheduler, prompts, None,
                          frames, guidance_scale, guidance_rescale, ddim_steps, eta, random_seed, self.device, canvas_offsets=offsets, solver=solver)
+        return self.params['autoencoder']['sr'], pred.cpu().numpy().squeeze(0).squeeze(0)
+
+    def generate_loop(self, text, length, window=10, overlap=2.5, guidance_scale=5, guidance_rescale=0.75, ddim_steps=100, eta=1,
+                      random_seed=None, randomize_seed=False, solver='ddim', decode_context=None):
+        """A clip of `length` seconds that runs from its end into its own beginning: ``np.tile(waveform, k)`` is the loop.  The latent canvas is a RING covered
+        by windows of `window` seconds, each sharing at least `overlap` seconds with the next one around the ring, the last with the first
+        (sampler.loop_windows chooses the fewest such windows, at least two, spread evenly); all windows are denoised together as the prompts of ONE batched
+        sampler call, the shared frames are cross-faded inside every step, and the ring is decoded in one call with wrapped context in place of the VAE's zero
+        halos (sampler.decode_circular; `decode_context` latent frames, None = the decoder's receptive field).  Returns (sr, waveform [T]).
+        `text` is one prompt for the whole loop, or a list with one prompt per window.  The settings are scalars.  Any `length` of at least 2 latent frames
+        is valid: a loop no longer than the window is two windows of its own length, half a turn apart.
+        Audio quality on the real checkpoints (whether the seam is audible, the choice of overlap and ramp) is unmeasured."""
+        latent_sr = self.params['autoencoder']['latent_sr']
+        if isinstance(length, (list, tuple)):
+            raise ValueError('generate_loop makes one clip: length is one duration in seconds')
+        ring, win, shared = int(round(length * latent_sr)), int(round(window * latent_sr)), int(round(overlap * latent_sr))
+        if shared < 0 or shared >= win:
+            raise ValueError(f'overlap={overlap} outside [0, window = {window})')
+        if ring <= win:   # two windows of the loop's own length share half a turn with each other, whatever was asked of the full window
+            shared = min(shared, ring // 2)
+        offsets, frames = loop_windows(ring, win, shared)
+        n_win = len(offsets)
+        if not isinstance(text, str) and len(text) != n_win:
+            raise ValueError(f'{len(text)} prompts for {n_win} windows (a loop of {length} s in windows of {window} s that share {overlap} s): one prompt, or one per window')
+        check_solver(solver, eta)
+        for name, v in (('guidance_scale', guidance_scale), ('guidance_rescale', guidance_rescale), ('eta', eta), ('random_seed', random_seed),
+                        ('ddim_steps', ddim_steps)):
+            if isinstance(v, (list, tuple)):
+                raise ValueError(f'generate_loop takes one {name} for the whole clip')
+        prompts = [text] * n_win if isinstance(text, str) else list(text)
+        if all(t == '' for t in prompts):
+            guidance_scale = None
+            print('empty input')
+        if randomize_seed:
+            random_seed = random.randint(0, MAX_SEED)
+        pred = inference(self.autoencoder, self.unet, None, None, self.tokenizer, self.text_encoder, self.params, self.noise_scheduler, prompts, None,
+                         frames, guidance_scale, guidance_rescale, ddim_steps, eta, random_seed, self.device, canvas_offsets=offsets, canvas_loop=ring,
+                         decode_context=decode_context, solver=solver)
         return self.params['autoencoder']['sr'], pred.cpu().numpy().squeeze(0).squeeze(0)
 
     def _load_edit_clip(self, gt_file):

@@ -131,8 +131,11 @@ struct ezdit_handle {
     int start_min = 0;
     // [P] first canvas frame of each window (ezdit_sampler_set_canvas): the P windows of the call overlap on a canvas of canvas_T frames and k_canvas_blend, one more
     // launch behind the update, averages the shared frames (T and the ramp are its arguments).  Off: the step issues the launches it has always issued
+    // canvas_loop (ezdit_sampler_set_canvas_loop): the same table read as a ring of canvas_T frames, blended by k_canvas_blend_loop -- another kernel, so the
+    // two setters replacing each other drop the graph
     Table<int> canvas;
     int canvas_T = 0, canvas_ramp = 1;
+    bool canvas_loop = false;
 
     int launches = 0;
     bool is_cn = false;          // ControlNet variant (cfg.controlnet)
@@ -780,7 +783,7 @@ void reset_call_state(ezdit_handle* h) {
     h->sp.set(h, false);
     h->coef.set(h, false); h->ms_hist = nullptr;
     h->start.set(h, false); h->start_min = 0;
-    h->canvas.set(h, false);
+    h->canvas.set(h, false); h->canvas_loop = false;
 }
 
 // ... bind-scoped ones, and the sampler call itself, belong to one binding of the workspace: a new one zeroes the device arrays and may have another shape, so
@@ -1659,7 +1662,7 @@ static int sampler_step(ezdit_handle* h, hipStream_t st) {
     if (h->canvas.on) {   // long-form canvas: the windows' shared frames are averaged on the updated latents (x0_hist stays per window)
         CanvasBlendArgs cb;
         cb.latents = h->latents; cb.off = h->canvas.dev; cb.P = h->P; cb.C = h->C; cb.L = h->L; cb.T = h->canvas_T; cb.ramp = h->canvas_ramp;
-        launch_canvas_blend(cb, st);
+        if (h->canvas_loop) launch_canvas_blend_loop(cb, st); else launch_canvas_blend(cb, st);
         h->launches += 1;
     }
     const hipError_t e = hipGetLastError();
@@ -1776,31 +1779,56 @@ int ezdit_canvas_blend(float* latents, const int32_t* offsets, int P, int C, int
     return hook_launch("k_canvas_blend", "", [&] { launch_canvas_blend(a, (hipStream_t)stream); return 0; });
 }
 
-int ezdit_sampler_set_canvas(ezdit_handle* h, const int32_t* offsets, int P, int T, int ramp, ezdit_stream stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = setter_checks(h, "ezdit_sampler_set_canvas", Needs::Begun, st)) return rc;
-    if (!offsets || P == 0) {   // off: independent windows again
-        h->canvas.set(h, false);
+// The canvas table has two setters: the line (ezdit_sampler_set_canvas: the last window ends the canvas) and the ring (ezdit_sampler_set_canvas_loop: the last
+// window starts inside the ring and reaches or passes its end, L <= T).  One slot, one lifetime; the form picks the kernel, so line <-> ring drops the graph.
+static int set_canvas_table(ezdit_handle* h, const char* who, const int32_t* offsets, int P, int T, int ramp, bool loop, hipStream_t st) {
+    if (int rc = setter_checks(h, who, Needs::Begun, st)) return rc;
+    if (!offsets || P == 0) {   // off: independent windows again (whichever setter switched the table on)
+        h->canvas.set(h, false); h->canvas_loop = false;
         return EZDIT_OK;
     }
     const int L = h->L;
     if (P != h->P) return fail(EZDIT_E_INVALID, "P = %d, the sampler was begun with P = %d", P, h->P);
     if (ramp < 1) return fail(EZDIT_E_INVALID, "ramp = %d: at least 1 (the plain mean)", ramp);
-    if (offsets[0] != 0) return fail(EZDIT_E_INVALID, "offsets[0] = %d: the first window starts the canvas", (int)offsets[0]);
+    if (loop && L > T) return fail(EZDIT_E_INVALID, "T = %d below the window length %d: a window holds a ring frame at most once", T, L);
+    if (offsets[0] != 0) return fail(EZDIT_E_INVALID, "offsets[0] = %d: the first window starts the %s", (int)offsets[0], loop ? "ring" : "canvas");
     for (int i = 0; i + 1 < P; ++i) {
         if (offsets[i + 1] <= offsets[i]) return fail(EZDIT_E_INVALID, "offsets[%d] = %d is not above offsets[%d] = %d", i + 1, (int)offsets[i + 1], i, (int)offsets[i]);
         if ((long)offsets[i + 1] > (long)offsets[i] + L)
             return fail(EZDIT_E_INVALID, "offsets[%d] = %d leaves a gap behind window %d, which ends at frame %ld", i + 1, (int)offsets[i + 1], i, (long)offsets[i] + L);
     }
-    if ((long)offsets[P - 1] + L != (long)T) return fail(EZDIT_E_INVALID, "T = %d, the last window ends at frame %ld", T, (long)offsets[P - 1] + L);
+    const long end = (long)offsets[P - 1] + L;
+    if (!loop && end != (long)T) return fail(EZDIT_E_INVALID, "T = %d, the last window ends at frame %ld", T, end);
+    if (loop && offsets[P - 1] >= T) return fail(EZDIT_E_INVALID, "offsets[%d] = %d: the last window starts inside the ring of T = %d frames", P - 1, (int)offsets[P - 1], T);
+    if (loop && end < (long)T) return fail(EZDIT_E_INVALID, "T = %d: the last window ends at frame %ld and leaves a gap at the wrap", T, end);
     if (h->lens.on) return fail(EZDIT_E_UNSUPPORTED, "a canvas with per-sample lengths (ezdit_set_lengths): its windows have one length");
     if (h->start.on) return fail(EZDIT_E_UNSUPPORTED, "a canvas with a start table (ezdit_sampler_set_start)");
     if (h->s_gt) return fail(EZDIT_E_UNSUPPORTED, "a canvas with gt / gt_mask: long edits are not implemented");
     if (h->cn) return fail(EZDIT_E_UNSUPPORTED, "a canvas with a ControlNet attached");
     if (int rc = upload_table(h->canvas, std::vector<int>(offsets, offsets + P), st)) return rc;
-    h->canvas.set(h, true, T != h->canvas_T || ramp != h->canvas_ramp);   // (T and the ramp are kernel arguments)
-    h->canvas_T = T; h->canvas_ramp = ramp;
+    h->canvas.set(h, true, T != h->canvas_T || ramp != h->canvas_ramp || loop != h->canvas_loop);   // (T and the ramp are kernel arguments; the other form is another kernel)
+    h->canvas_T = T; h->canvas_ramp = ramp; h->canvas_loop = loop;
     return EZDIT_OK;
+}
+
+int ezdit_sampler_set_canvas(ezdit_handle* h, const int32_t* offsets, int P, int T, int ramp, ezdit_stream stream) {
+    return set_canvas_table(h, "ezdit_sampler_set_canvas", offsets, P, T, ramp, false, (hipStream_t)stream);
+}
+
+int ezdit_canvas_blend_loop(float* latents, const int32_t* offsets, int P, int C, int L, int T, int ramp, ezdit_stream stream) {
+    if (!latents || !offsets) return fail(EZDIT_E_INVALID, "null argument");
+    if (P < 1 || C < 1 || L < 1 || C > 65535) return fail(EZDIT_E_INVALID, "P = %d, C = %d, L = %d", P, C, L);
+    if (ramp < 1) return fail(EZDIT_E_INVALID, "ramp = %d: at least 1 (the plain mean)", ramp);
+    // the table is on the device and this call does not wait for it: T is checked against what any valid table gives
+    if (L > T) return fail(EZDIT_E_INVALID, "L = %d above T = %d: a window holds a ring frame at most once", L, T);
+    if ((long)T > (long)P * L) return fail(EZDIT_E_INVALID, "T = %d: %d windows of %d frames cover at most %ld frames", T, P, L, (long)P * L);
+    CanvasBlendArgs a;
+    a.latents = latents; a.off = offsets; a.P = P; a.C = C; a.L = L; a.T = T; a.ramp = ramp;
+    return hook_launch("k_canvas_blend_loop", "", [&] { launch_canvas_blend_loop(a, (hipStream_t)stream); return 0; });
+}
+
+int ezdit_sampler_set_canvas_loop(ezdit_handle* h, const int32_t* offsets, int P, int T, int ramp, ezdit_stream stream) {
+    return set_canvas_table(h, "ezdit_sampler_set_canvas_loop", offsets, P, T, ramp, true, (hipStream_t)stream);
 }
 
 int ezdit_sampler_set_sample_params(ezdit_handle* h, const float* guidance_scale, const float* guidance_rescale, const ezdit_ddim_coef* coefs, int P,

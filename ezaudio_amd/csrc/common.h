@@ -402,6 +402,8 @@ struct CanvasBlendArgs {  // long-form canvas: the P windows of one call are ove
     int ramp;             // weight of local frame r: min(r + 1, L - r, ramp) -- 1: the plain mean; the overlap: a linear cross-fade
 };
 void launch_canvas_blend(const CanvasBlendArgs& a, hipStream_t st);
+// the same arguments read as a ring of T frames (seamless loops): window p's local frame r is ring frame (off[p] + r) mod T, L <= T, off[P - 1] + L >= T
+void launch_canvas_blend_loop(const CanvasBlendArgs& a, hipStream_t st);
 struct Conv1dArgs {  // out[b][co][lo] = act(bias[co] + sum_{ci,k} w[co][ci][k] * x[b][ci][lo*stride + k - pad]); fp32
     const float* x; const float* w; const float* b; float* out;
     int B, Cin, Cout, Lin, Lout, ksize, stride, pad, act;  // act 1 = SiLU

@@ -665,6 +665,39 @@ __global__ __launch_bounds__(256) void k_canvas_blend(CanvasBlendArgs a) {
     }
 }
 
+// The canvas as a ring of T frames (seamless loops): window p holds the ring frames (off[p] + r) mod T, r in [0, L), L <= T, so it holds a ring frame at most
+// once and the last window runs into the first.  The holders of j need not be one range of windows any more (window 0 and window P - 1 meet at the wrap): every
+// pass walks the windows from the lowest holder to the highest and repeats the range test, which is also what keeps every access inside window p's row whatever
+// the device table holds.  Same ownership, same order of the sum and same arithmetic as k_canvas_blend, which a table without wrap overlap reproduces bit for
+// bit.  The thread index runs along j: a wave's accesses are consecutive floats of a window row except at the one wrap point of that window.
+__global__ __launch_bounds__(256) void k_canvas_blend_loop(CanvasBlendArgs a) {
+    const int j = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
+    if (j >= a.T) return;
+    int lo = a.P, hi = -1;
+    for (int p = 0; p < a.P; ++p) {
+        long r = (long)j - a.off[p];
+        if (r < 0) r += a.T;
+        if (r >= 0 && r < a.L) { if (p < lo) lo = p; hi = p; }
+    }
+    if (hi <= lo) return;   // one holder, or none
+    float num = 0.f, den = 0.f;
+    for (int p = lo; p <= hi; ++p) {
+        long r = (long)j - a.off[p];
+        if (r < 0) r += a.T;
+        if (r < 0 || r >= a.L) continue;
+        const int ri = (int)r;
+        const float w = (float)min(min(ri + 1, a.L - ri), a.ramp);
+        num += w * a.latents[((long)p * a.C + c) * a.L + ri];
+        den += w;
+    }
+    const float v = num / den;
+    for (int p = lo; p <= hi; ++p) {
+        long r = (long)j - a.off[p];
+        if (r < 0) r += a.T;
+        if (r >= 0 && r < a.L) a.latents[((long)p * a.C + c) * a.L + r] = v;
+    }
+}
+
 // small direct Conv1d in fp32 for the ControlNet condition embed (controlnet.py:15-39,65-84): 4 tiny layers, once per call
 __global__ __launch_bounds__(256) void k_conv1d(Conv1dArgs a) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -778,6 +811,9 @@ void launch_add_noise(const AddNoiseArgs& a, hipStream_t st) {
 
 void launch_canvas_blend(const CanvasBlendArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(k_canvas_blend, dim3((a.T + 255) / 256, a.C), dim3(256), 0, st, a);
+}
+void launch_canvas_blend_loop(const CanvasBlendArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(k_canvas_blend_loop, dim3((a.T + 255) / 256, a.C), dim3(256), 0, st, a);
 }
 
 // ---- LayerNorm algebra tables (common.h, GemmArgs.z*): G' = g W^T and C' = c W^T (+ bias) for every modulation slot.  The gain / shift

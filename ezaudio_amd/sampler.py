@@ -71,7 +71,7 @@ class LatentSampler:
     def prepare(self, text, text_mask, uncond_text, uncond_mask, init_noise, step_noises, guidance_scale,
                 guidance_rescale, ddim_steps, eta, gt=None, gt_mask=None, controlnet=None, condition=None,
                 conditioning_scale=1.0, lengths=None, init_latents=None, start_steps=None, latent_scale=1.0, latent_shift=0.0, canvas=None,
-                solver='ddim'):
+                canvas_loop=None, solver='ddim'):
         """``lengths`` (list of P ints): init_noise / step_noises / gt / gt_mask are padded to L = max(lengths) frames and sample p is valid on
         [0, lengths[p]) -- its final latent is what a call with that sample alone at its own length gives, zero beyond (include/ezdit.h
         ezdit_set_lengths).  With a ControlNet the table goes to the attached pair (ezdit_sampler_set_pair_lengths) and ``condition`` is
@@ -99,7 +99,12 @@ class LatentSampler:
         [offsets[p], offsets[p] + L) (canvas_windows() chooses such offsets; draw_noises(canvas_offsets=) slices one canvas noise for them).  Every step then
         ends by averaging the frames that windows share, with the weights min(r + 1, L - r, ramp) of the local frame r (ezdit_sampler_set_canvas), and
         canvas_latents() reads the [1, C, T] canvas off the windows after finish().  Not with lengths, gt / gt_mask, a ControlNet or init_latents.  A canvas of
-        one window, or one whose windows do not overlap, calls nothing new: the same bits as without the argument."""
+        one window, or one whose windows do not overlap, calls nothing new: the same bits as without the argument.
+
+        ``canvas_loop=(offsets, T, ramp)`` (seamless loops; not together with ``canvas``): the canvas is a RING of T >= L frames, window p holding the frames
+        (offsets[p] + r) mod T for r in [0, L), so the last window runs into the first (loop_windows() chooses such offsets; draw_noises(canvas_loop=) cuts
+        one ring noise for them).  The step ends with the wrap blend (ezdit_sampler_set_canvas_loop: the same table as ``canvas``, the same refusals), and
+        canvas_latents() reads the [1, C, T] ring, whose last frame continues into its first."""
         check_solver(solver, eta)
         if (init_latents is None) != (start_steps is None):
             raise ValueError('init_latents and start_steps must be given together')
@@ -146,6 +151,17 @@ class LatentSampler:
             if lengths is not None or gt is not None or controlnet is not None or init_latents is not None:
                 raise ValueError('a canvas does not combine with lengths, gt / gt_mask, a ControlNet or init_latents')
             self.canvas = (offs, T, ramp)
+        self.loop = False
+        if canvas_loop is not None:
+            if canvas is not None:
+                raise ValueError('canvas and canvas_loop are two forms of one table: give one')
+            offs, T, ramp = [int(v) for v in canvas_loop[0]], int(canvas_loop[1]), int(canvas_loop[2])
+            check_canvas_loop(offs, L, T, ramp)
+            if len(offs) != P:
+                raise ValueError(f'{len(offs)} loop offsets for P={P} windows')
+            if lengths is not None or gt is not None or controlnet is not None or init_latents is not None:
+                raise ValueError('a loop does not combine with lengths, gt / gt_mask, a ControlNet or init_latents')
+            self.canvas, self.loop = (offs, T, ramp), True
         self.scheduler.set_timesteps(ddim_steps)
         ts = [int(t) for t in self.scheduler.timesteps]
         coefs = self.scheduler.ddim_coefficients(eta)
@@ -216,7 +232,10 @@ class LatentSampler:
                                                  float(latent_shift), _ptr(self._start_lens), L, P, Cc * L, st))
             self._table_call(u.lib.ezdit_sampler_set_start, (C.c_int32 * P)(*starts), P)
             self.first_step = min(starts)
-        if self.canvas is not None and any(b < a + L for a, b in zip(self.canvas[0], self.canvas[0][1:])):   # windows that share frames
+        if self.loop:
+            if P > 1:   # (one window that is the whole ring shares no frame with anybody)
+                self.set_canvas_loop(*self.canvas)
+        elif self.canvas is not None and any(b < a + L for a, b in zip(self.canvas[0], self.canvas[0][1:])):   # windows that share frames
             self.set_canvas(*self.canvas)
         if table is not None:
             self.set_sample_params(*table)
@@ -263,16 +282,32 @@ class LatentSampler:
         offs = [int(v) for v in offsets]
         self._table_call(u.lib.ezdit_sampler_set_canvas, (C.c_int32 * len(offs))(*offs), len(offs), int(T), int(ramp))
         u._canvas_on = True
-        self.canvas = (offs, int(T), int(ramp))
+        self.canvas, self.loop = (offs, int(T), int(ramp)), False
+
+    def set_canvas_loop(self, offsets=None, T=0, ramp=1):
+        """set_canvas for the ring (ezdit_sampler_set_canvas_loop): the two replace each other, no argument on either switches the blend off."""
+        u = self.unet
+        if offsets is None:
+            self._table_call(u.lib.ezdit_sampler_set_canvas_loop, None, 0, 0, 1)
+            u._canvas_on = False
+            return
+        offs = [int(v) for v in offsets]
+        self._table_call(u.lib.ezdit_sampler_set_canvas_loop, (C.c_int32 * len(offs))(*offs), len(offs), int(T), int(ramp))
+        u._canvas_on = True
+        self.canvas, self.loop = (offs, int(T), int(ramp)), True
 
     def canvas_latents(self):
-        """The [1, C, T] canvas of a call prepared with ``canvas=``, assembled from the windows after finish().  With the blend on the windows agree bit for bit
-        on the frames they share; the lowest window is the one copied."""
+        """The [1, C, T] canvas of a call prepared with ``canvas=`` or ``canvas_loop=``, assembled from the windows after finish().  With the blend on the
+        windows agree bit for bit on the frames they share; the lowest window is the one copied.  A ring is cut at the first window's first frame."""
         if self.canvas is None:
-            raise ValueError('prepare(canvas=...) first')
+            raise ValueError('prepare(canvas=...) or prepare(canvas_loop=...) first')
         offs, T, _ = self.canvas
         P, Cc, L = self.latents.shape
         out = torch.empty((1, Cc, T), dtype=self.latents.dtype, device=self.latents.device)
+        if self.loop:
+            for p in reversed(range(P)):
+                out[0, :, _ring(offs[p], L, T, out.device)] = self.latents[p]
+            return out
         for p in reversed(range(P)):
             out[0, :, offs[p]:offs[p] + L] = self.latents[p]
         return out
@@ -327,6 +362,51 @@ def check_canvas(offsets, L, T, ramp):
         raise ValueError(f'canvas ramp {ramp}: at least 1')
 
 
+def _ring(offset, L, T, device):
+    """The ring frames (offset + r) mod T, r in [0, L), as an index tensor."""
+    return (torch.arange(L, device=device) + int(offset)) % int(T)
+
+
+def loop_overlaps(offsets, L, T):
+    """Frames that each window's tail shares with the head of its cyclic successor, the last window's with the first window's: L minus the step to it."""
+    return [a + L - b for a, b in zip(offsets, list(offsets[1:]) + [offsets[0] + T])]
+
+
+def check_canvas_loop(offsets, L, T, ramp):
+    """The rules of ezdit_sampler_set_canvas_loop, on the host: a window no longer than the ring, first offset 0, strictly ascending, no uncovered frame
+    between neighbours or at the wrap, the last window starts inside the ring."""
+    if L < 1 or L > T:
+        raise ValueError(f'a ring of {T} frames in windows of {L}: a window holds a ring frame at most once')
+    if not offsets or offsets[0] != 0:
+        raise ValueError(f'loop offsets {offsets}: the first window starts at frame 0')
+    for a, b in zip(offsets, offsets[1:]):
+        if b <= a or b > a + L:
+            raise ValueError(f'loop offsets {offsets}: each window starts behind the one before and no later than its end (window length {L})')
+    if offsets[-1] >= T:
+        raise ValueError(f'ring of {T} frames: the last window starts at frame {offsets[-1]}')
+    if offsets[-1] + L < T:
+        raise ValueError(f'ring of {T} frames: the last window ends at frame {offsets[-1] + L} and leaves a gap at the wrap')
+    if ramp < 1:
+        raise ValueError(f'loop ramp {ramp}: at least 1')
+
+
+def loop_windows(total_frames, window_frames, min_overlap):
+    """(offsets, L) for a ring of total_frames: windows of L = min(window_frames, total_frames) frames at the offsets i T // P, with the fewest P >= 2 for
+    which every window shares at least min_overlap frames with its cyclic successor (loop_overlaps).  The largest step between such offsets is
+    ceil(T / P), so P = max(2, ceil(T / (L - min_overlap))).  A ring no longer than one window is two windows of L = T half a turn apart: a single window
+    would have nobody to agree with at its own seam."""
+    T, O = int(total_frames), int(min_overlap)
+    if T < 2 or int(window_frames) < 1:
+        raise ValueError(f'total_frames={total_frames}, window_frames={window_frames}: a ring has at least 2 frames, a window at least 1')
+    L = min(int(window_frames), T)
+    if O < 0 or O >= L:
+        raise ValueError(f'min_overlap={min_overlap} outside [0, window length {L})')
+    P = max(2, -(-T // (L - O)))
+    if P > T:
+        raise ValueError(f'min_overlap={min_overlap}: no {T} or fewer windows of {L} frames on a ring of {T} share that much')
+    return [i * T // P for i in range(P)], L
+
+
 def canvas_windows(total_frames, window_frames, min_overlap):
     """(offsets, L): the fewest windows of L <= window_frames latent frames that cover total_frames with at least min_overlap frames shared between
     neighbours, spread evenly (integer arithmetic).  A canvas that fits one window is ([0], total_frames): the plain call."""
@@ -339,6 +419,26 @@ def canvas_windows(total_frames, window_frames, min_overlap):
         return [0], T
     n = -(-(T - O) // (L - O))
     return [(i * (T - L) + (n - 1) // 2) // (n - 1) for i in range(n)], L
+
+
+def decode_circular(autoencoder, latents, context=None):
+    """Decode a ring of latents [N, C, T] as a ring: the VAE's convolutions pad with zeros, so the ring is extended by `context` wrapped frames on either side
+    (tiled when context > T), decoded in ONE call, and context * (out_len // in_len) samples are cut from each end.  Once `context` covers the decoder's
+    receptive field (``autoencoder.decoder_context_frames()``, what None asks for) no kept sample has seen a zero halo and the result is what a decoder with
+    circular convolutions gives: its last sample continues into its first.  An injected autoencoder without that method needs an explicit `context`."""
+    if context is None:
+        ask = getattr(autoencoder, 'decoder_context_frames', None)
+        if ask is None:
+            raise ValueError('decode_circular: this autoencoder does not tell its receptive field (decoder_context_frames): pass context=')
+        context = ask()
+    context = int(context)
+    if context < 0:
+        raise ValueError(f'context={context}: at least 0')
+    T = latents.shape[-1]
+    ext = latents[..., torch.arange(-context, T + context, device=latents.device) % T]
+    wav = autoencoder(embedding=ext)
+    cut = context * (wav.shape[-1] // ext.shape[-1])
+    return wav[..., cut:wav.shape[-1] - cut]
 
 
 def sample_coefficients(scheduler, etas):
@@ -385,7 +485,7 @@ def pad_conditions(condition, frames, n_prompts):
     return condition
 
 
-def draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n_prompts=1, first_index=0, start_steps=None, canvas_offsets=None):
+def draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n_prompts=1, first_index=0, start_steps=None, canvas_offsets=None, canvas_loop=None):
     """Init noise + per-step DDIM noise in the order the reference draws them from ONE generator
     (src/inference.py:58-67 then one randn per scheduler.step, diffusers `randn_tensor`).  For several
     prompts each sample gets its own generator seeded seed + index, so results do not depend on how
@@ -404,19 +504,28 @@ def draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n
 
     ``canvas_offsets`` (long-form canvas, one offset per window; ``audio_frames`` is the window length L): ONE generator, seeded like the single prompt's,
     draws the init noise (1, C, T) of the canvas of T = canvas_offsets[-1] + L frames and then, when eta > 0, one (1, C, T) per step; window i receives the
-    slice [canvas_offsets[i], canvas_offsets[i] + L), so the windows share their noise where they share frames.  One window draws what the plain call draws."""
+    slice [canvas_offsets[i], canvas_offsets[i] + L), so the windows share their noise where they share frames.  One window draws what the plain call draws.
+
+    ``canvas_loop=T`` with ``canvas_offsets`` (seamless loops): the canvas draws are (1, C, T) -- the numbers the plain call of T frames draws -- and window i
+    receives the ring frames (canvas_offsets[i] + r) mod T, r in [0, L): the cut wraps."""
+    if canvas_loop is not None and canvas_offsets is None:
+        raise ValueError('canvas_loop is the length of the ring that canvas_offsets lie on')
     if canvas_offsets is not None:
         offs = [int(v) for v in canvas_offsets]
         if _is_seq(audio_frames) or _is_seq(eta) or _is_seq(random_seed) or start_steps is not None:
             raise ValueError('a canvas takes one window length, one eta and one seed, and no start steps')
         L = int(audio_frames)
-        T = offs[-1] + L
+        T = offs[-1] + L if canvas_loop is None else int(canvas_loop)
         g = torch.Generator(device=device)
         if random_seed is not None:
             g.manual_seed(random_seed + first_index)
         else:
             g.seed()
         cut = lambda t: torch.cat([t[:, :, o:o + L] for o in offs], dim=0)   # noqa: E731
+        if canvas_loop is not None:
+            if L > T:
+                raise ValueError(f'windows of {L} frames on a ring of {T}')
+            cut = lambda t: torch.cat([t[:, :, _ring(o, L, T, t.device)] for o in offs], dim=0)   # noqa: E731
         init = cut(torch.randn((1, codec_dim, T), generator=g, device=device))
         if not (eta or 0) > 0:
             return init, None
@@ -463,7 +572,7 @@ def inference_controlnet(autoencoder, unet, controlnet, gt, gt_mask, condition, 
 def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, noise_scheduler, text_raw,
               neg_text=None, audio_frames=500, guidance_scale=3, guidance_rescale=0.0, ddim_steps=50, eta=1,
               random_seed=2024, device='cuda', use_graph=True, controlnet=None, condition=None, conditioning_scale=1.0,
-              first_index=None, init_latents=None, strength=None, canvas_offsets=None, canvas_ramp=None, solver='ddim'):
+              first_index=None, init_latents=None, strength=None, canvas_loop=None, decode_context=None, canvas_offsets=None, canvas_ramp=None, solver='ddim'):
     """Same signature and semantics as the reference's ``inference`` (src/inference.py:26-107).
 
     Extension: ``solver='dpmpp_2m'`` samples with DPM-Solver++(2M) instead of DDIM (deterministic: eta must be 0, the signature's
@@ -495,7 +604,12 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
     (None: the smallest overlap between neighbours, a linear cross-fade; 1: the plain mean).  ``text_raw`` is one prompt for every window or a list with one
     prompt per window (a scene that changes over time); the settings are scalars; no gt, ControlNet or init_latents.  The canvas is decoded in one call:
     the result is [1, 1, T * ratio].  The windows are coupled, so the call is never sharded over ranks.  One window is the plain call.  Audio quality on the
-    real checkpoints -- seam audibility, the choice of overlap and ramp, the comparison with one long row -- is unmeasured."""
+    real checkpoints -- seam audibility, the choice of overlap and ramp, the comparison with one long row -- is unmeasured.
+
+    Extension (seamless loops): ``canvas_loop=T`` with ``canvas_offsets`` (loop_windows() chooses them) makes the canvas a RING of T >= audio_frames latent
+    frames: window p holds the frames (canvas_offsets[p] + r) mod T, the last window runs into the first, and the default ramp is the smallest cyclic overlap.
+    The ring is decoded as a ring (decode_circular, with ``decode_context`` wrapped frames on either side; None asks the autoencoder): the result is
+    [1, 1, T * ratio], and its end continues into its beginning.  Everything else as with the line; audio quality on the real checkpoints is unmeasured."""
     if (init_latents is None) != (strength is None):
         raise ValueError('init_latents and strength must be given together')
     if neg_text is None:
@@ -516,12 +630,20 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
                 raise ValueError(f'a canvas takes one {name}, not one per window')
         if gt is not None or gt_mask is not None or controlnet is not None or init_latents is not None:
             raise ValueError('a canvas does not combine with gt / gt_mask, a ControlNet or init_latents')
-        overlaps = [a + audio_frames - b for a, b in zip(canvas_offsets, canvas_offsets[1:])]
-        if canvas_ramp is None:
-            canvas_ramp = max(1, min(overlaps)) if overlaps else 1
-        check_canvas(canvas_offsets, audio_frames, canvas_offsets[-1] + audio_frames, canvas_ramp)
-    elif canvas_ramp is not None:
-        raise ValueError('canvas_ramp without canvas_offsets')
+        if canvas_loop is not None:
+            canvas_loop = int(canvas_loop)
+            if canvas_ramp is None:
+                canvas_ramp = max(1, min(loop_overlaps(canvas_offsets, audio_frames, canvas_loop))) if n_win else 1
+            check_canvas_loop(canvas_offsets, audio_frames, canvas_loop, canvas_ramp)
+        else:
+            overlaps = [a + audio_frames - b for a, b in zip(canvas_offsets, canvas_offsets[1:])]
+            if canvas_ramp is None:
+                canvas_ramp = max(1, min(overlaps)) if overlaps else 1
+            check_canvas(canvas_offsets, audio_frames, canvas_offsets[-1] + audio_frames, canvas_ramp)
+    elif canvas_ramp is not None or canvas_loop is not None:
+        raise ValueError('canvas_ramp / canvas_loop without canvas_offsets')
+    if decode_context is not None and canvas_loop is None:
+        raise ValueError('decode_context belongs to canvas_loop: only a ring is decoded with wrapped context')
     if isinstance(text_raw, str):
         text_raw = [text_raw]
     if isinstance(ddim_steps, (list, tuple)):
@@ -583,22 +705,27 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
         if init_latents.dim() != 3 or init_latents.shape[0] not in (1, n_prompts) or tuple(init_latents.shape[1:]) != (codec_dim, lmax):
             raise ValueError(f'init_latents must be [1 or {n_prompts}, {codec_dim}, {lmax}], got {tuple(init_latents.shape)}')
         a2a = dict(init_latents=init_latents, start_steps=starts, latent_scale=params['autoencoder']['scale'], latent_shift=params['autoencoder']['shift'])
-    long_form = canvas_offsets is not None and len(canvas_offsets) > 1   # (one window is the plain call, through the plain code)
+    long_form = canvas_offsets is not None and (len(canvas_offsets) > 1 or canvas_loop is not None)   # (one window of a line is the plain call, through the plain code)
     init, step_noises = draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n_prompts, first_index,
-                                    **(dict(start_steps=a2a['start_steps']) if a2a else {}), **(dict(canvas_offsets=canvas_offsets) if long_form else {}))
+                                    **(dict(start_steps=a2a['start_steps']) if a2a else {}), **(dict(canvas_offsets=canvas_offsets) if long_form else {}),
+                                    **(dict(canvas_loop=canvas_loop) if canvas_loop is not None else {}))
     smp = LatentSampler(unet, noise_scheduler)
     # equal lengths are the unpadded batch (the same bits; include/ezdit.h ezdit_set_lengths): the length table is for ragged batches only
     ragged = frames is not None and len(set(frames)) > 1
     kw = dict(lengths=frames) if ragged else {}
     if solver != 'ddim':
         kw['solver'] = solver
-    if long_form:
+    if canvas_loop is not None:
+        kw['canvas_loop'] = (canvas_offsets, canvas_loop, canvas_ramp)
+    elif long_form:
         kw['canvas'] = (canvas_offsets, canvas_offsets[-1] + audio_frames, canvas_ramp)
     smp.prepare(text.float(), text_mask, uncond_text.float(), uncond_mask, init, step_noises, guidance_scale,
                 guidance_rescale, ddim_steps, eta, gt=gt, gt_mask=gt_mask, controlnet=controlnet, condition=condition,
                 conditioning_scale=conditioning_scale, **kw, **a2a)
     smp.run(use_graph=use_graph)
     latents = smp.finish()
+    if canvas_loop is not None:   # one decode of the ring, with wrapped context
+        return decode_circular(autoencoder, scale_shift_re(smp.canvas_latents(), params['autoencoder']['scale'], params['autoencoder']['shift']), decode_context)
     if long_form:   # one decode of the whole canvas
         return autoencoder(embedding=scale_shift_re(smp.canvas_latents(), params['autoencoder']['scale'], params['autoencoder']['shift']))
     pred = scale_shift_re(latents, params['autoencoder']['scale'], params['autoencoder']['shift'])

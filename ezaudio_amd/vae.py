@@ -239,6 +239,29 @@ class OobleckDecoder(_OobleckNet):
             gap = max(gap, -(-UNIT_HALO // mul))
         return gap
 
+    def layer_list(self):
+        """The decoder's convolutions in forward order, as what decides which inputs an output reads: ('conv', kernel, dilation, padding) for a Conv1d of
+        stride 1 and ('up', kernel, stride, padding) for a ConvTranspose1d (autoencoders.py:149-190; the k = 1 convs of the residual units and the
+        activations read one position and are left out)."""
+        layers = [('conv', 7, 1, 3)]
+        for s in reversed(self.strides):
+            layers.append(('up', 2 * s, s, math.ceil(s / 2)))
+            layers += [('conv', 7, d, 3 * d) for d in DILATIONS]
+        return layers + [('conv', 7, 1, 3)]
+
+    def context_frames(self):
+        """Half-width of the decoder's receptive field in latent frames, rounded up: the audio of latent frame q -- the samples [q ratio, (q + 1) ratio) -- reads
+        no latent frame outside [q - n, q + n].  Walked backwards through layer_list(): the samples [lo, hi] of a level need [lo - p, hi - p + (k - 1) d]
+        of the level before through a Conv1d (output t reads t - p + tap d) and [ceil((lo + p - k + 1) / s), floor((hi + p) / s)] through a ConvTranspose1d
+        (output t reads input q where 0 <= t + p - q s <= k - 1)."""
+        lo, hi = 0, self.ratio - 1
+        for kind, k, a, p in reversed(self.layer_list()):
+            if kind == 'conv':
+                lo, hi = lo - p, hi - p + (k - 1) * a
+            else:
+                lo, hi = -((k - 1 - p - lo) // a), (hi + p) // a
+        return max(-lo, hi)
+
     def _decode_one(self, zt, out, st, seg=None, Lmax=None):
         """zt fp32 [L][latent] (token-major), out fp32 [L * ratio].  With `seg`: zt [B][Lmax][latent], L the stacked row count (B - 1) S + Lmax, out
         [B][Lmax * ratio]; the same launches over the stacked rows, the segment kernels in place of the plain ones."""
@@ -571,6 +594,11 @@ class Autoencoder:
         if self.ae.encoder is None:
             raise RuntimeError('this Autoencoder was loaded without encoder weights')
         return self.ae.encoder.latent_lengths(lengths)
+
+    def decoder_context_frames(self):
+        """Half-width of the decoder's receptive field in latent frames (OobleckDecoder.context_frames, computed from its layer list): the context that
+        sampler.decode_circular wraps around a ring of latents so that the decode equals one with circular convolutions."""
+        return self.ae.decoder.context_frames()
 
     def eval(self):
         return self

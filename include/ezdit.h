@@ -11,11 +11,11 @@
  *     allocates or frees persistent device memory.  Weights live in one caller-owned blob laid out
  *     by ezdit_param_info(); all activations / tables live in one caller-owned workspace.
  *   - the PER-STEP entry points (ezdit_forward, ezdit_controlnet_forward, ezdit_sampler_run, ezdit_set_step,
- *     ezdit_cfg_ddim_step, ezdit_cfg_ddim_step_per_sample, ezdit_cfg_multistep_step, ezdit_add_noise, ezdit_canvas_blend, the ezvae_* ops) are ASYNCHRONOUS on their stream: no device sync, no host read of
+ *     ezdit_cfg_ddim_step, ezdit_cfg_ddim_step_per_sample, ezdit_cfg_multistep_step, ezdit_add_noise, ezdit_canvas_blend, ezdit_canvas_blend_loop, the ezvae_* ops) are ASYNCHRONOUS on their stream: no device sync, no host read of
  *     device data (a sampler step is hipGraph-capturable).  The once-per-call SET-UP entry points synchronise the
  *     stream and must not be called inside a stream capture: ezdit_bind_workspace (diagnostic builds only),
  *     ezdit_prepare_context (reads the context mask back to find single-key batch elements when `xkey1` is on),
- *     ezdit_prepare_timesteps, ezdit_sampler_begin, ezdit_sampler_set_sample_params, ezdit_sampler_set_multistep, ezdit_sampler_set_start and ezdit_sampler_set_canvas (host staging
+ *     ezdit_prepare_timesteps, ezdit_sampler_begin, ezdit_sampler_set_sample_params, ezdit_sampler_set_multistep, ezdit_sampler_set_start, ezdit_sampler_set_canvas and ezdit_sampler_set_canvas_loop (host staging
  *     buffers of the timestep / coefficient tables), ezdit_set_lengths, ezdit_sampler_set_pair_lengths and ezdit_sampler_set_cn_scales
  *     (host mirrors of the length / scale tables).
  *   - return 0 = OK, negative = error; ezdit_last_error() gives a thread-local message.  No C++
@@ -114,8 +114,8 @@ int    ezdit_bind_workspace(ezdit_handle* h, void* dev_ws, size_t bytes, int B, 
                             ezdit_stream stream);
 
 /* ---- Run-time tables of the step -------------------------------------------------------------- */
-/* Seven setters below hand the step a RUN-TIME TABLE: a small array in the workspace that the kernels of the step read at run time.  One
- * contract holds for all seven; their own comments say only what is specific to each.
+/* The setters below hand the step a RUN-TIME TABLE: a small array in the workspace that the kernels of the step read at run time.  One
+ * contract holds for all of them; their own comments say only what is specific to each.
  *   - A set-up entry point: the values are a HOST array, the call uploads them and waits for `stream`.  EZDIT_E_STATE inside a stream
  *     capture and before the state the table lives in exists: a bound workspace, or, for a call-scoped table, a sampler call begun on
  *     it ("ezdit_sampler_begin first").  NULL or a count of 0 switches the table off: bit for bit the call that never set it.
@@ -136,7 +136,8 @@ int    ezdit_bind_workspace(ezdit_handle* h, void* dev_ws, size_t bytes, int B, 
  *       start (.._set_start)                      off <-> on (also moves the step     ezdit_bind_workspace, ezdit_sampler_begin
  *                                                   counter: on, min(start_steps);
  *                                                   off after on, 0)
- *       canvas (.._set_canvas)                    off <-> on, another T or ramp       ezdit_bind_workspace, ezdit_sampler_begin
+ *       canvas (.._set_canvas, .._set_canvas_loop:  off <-> on, another T or ramp,    ezdit_bind_workspace, ezdit_sampler_begin, either setter
+ *         one table, a line or a ring)              line <-> ring                       with NULL
  * ezdit_bind_workspace ends the sampler call as well: ezdit_sampler_run and the call-scoped setters (the last four) return EZDIT_E_STATE
  * until the next ezdit_sampler_begin, whatever shape was bound. */
 
@@ -370,6 +371,28 @@ int ezdit_canvas_blend(float* dev_latents, const int32_t* dev_offsets, int P, in
  * are not implemented; while the canvas is on, ezdit_set_lengths, ezdit_sampler_set_start and ezdit_sampler_attach_controlnet (with a
  * ControlNet) are refused the same way. */
 int ezdit_sampler_set_canvas(ezdit_handle* h, const int32_t* offsets, int P, int T, int ramp, ezdit_stream stream);
+
+/* ---- seamless loops: the canvas as a ring ------------------------------------------------------------------------------------------------ */
+/* The canvas above is a line: its first and last frame know nothing of each other.  Here the T frames are a RING: window p holds the ring
+ * frames (dev_offsets[p] + r) mod T for r in [0, L), so the last window runs into the first and every window has both its edges inside a
+ * neighbour; a clip decoded from the ring (with wrapped context: ezaudio_amd.sampler.decode_circular) ends where it begins.  L <= T, so a
+ * window holds a ring frame at most once.  Everything else is ezdit_canvas_blend: the same weights min(r + 1, L - r, ramp), the fp32 sum over
+ * the holders in ascending p, the same v into every holder (bit-identical aliases, across the wrap too), one thread per (c, j), an element
+ * with one holder neither read nor written, and no value of the device table makes the kernel touch memory outside the P * C * L elements.
+ * With a table whose last window ends exactly at T (no window wraps) the result is ezdit_canvas_blend's bit for bit.
+ * Asynchronous, no handle needed.  EZDIT_E_INVALID: a NULL pointer; P, C or L < 1; ramp < 1; L > T; T > P * L (what no table can cover). */
+int ezdit_canvas_blend_loop(float* dev_latents, const int32_t* dev_offsets, int P, int C, int L, int T, int ramp, ezdit_stream stream);
+
+/* ezdit_sampler_set_canvas for the ring: while on, every step ends with ezdit_canvas_blend_loop on the updated latents -- one more node of
+ * the captured step than the plain step, the same count as the line.  It is the SAME run-time table as ezdit_sampler_set_canvas (the same
+ * slot of the workspace: ezdit_workspace_bytes does not grow): the two setters replace each other (line <-> ring is another kernel and
+ * drops the graph), NULL or P = 0 on either switches the table off, ezdit_sampler_begin clears it.  The per-sample settings table and the
+ * multistep solver work with it; the multistep history stays per window.
+ * EZDIT_E_INVALID unless P is the P of ezdit_sampler_begin, L <= T, offsets[0] == 0, the offsets ascend strictly, offsets[i + 1] <=
+ * offsets[i] + L, offsets[P - 1] < T, offsets[P - 1] + L >= T (no gap at the wrap) and ramp >= 1.  EZDIT_E_STATE and EZDIT_E_UNSUPPORTED
+ * as ezdit_sampler_set_canvas: not with a length table, a start table, gt / gt_mask or an attached ControlNet, and those four are refused
+ * while the ring is on.  Audio quality on the real checkpoints (whether the seam is audible, the choice of overlap and ramp) is unmeasured. */
+int ezdit_sampler_set_canvas_loop(ezdit_handle* h, const int32_t* offsets, int P, int T, int ramp, ezdit_stream stream);
 
 /* ---- Oobleck VAE decoder building blocks (src/modules/stable_vae/models/autoencoders.py:38-61,82-113,149-190) --------
  * Stateless ops on caller-owned device buffers; the layer sequence is host code (ezaudio_amd/vae.py), run once per call.
