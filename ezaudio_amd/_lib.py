@@ -138,6 +138,9 @@ PROTOTYPES = {
     'ezdit_last_launch_count': (C.c_int, [C.c_void_p]),
     'ezdit_debug_stop_after': (C.c_int, [C.c_void_p, C.c_int]),
     'ezdit_set_option': (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
+    'ezdit_set_attention_window': (C.c_int, [C.c_void_p, C.c_int]),
+    'ezdit_test_attention_band': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                            C.c_void_p]),
 }
 
 

@@ -83,8 +83,21 @@ class EzAudio:
         noise_scheduler = DDIMScheduler(**params['diff'])
         return autoencoder, unet, tokenizer, text_encoder, noise_scheduler, params
 
+    def _window_radius(self, attention_window):
+        """Seconds (the full span a frame sees) -> radius in latent frames for sampler.inference; None stays None."""
+        if attention_window is None:
+            return None
+        if isinstance(attention_window, (list, tuple)):
+            raise ValueError('attention_window is one value per call: the prompts of a call share the attention kernels')
+        if isinstance(attention_window, bool) or not attention_window > 0:
+            raise ValueError(f'attention_window is a span in seconds > 0, got {attention_window!r}')
+        radius = int(round(attention_window * self.params['autoencoder']['latent_sr'] / 2))
+        if radius < 1:
+            raise ValueError(f'attention_window of {attention_window} s is less than one latent frame on either side')
+        return radius
+
     def generate_audio(self, text, length=10, guidance_scale=5, guidance_rescale=0.75, ddim_steps=100, eta=1,
-                       random_seed=None, randomize_seed=False, solver='ddim'):
+                       random_seed=None, randomize_seed=False, attention_window=None, solver='ddim'):
         """api/ezaudio.py:101-130.  `text` may also be a list of prompts (batched extension): the result is then
         an array [N, T].  With a list of prompts `length` may be a list too, one duration in seconds per prompt (mixed-length
         batch, one call): the result is then (sr, [one 1-D array per prompt]), each trimmed to its own duration.
@@ -92,9 +105,14 @@ class EzAudio:
         prompt is sampled as the call with it alone would sample it (return shapes unchanged).  A prompt '' inside a list runs without
         guidance (the "empty input" rule per prompt); `randomize_seed` draws one seed per prompt of a list.
         `solver='dpmpp_2m'` samples with DPM-Solver++(2M) instead of DDIM; it is deterministic, so pass eta=0 with it (the default eta=1
-        raises).  Quality at reduced `ddim_steps` on the real checkpoints is unmeasured."""
+        raises).  Quality at reduced `ddim_steps` on the real checkpoints is unmeasured.
+        `attention_window` (seconds; one value): sliding-window self-attention -- every latent frame attends to the frames inside a span of that many seconds
+        centred on it (radius round(seconds * latent_sr / 2) frames), so a `length` beyond the trained 10 s keeps every pair of frames inside the trained range
+        of relative positions: attention_window=10 gives each frame the 501 keys of the trained row.  A span that covers the clip is the plain call, bit for
+        bit.  Audio quality of windowed sampling on the real checkpoints is unmeasured."""
         neg_text = None
         check_solver(solver, eta)
+        radius = self._window_radius(attention_window)
         for name, v in (('guidance_scale', guidance_scale), ('guidance_rescale', guidance_rescale), ('eta', eta), ('random_seed', random_seed)):
             if isinstance(v, (list, tuple)) and (isinstance(text, str) or len(v) != len(text)):
                 raise ValueError(f'a list of {name} needs a list of prompts of the same size')
@@ -120,7 +138,7 @@ class EzAudio:
             random_seed = random.randint(0, MAX_SEED) if isinstance(text, str) else [random.randint(0, MAX_SEED) for _ in text]
         pred = inference(self.autoencoder, self.unet, gt, gt_mask, self.tokenizer, self.text_encoder, self.params,
                          self.noise_scheduler, text, neg_text, length, guidance_scale, guidance_rescale, ddim_steps,
-                         eta, random_seed, self.device, solver=solver)
+                         eta, random_seed, self.device, solver=solver, attention_window=radius)
         pred = pred.cpu().numpy()
         if per_prompt:
             ratio = self.params['autoencoder']['sr'] // latent_sr
@@ -235,8 +253,9 @@ class EzAudio:
                     chunk_length=end_idx - start_idx)
 
     def editing_audio(self, text, boundary, gt_file, mask_start, mask_length, guidance_scale=3.5, guidance_rescale=0,
-                      ddim_steps=100, eta=1, random_seed=None, randomize_seed=False, solver='ddim'):
-        """api/ezaudio.py:132-207 (crop / pad / mask bookkeeping on the host, sampling on the GPU).  `solver` as in generate_audio.  `gt_file` is a path or a
+                      ddim_steps=100, eta=1, random_seed=None, randomize_seed=False, attention_window=None, solver='ddim'):
+        """api/ezaudio.py:132-207 (crop / pad / mask bookkeeping on the host, sampling on the GPU).  `solver` and `attention_window` (seconds; quality on the real
+        checkpoints unmeasured) as in generate_audio.  `gt_file` is a path or a
         1-D numpy waveform at the model's sample rate.
 
         Batched extension: `text` may be a list of prompts, one edit per entry in ONE encode, ONE sampler call and ONE decode; the result is then
@@ -247,9 +266,10 @@ class EzAudio:
         from the global generator, in list order: the draws the single calls in that order make.  The autoencoder must take `lengths=` and have
         `latent_lengths` (this package's Autoencoder does)."""
         check_solver(solver, eta)
+        radius = self._window_radius(attention_window)
         if not isinstance(text, str):
             return self._editing_audio_batch(list(text), boundary, gt_file, mask_start, mask_length, guidance_scale, guidance_rescale, ddim_steps, eta,
-                                             random_seed, randomize_seed, solver)
+                                             random_seed, randomize_seed, solver, radius)
         for name, v in (('gt_file', gt_file), ('boundary', boundary), ('mask_start', mask_start), ('mask_length', mask_length),
                         ('guidance_scale', guidance_scale), ('guidance_rescale', guidance_rescale), ('eta', eta), ('random_seed', random_seed)):
             if isinstance(v, (list, tuple)):
@@ -273,7 +293,7 @@ class EzAudio:
             random_seed = random.randint(0, MAX_SEED)
         pred = inference(self.autoencoder, self.unet, gt_latent, gt_mask, self.tokenizer, self.text_encoder,
                          self.params, self.noise_scheduler, text, neg_text, L, guidance_scale, guidance_rescale,
-                         ddim_steps, eta, random_seed, self.device, solver=solver)
+                         ddim_steps, eta, random_seed, self.device, solver=solver, attention_window=radius)
         pred = pred.cpu().numpy().squeeze(0).squeeze(0)
         pred = pred[:round(req['chunk_length'] * sr)]
         output_audio = req['output_audio']
@@ -281,7 +301,7 @@ class EzAudio:
         return sr, output_audio
 
     def _editing_audio_batch(self, text, boundary, gt_file, mask_start, mask_length, guidance_scale, guidance_rescale, ddim_steps, eta, random_seed,
-                             randomize_seed, solver):
+                             randomize_seed, solver, radius=None):
         """editing_audio for a list of prompts: N crops in one ragged encode, one sampler call at per-request latent lengths, one ragged decode."""
         n = len(text)
         if isinstance(ddim_steps, (list, tuple)):
@@ -320,7 +340,7 @@ class EzAudio:
             random_seed = [random.randint(0, MAX_SEED) for _ in text]
         pred = inference(self.autoencoder, self.unet, gt_latent, gt_mask, self.tokenizer, self.text_encoder,
                          self.params, self.noise_scheduler, text, None, frames, guidance_scale, guidance_rescale,
-                         ddim_steps, eta, random_seed, self.device, solver=solver)
+                         ddim_steps, eta, random_seed, self.device, solver=solver, attention_window=radius)
         pred = pred.cpu().numpy()
         outs = []
         for i, r in enumerate(reqs):
@@ -330,7 +350,7 @@ class EzAudio:
         return sr, outs
 
     def audio_to_audio(self, text, audio, strength=0.5, guidance_scale=5, guidance_rescale=0.75, ddim_steps=100, eta=1, random_seed=None,
-                       randomize_seed=False, solver='ddim'):
+                       randomize_seed=False, attention_window=None, solver='ddim'):
         """Re-render a recording under a prompt, staying as close to it as `strength` says (not in the reference: the standard "start the sampler from the
         noised clip" of image-to-image, SDEdit).  `audio` is a path or a 1-D numpy waveform at the model's sample rate, peak-normalised and encoded whole;
         `strength` in (0, 1] is the share of the `ddim_steps` that are run (scheduler.start_step): 1 starts from pure noise, the plain generate_audio of the
@@ -342,8 +362,11 @@ class EzAudio:
         inside a list runs without guidance; `randomize_seed` draws one seed per request.  The autoencoder must take `lengths=` and have `latent_lengths`
         (this package's Autoencoder does).
 
-        Audio quality versus strength on the real checkpoints is unmeasured."""
+        `attention_window` (seconds) as in generate_audio: a recording longer than the trained 10 s sampled with sliding-window self-attention.
+
+        Audio quality versus strength, and of windowed sampling, on the real checkpoints is unmeasured."""
         check_solver(solver, eta)
+        radius = self._window_radius(attention_window)
         if isinstance(ddim_steps, (list, tuple)):
             raise ValueError('ddim_steps must be one value per call: per-prompt step counts are not supported')
         sr = self.params['autoencoder']['sr']
@@ -382,7 +405,7 @@ class EzAudio:
             L = latent.shape[-1]
             pred = inference(self.autoencoder, self.unet, None, None, self.tokenizer, self.text_encoder, self.params, self.noise_scheduler, text, None, L,
                              guidance_scale, guidance_rescale, ddim_steps, eta, random_seed, self.device, solver=solver, init_latents=latent,
-                             strength=strength)
+                             strength=strength, attention_window=radius)
             return sr, pred.cpu().numpy().squeeze(0).squeeze(0)
         text = list(text)
         if '' in text:
@@ -398,7 +421,7 @@ class EzAudio:
         frames = [int(v) for v in self.autoencoder.latent_lengths(samples)]
         pred = inference(self.autoencoder, self.unet, None, None, self.tokenizer, self.text_encoder, self.params, self.noise_scheduler, text, None, frames,
                          guidance_scale, guidance_rescale, ddim_steps, eta, random_seed, self.device, solver=solver, init_latents=latent,
-                         strength=per(strength))
+                         strength=per(strength), attention_window=radius)
         pred = pred.cpu().numpy()
         up = pred.shape[-1] // max(frames)                                     # samples per latent frame, as decoded
         return sr, [pred[i, 0, :f * up] for i, f in enumerate(frames)]

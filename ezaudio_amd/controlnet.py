@@ -13,6 +13,8 @@ from .weights import pack_state_dict
 
 
 class DiTControlNet:
+    attention_window = None   # as MaskDiT.attention_window
+
     def __init__(self, cond_in=None, cond_blocks=None, cond_mask=False, cond_mask_prob=None, cond_mask_ratio=None,
                  cond_mask_span=None, device='cuda', max_len=2048, **kwargs):
         cfg = dict(kwargs)
@@ -70,6 +72,12 @@ class DiTControlNet:
         context = context.to(self.device, torch.float32).contiguous()
         mask = None if context_mask is None else context_mask.to(self.device).to(torch.uint8).contiguous()
         _lib.check(self.lib.ezdit_prepare_context(self._h, _ptr(context), _ptr(mask), _stream()))
+
+    def set_attention_window(self, frames):
+        """MaskDiT.set_attention_window for the ControlNet's blocks.  An attached pair must agree (ezdit_sampler_attach_controlnet refuses one that does not)."""
+        radius = 0 if frames is None else int(frames)
+        _lib.check(self.lib.ezdit_set_attention_window(self._h, radius))
+        self.attention_window = radius or None
 
     def prepare_timesteps(self, ts, per_row):
         arr = (C.c_int32 * len(ts))(*[int(t) for t in ts])

@@ -235,6 +235,11 @@ struct ezdit_handle {
     int opt_attn_nkh = 0;                                                                 // attention key sub-blocks per tile (0 = auto)
     int opt_q2_pp = 1;                                                                    // cross-attn q projection at large grids: ping-pong GEMM with the per-head LayerNorm in its epilogue (0: fp32 GEMM + normalisation inside k_attn)
     int opt_attn_xcd = 1;                                                                 // attention: all query tiles of a (batch, head) on one XCD
+    // sliding-window self-attention (ezdit_set_attention_window): radius in frames, 0 = off.  Handle-scoped: neither ezdit_bind_workspace nor ezdit_sampler_begin
+    // clears it.  A radius that covers the bound row (>= L - 1) masks nothing and launches the plain kernel: attn_band() is what the self-attention launch is given
+    int attn_window = 0;
+    int attn_band() const { return attn_window > 0 && attn_window < L - 1 ? attn_window : 0; }
+    hipStream_t last_stream = nullptr;   // the stream of the latest forward / sampler call on this handle: what a setter without a stream argument asks about a capture
     // XCD affinity of the residual path at M <= 1024 (placement only, results bit-identical): gemm_panel = shapes (1 D x D, 2 skip, 4 MLP-out)
     // whose split-K GEMM puts ALL workgroups of an M tile on XCD tm % 8; row_affine = the row kernel processes row panel p on XCD p % 8, so
     // a panel's slabs, residual stream and LayerNorm output stay in one XCD's L2 (the L2 keeps its lines across kernel boundaries: a
@@ -900,6 +905,7 @@ int ezdit_bind_workspace(ezdit_handle* h, void* ws, size_t bytes, int B, int L, 
     const size_t need = carve(h, B, L, Lc, n_slots, &bufs);
     if (bytes < need) return fail(EZDIT_E_INVALID, "workspace %zu < required %zu bytes", bytes, need);
     hipStream_t st = (hipStream_t)stream;
+    h->last_stream = st;
     h->ws = reinterpret_cast<char*>(ws);
     h->ws_bytes = bytes;
     h->bufs = bufs;
@@ -1351,6 +1357,7 @@ static int forward_impl(ezdit_handle* h, const float* x, int in_ch, int x_rows, 
         at.out = p.ao; at.ldo = h->ldD;
         at.B = h->B; at.H = h->H; at.Lq = h->L; at.Lk = h->L; at.Lqp = h->Lp; at.Lkp = h->Lp; at.dh = h->dh;
         at.klen = h->lens_dev();   // the reference's x_mask: keys beyond a sample's length do not exist
+        at.band = h->attn_band();  // sliding window (0: the plain kernel, today's launch); the same single launch either way
         STOPCHK();
         at.ts = c.stamps(); at.ts_cap = g_gemm_ts_cap;
         c.launched("k_attn (self)", launch_attention(at, st));
@@ -1409,7 +1416,7 @@ static int forward_impl(ezdit_handle* h, const float* x, int in_ch, int x_rows, 
             at.q = p.q;
             at.k = p.kc + (size_t)b * h->B * h->H * h->Lcp * h->DQK;
             at.v = p.vc + (size_t)b * h->B * h->H * h->Lcp * h->DV;
-            at.kmask = p.kmask; at.klen = nullptr;   // (the key lengths are self-attention's: context keys have their own mask)
+            at.kmask = p.kmask; at.klen = nullptr; at.band = 0;   // (the key lengths and the band are self-attention's: context keys have their own mask and no time axis)
             at.Lk = h->Lc; at.Lkp = h->Lcp;
             STOPCHK();
             at.ts = c.stamps(); at.ts_cap = g_gemm_ts_cap;
@@ -1558,6 +1565,8 @@ int ezdit_sampler_attach_controlnet(ezdit_handle* h, ezdit_handle* cn, float con
     if (!h || h->is_cn) return fail(EZDIT_E_INVALID, "first argument must be a backbone handle");
     if (cn && !cn->is_cn) return fail(EZDIT_E_INVALID, "second argument must be a ControlNet handle");
     if (cn && h->canvas.on) return fail(EZDIT_E_UNSUPPORTED, "a ControlNet while the canvas is on (ezdit_sampler_set_canvas)");
+    if (cn && cn->attn_window != h->attn_window)
+        return fail(EZDIT_E_INVALID, "attention windows differ: backbone %d, ControlNet %d frames (ezdit_set_attention_window on both)", h->attn_window, cn->attn_window);
     if (h->cn && h->cn != cn) {
         auto& v = h->cn->cn_users;
         for (size_t i = 0; i < v.size(); ++i) if (v[i] == h) { v.erase(v.begin() + i); break; }
@@ -1597,6 +1606,7 @@ int ezdit_sampler_begin(ezdit_handle* h, float* latents, int P, const float* noi
             if (h->lens.host[p] != h->lens.host[P + p])
                 return fail(EZDIT_E_INVALID, "lengths of the CFG pair of sample %d differ (%d, %d)", p, h->lens.host[p], h->lens.host[P + p]);
     hipStream_t st = (hipStream_t)stream;
+    h->last_stream = st;
     std::vector<float> cf((size_t)n_steps * 8, 0.f);
     for (int i = 0; i < n_steps; ++i) {
         cf[i * 8 + 0] = coefs[i].sa; cf[i * 8 + 1] = coefs[i].sb; cf[i * 8 + 2] = coefs[i].c_x0;
@@ -1887,8 +1897,11 @@ int ezdit_sampler_run(ezdit_handle* h, int n, int use_graph, ezdit_stream stream
                         b < hl.size() ? hl[b] : -1, b < cl.size() ? cl[b] : -1);
         }
         if (!cn->cond_ready) return fail(EZDIT_E_STATE, "the attached ControlNet has no condition embed for its current lengths: ezdit_prepare_condition first");
+        if (cn->attn_window != h->attn_window)
+            return fail(EZDIT_E_STATE, "attention windows of the backbone (%d) and the attached ControlNet (%d) differ", h->attn_window, cn->attn_window);
     }
     hipStream_t st = (hipStream_t)stream;
+    h->last_stream = st;
     if (!use_graph) {
         for (int i = 0; i < n; ++i) {
             int rc = sampler_step(h, st);
@@ -2103,6 +2116,30 @@ int ezdit_test_attention_varlen(ezdit_handle* h, const void* q, const void* k, c
     return hook_launch("k_attn", "attention configuration", [&] { return launch_attention(a, (hipStream_t)stream); });
 }
 
+// the band form of plain self-attention, stand-alone.  ALWAYS the band instantiation, also for a radius that masks nothing (>= L - 1): that run is what compares the
+// band code with the plain kernel on equal masks
+int ezdit_test_attention_band(ezdit_handle* h, const void* q, const void* k, const void* v, void* out, int B, int L, int Lp, const int32_t* dev_klen, int radius,
+                              ezdit_stream stream) {
+    if (radius < 1) return fail(EZDIT_E_INVALID, "radius = %d: the band form needs a radius >= 1", radius);
+    if (int rc = attn_hook_refusals(h, q, k, v, nullptr, out, B, L, L, Lp, Lp, (hipStream_t)stream)) return rc;
+    if (dev_klen) {   // a test hook may wait: the lengths bound what the kernel reads and which rows it zeroes
+        std::vector<int> kl((size_t)B);
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+        HIPCHK(hipMemcpy(kl.data(), dev_klen, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; ++b)
+            if (kl[b] < 1 || kl[b] > L) return fail(EZDIT_E_INVALID, "klen[%d] = %d outside [1, L = %d]", b, kl[b], L);
+    }
+    AttnArgs a;
+    memset(&a, 0, sizeof a);
+    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v;
+    a.nkh = h->opt_attn_nkh; a.xcd_map = h->opt_attn_xcd;
+    a.out = (bf16_t*)out; a.ldo = h->ldD;
+    a.B = B; a.H = h->H; a.Lq = L; a.Lk = L; a.Lqp = Lp; a.Lkp = Lp; a.dh = h->dh;
+    a.klen = dev_klen;
+    a.band = radius;
+    return hook_launch("k_attn", "attention configuration", [&] { return launch_attention(a, (hipStream_t)stream); });
+}
+
 int ezdit_test_final_conv(const float* y, int ldy, const float* w, const float* b, float* out, int B, int C, int L, const int32_t* dev_lens,
                           ezdit_stream stream) {
     if (!y || !w || !b || !out) return fail(EZDIT_E_INVALID, "null argument");
@@ -2245,6 +2282,18 @@ int ezdit_debug_stop_after(ezdit_handle* h, int n) {
     h->debug_stop = n;
     return EZDIT_OK;
 }
+// radius of the sliding-window self-attention (include/ezdit.h).  The radius is a kernel argument and chooses the kernel: a change drops the captured step
+int ezdit_set_attention_window(ezdit_handle* h, int radius) {
+    if (!h) return fail(EZDIT_E_INVALID, "null handle");
+    if (radius < 0) return fail(EZDIT_E_INVALID, "radius = %d (0 = off, >= 1 = frames on either side)", radius);
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(h->last_stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    if (cs != hipStreamCaptureStatusNone) return fail(EZDIT_E_STATE, "ezdit_set_attention_window inside a stream capture (it changes the kernels of the step)");
+    if (radius != h->attn_window) drop_graph(h);
+    h->attn_window = radius;
+    return EZDIT_OK;
+}
+
 int ezdit_set_option(ezdit_handle* h, const char* name, int value) {
     if (!h || !name) return fail(EZDIT_E_INVALID, "null argument");
     if (!strcmp(name, "zfuse")) h->opt_zfuse = value;

@@ -60,9 +60,12 @@ struct HeadGeom<72> { static constexpr int DQK = 80, DV = 96; };
 // it is bound by what ONE CU can keep in flight -- 32-row tiles give every CU a workgroup at one prompt (256 instead of 128), 22 % fewer operand bytes
 // per workgroup ((32 + 80) instead of (64 + 80) rows per K tile) and a ring of FOUR double stages (six K tiles in flight instead of four).  All eight
 // waves split K in the projection (one 16-wide k-step of a double stage each); the attention proper runs on waves 0 - 3 (one query sub-block x 4 key sub-blocks)
-template <int DH, int NKH, bool ZQ = false, int QT = 64>
+// BAND: sliding-window self-attention (AttnArgs.band): key j exists for query i iff |i - j| <= band.  A template switch like ZQ: the plain kernel carries neither
+// its registers nor its code.  Plain self-attention only (no query prologue, no key mask, Lq == Lk); what changes is marked "band:" below
+template <int DH, int NKH, bool ZQ = false, int QT = 64, bool BAND = false>
 __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
     static_assert(QT == 64 || (QT == 32 && NKH == 4), "32-query tiles: the 8-wave fused-projection form only");
+    static_assert(!BAND || (!ZQ && QT == 64), "the band exists in the plain self-attention form only");
     constexpr int NQS = QT / 32;   // query sub-blocks (of 32 rows) per workgroup
     constexpr int NT = 128 * NKH;
     constexpr int TK = 32 * NKH;   // keys per staged tile
@@ -511,27 +514,59 @@ __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
     // ignores EXEC.
     if (NKH == 4 && __builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
     const int ntiles = (Lk + TK - 1) / TK;
-    LOAD_TILE(0);
+    // band: the tile loop and its register prefetch run over [t_lo, t_hi), the key tiles that hold a key within `band` of one of the workgroup's 64 queries
+    // (workgroup-uniform; qt * QT < Lk here, so t_lo < t_hi <= ntiles).  The LDS double-buffer parity follows t - t_lo: tile t_lo is staged into buffer 0
+    int band = 0, t_lo = 0, t_hi = ntiles;
+    if constexpr (BAND) {
+        band = a.band;
+        // (queries >= Lk are padding: the range ends with the last query that exists.  launch_attention bounds band by Lk: no overflow)
+        const int klo = qt * QT - band, khi = (qt * QT + QT - 1 < Lk ? qt * QT + QT - 1 : Lk - 1) + band;
+        t_lo = klo > 0 ? klo / TK : 0;
+        t_hi = khi / TK + 1 < ntiles ? khi / TK + 1 : ntiles;
+    }
+    LOAD_TILE(t_lo);
     WRITE_TILE(0);
     __syncthreads();
     if (ts && lane == 0) ts[1] = __builtin_readcyclecounter();
-    for (int t = 0; t < ntiles; ++t) {
-        if (t + 1 < ntiles) LOAD_TILE(t + 1);
-        const char* kb = smem + (t & 1) * BUF;
+    for (int t = t_lo; t < t_hi; ++t) {
+        if (t + 1 < t_hi) LOAD_TILE(t + 1);
+        const char* kb = smem + ((t - t_lo) & 1) * BUF;
         const char* vb = kb + KBYTES;
         const char* vtr = vb + (32 * kh + 4 * hi + ((lane & 15) >> 2)) * VSTR + ((lane & 16) + 4 * (lane & 3)) * 2;   // this lane's corner of the transposing reads
         const int key0 = t * TK + kh * 32;
-        if (active && key0 < Lk) {  // wave-uniform: the whole 32-key sub-tile may lie beyond Lk (32-query tiles: waves 4 - 7 only stage)
+        // band: a sub-tile whose nearest key is farther than `band` from all 32 queries of the wave is skipped like one beyond Lk (wave-uniform)
+        bool run = active && key0 < Lk;  // wave-uniform: the whole 32-key sub-tile may lie beyond Lk (32-query tiles: waves 4 - 7 only stage)
+        const int qlast = q0 + 31 < Lk ? q0 + 31 : Lk - 1;   // band: the last query of the wave that exists (rows >= Lk are padding: never stored, or stored as zeros)
+        if constexpr (BAND) run = run && key0 - qlast <= band && q0 - (key0 + 31) <= band;
+        if (run) {
+            uint32_t tmask;
+            bool full;
+            if constexpr (BAND) {
+                // lane-local validity: the lane owns query q0 + r32 and bit o of its mask stands for key key0 + 4 hi + o, at signed distance dist0 + o.  Valid bits are
+                // the run [lo, up]: inside the band on both sides and below Lk.  A masked element takes P = 0 through the select below, never through the exponent
+                // (under the sentinel max, exp2(-1e30 - (-1e30)) would be 1)
+                const int dist0 = key0 + 4 * hi - (q0 + r32);
+                int lo = -band - dist0, up = band - dist0;
+                const int lim = Lk - 1 - key0 - 4 * hi;
+                lo = lo > 0 ? lo : 0;
+                up = up < lim ? up : lim;
+                up = up < 31 ? up : 31;
+                tmask = lo <= up ? (0xffffffffu >> (31 - up)) & (0xffffffffu << lo) : 0u;
+                // wave-uniform: the farthest (query, key) pair of the sub-tile is inside the band on both sides and every key is below Lk -- every interior sub-tile.
+                // Padding queries do not count, so a band that masks nothing takes exactly the paths, and gives exactly the bits, of the plain kernel
+                full = key0 + 31 - q0 <= band && qlast - key0 <= band && key0 + 32 <= Lk;
+            } else {
             // validity of this wave's 32 keys as one bit mask (bit j <-> key0 + j), built BEFORE the MFMAs
             const int kidx = key0 + r32;
             bool kv = kidx < Lk;
             if (km) kv = kv && (km[kidx < Lk ? kidx : 0] != 0);
             const uint32_t ball = (uint32_t)__ballot(kv);               // lanes 0..31 fill bits 0..31
-            const uint32_t tmask = ball >> (4 * hi);
+            tmask = ball >> (4 * hi);
             // wave-uniform: no key of this sub-tile is masked or beyond Lk (every self-attention tile but the last).  The loop is bound
             // by VALU issue (~300 instructions per wave and tile against 11 MFMAs, tools/microbench/attn_bench.cpp), so the common case
             // drops the per-element mask selects and folds scale and reference max into one FMA feeding exp2.
-            const bool full = ball == 0xffffffffu;
+            full = ball == 0xffffffffu;
+            }
             // S^T in VGPRs (the softmax reads every element once: through AGPRs that is 16 v_accvgpr_read per tile), written by inline-asm
             // MFMAs so that the register class is ours to choose.  The wait states hipcc would insert are inside the strings: 2 in front
             // (an operand may have just been written by a VALU or DS instruction the compiler scheduled right before the statement) and
@@ -621,7 +656,7 @@ __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
                 }
             }
         }
-        if (t + 1 < ntiles) WRITE_TILE((t + 1) & 1);
+        if (t + 1 < t_hi) WRITE_TILE((t + 1 - t_lo) & 1);
         __syncthreads();
     }
 
@@ -650,6 +685,8 @@ __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
     __syncthreads();
     if (ts && lane == 0) ts[4] = __builtin_readcyclecounter();
     // weights of the NKH partials for query row q0 + r32 (the items of a wave all belong to its own query sub-block: NW is even)
+    // (band: a partner that never met a valid key of this query still holds m = -1e30 with lsum = 0 and zero accumulators; some partner holds the query's own key, so
+    // mm is a real maximum and the partner's weight exp2(-1e30 - mm) is exactly 0)
     float wgt[NKH];
     {
         float mk[NKH], mm = -1e30f;
@@ -716,6 +753,8 @@ int launch_attention(const AttnArgs& a0, hipStream_t st) {
     if (a.xu && nkh != 4) return 1;   // the fused projection exists in the 8-wave form only (needs Lkp % 128 == 0)
     if (a.dh != 64 && a.dh != 72) return 1;
     if (a.klen && (a.xu || a.q_raw || a.Lq != a.Lk)) return 1;   // per-batch-element lengths: plain self-attention only
+    if (a.band < 0 || (a.band > 0 && (a.xu || a.q_raw || a.kmask || a.Lq != a.Lk))) return 1;   // the band: plain self-attention only
+    if (a.band > a.Lk) a.band = a.Lk;   // (the same mask: keeps the kernel's tile-range arithmetic far from overflow)
     const bool zq = a.xu && a.zstat_in;
     if (zq && !(a.zG && a.zC && a.zparts > 0 && a.zparts <= Z_MAXP && a.zs_stride > 0 && a.zw > 0)) return 1;
     // 32-query tiles (fused projection with the LayerNorm algebra, an even number of K tiles): when the 64-row grid leaves half the CUs without a workgroup
@@ -731,6 +770,16 @@ int launch_attention(const AttnArgs& a0, hipStream_t st) {
     if (q32) {
         if (a.dh == 64) hipLaunchKernelGGL((k_attn<64, 4, true, 32>), grid, dim3(512), 0, st, a);
         else hipLaunchKernelGGL((k_attn<72, 4, true, 32>), grid, dim3(512), 0, st, a);
+        return 0;
+    }
+    if (a.band > 0) {
+        if (a.dh == 64) {
+            if (nkh == 4) hipLaunchKernelGGL((k_attn<64, 4, false, 64, true>), grid, dim3(512), 0, st, a);
+            else hipLaunchKernelGGL((k_attn<64, 2, false, 64, true>), grid, dim3(256), 0, st, a);
+        } else {
+            if (nkh == 4) hipLaunchKernelGGL((k_attn<72, 4, false, 64, true>), grid, dim3(512), 0, st, a);
+            else hipLaunchKernelGGL((k_attn<72, 2, false, 64, true>), grid, dim3(256), 0, st, a);
+        }
         return 0;
     }
     if (a.dh == 64) {

@@ -305,6 +305,9 @@ struct AttnArgs {
     // klen[b] stores zeros and leaves).  Read at run time: one captured graph serves every set of lengths.  Not for the forms with a query prologue (q_raw, xu).
     // At the END of the struct: the offsets of everything above stay what they were
     const int* klen;
+    // sliding-window self-attention (0 = off): key j exists for query i iff |i - j| <= band (and j < klen[b] / Lk).  Another instantiation of k_attn (BAND), which
+    // walks only the key tiles that reach the band of its 64 queries.  Plain self-attention only: no kmask, no query prologue, Lq == Lk.  Behind klen, for the same reason
+    int band;
 };
 int launch_attention(const AttnArgs& a, hipStream_t st);   // 0 = launched, nonzero = configuration not supported
 

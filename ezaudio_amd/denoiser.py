@@ -43,6 +43,8 @@ class _UDiTView:
 
 
 class MaskDiT:
+    attention_window = None   # radius of the sliding-window self-attention in latent frames (set_attention_window); None = full attention
+
     def __init__(self, mae=False, mae_prob=0.5, mask_ratio=(0.25, 1.0), mask_span=10, device='cuda', max_len=2048,
                  **kwargs):
         cfg = dict(kwargs)
@@ -124,6 +126,13 @@ class MaskDiT:
         vals = [int(v) for v in (lengths.reshape(-1).tolist() if torch.is_tensor(lengths) else lengths)]
         arr = (C.c_int32 * len(vals))(*vals)
         _lib.check(self.lib.ezdit_set_lengths(self._h, arr, len(vals), st))
+
+    def set_attention_window(self, frames):
+        """Sliding-window self-attention (ezdit_set_attention_window): every frame attends to the frames within ``frames`` of it, on either side.  None or 0
+        switches it off.  Stays with the model until it is changed; a window that covers the bound row runs the plain kernels, bit for bit."""
+        radius = 0 if frames is None else int(frames)
+        _lib.check(self.lib.ezdit_set_attention_window(self._h, radius))
+        self.attention_window = radius or None
 
     def prepare_timesteps(self, ts, per_row):
         arr = (C.c_int32 * len(ts))(*[int(t) for t in ts])

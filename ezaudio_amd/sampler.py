@@ -572,8 +572,15 @@ def inference_controlnet(autoencoder, unet, controlnet, gt, gt_mask, condition, 
 def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, noise_scheduler, text_raw,
               neg_text=None, audio_frames=500, guidance_scale=3, guidance_rescale=0.0, ddim_steps=50, eta=1,
               random_seed=2024, device='cuda', use_graph=True, controlnet=None, condition=None, conditioning_scale=1.0,
-              first_index=None, init_latents=None, strength=None, canvas_loop=None, decode_context=None, canvas_offsets=None, canvas_ramp=None, solver='ddim'):
+              first_index=None, init_latents=None, strength=None, attention_window=None, canvas_loop=None, decode_context=None, canvas_offsets=None, canvas_ramp=None,
+              solver='ddim'):
     """Same signature and semantics as the reference's ``inference`` (src/inference.py:26-107).
+
+    Extension (sliding-window self-attention): ``attention_window`` is a radius in latent frames: in every block's self-attention a frame attends to the frames
+    within that many frames of it, so a row longer than the trained length stays inside the trained range of relative positions.  It is set on ``unet`` (and on
+    ``controlnet``) before anything is prepared and the previous value is put back when the call ends, also when it raises; the shards of a distributed call run
+    on the same models and so under the same window.  It combines with everything below; a canvas' windows are short, so there it changes nothing.  Audio quality
+    on the real checkpoints is unmeasured.
 
     Extension: ``solver='dpmpp_2m'`` samples with DPM-Solver++(2M) instead of DDIM (deterministic: eta must be 0, the signature's
     default eta=1 is refused, not ignored).  How few steps give the quality of a longer DDIM run on the real checkpoints is unmeasured.
@@ -610,6 +617,21 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
     frames: window p holds the frames (canvas_offsets[p] + r) mod T, the last window runs into the first, and the default ramp is the smallest cyclic overlap.
     The ring is decoded as a ring (decode_circular, with ``decode_context`` wrapped frames on either side; None asks the autoencoder): the result is
     [1, 1, T * ratio], and its end continues into its beginning.  Everything else as with the line; audio quality on the real checkpoints is unmeasured."""
+    if attention_window is not None:
+        if isinstance(attention_window, bool) or int(attention_window) != attention_window or int(attention_window) < 1:
+            raise ValueError(f'attention_window is a radius in latent frames, a whole number >= 1: got {attention_window!r}')
+        models = [unet] + ([controlnet] if controlnet is not None else [])
+        previous = [getattr(m, 'attention_window', None) for m in models]
+        try:
+            for m in models:
+                m.set_attention_window(int(attention_window))
+            return inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, noise_scheduler, text_raw, neg_text, audio_frames, guidance_scale,
+                             guidance_rescale, ddim_steps, eta, random_seed, device, use_graph, controlnet, condition, conditioning_scale, first_index=first_index,
+                             init_latents=init_latents, strength=strength, canvas_loop=canvas_loop, decode_context=decode_context, canvas_offsets=canvas_offsets,
+                             canvas_ramp=canvas_ramp, solver=solver)
+        finally:
+            for m, prev in zip(models, previous):
+                m.set_attention_window(prev)
     if (init_latents is None) != (strength is None):
         raise ValueError('init_latents and strength must be given together')
     if neg_text is None:

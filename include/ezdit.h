@@ -588,6 +588,23 @@ int ezdit_debug_stop_after(ezdit_handle* h, int n_launches);
  * LayerNorm with neutral tables (what the consumer side costs by itself; results change by the factor rsqrt(1 + 1e-5)). */
 int ezdit_set_option(ezdit_handle* h, const char* name, int value);
 
+/* ---- Sliding-window self-attention ------------------------------------------------------------------------------------------------------------------------
+ * radius >= 1: in every block's SELF-attention frame i attends to the frames j with |i - j| <= radius (and j below the sample's length, ezdit_set_lengths) --
+ * 2 radius + 1 keys, so a row of any length stays inside the range of relative RoPE positions the model was trained on (radius 250 = the 501 keys of the
+ * trained 10 s row).  radius 0 = off (default).  Cross-attention, the single-key shortcut and everything else in the block are untouched: nothing else looks
+ * along the time axis.  Handle-scoped: it survives ezdit_bind_workspace and ezdit_sampler_begin.  With radius >= L - 1 of the bound row nothing is masked and the
+ * step launches exactly the kernels of radius 0 (same bits, same launch count); otherwise the self-attention launch of each block is the band form of k_attn
+ * (csrc/attn.hip BAND: it walks only the key tiles its queries can see), one launch as before.  A change drops the captured step, like ezdit_set_option.
+ * Accepted on backbone and ControlNet handles; ezdit_sampler_attach_controlnet refuses (EZDIT_E_INVALID) a pair whose radii differ -- set both before attaching.
+ * EZDIT_E_INVALID: radius < 0.  EZDIT_E_STATE: the handle's stream (that of its latest bind / sampler run) is being captured.
+ * Audio quality of windowed sampling on the released checkpoints is unmeasured. */
+int ezdit_set_attention_window(ezdit_handle* h, int radius);
+/* unit-test hook of the band form: self-attention (Lq = Lk = L, padded to Lp) with key j valid for query i iff |i - j| <= radius and j < klen[b] (L where dev_klen is
+ * NULL).  Buffer layouts, refusals and the klen read-back are those of ezdit_test_attention_varlen (no key mask); radius >= 1 is required (EZDIT_E_INVALID).  It ALWAYS
+ * launches the band instantiation, also for radius >= L - 1 where nothing is masked: that launch must equal ezdit_test_attention bit for bit. */
+int ezdit_test_attention_band(ezdit_handle* h, const void* dev_q, const void* dev_k, const void* dev_v, void* dev_out, int B, int L, int Lp,
+                              const int32_t* dev_klen, int radius, ezdit_stream stream);
+
 /* ---- T5 text encoder (csrc/t5.hip): stands in for transformers' T5EncoderModel in the `text_encoder` slot (api/ezaudio.py:80-82, src/inference.py:42-50) --------
  * Encoder stacks of the flan-t5 / T5 v1.1 family only: gated gelu_new feed-forward, head dim 64, no biases, T5LayerNorm (RMS), the bidirectional
  * relative-position bias of block 0 shared by all layers.  Same conventions as above: caller-owned device memory (one weight blob, one workspace per
