@@ -141,6 +141,14 @@ PROTOTYPES = {
     'ezdit_set_attention_window': (C.c_int, [C.c_void_p, C.c_int]),
     'ezdit_test_attention_band': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                             C.c_void_p]),
+    'ezdit_set_context_weights': (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
+    'ezdit_test_attention_timeline': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
+    'ezdit_test_cross_attention_timeline': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                      C.c_int, C.c_int, C.c_int, C.c_int,
+                                                      C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
+                                                      C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
 }
 
 

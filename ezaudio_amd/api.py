@@ -146,6 +146,32 @@ class EzAudio:
         pred = pred.squeeze(0).squeeze(0) if isinstance(text, str) or len(text) == 1 else pred.squeeze(1)
         return self.params['autoencoder']['sr'], pred
 
+    def generate_scene(self, scene, length, crossfade=1.0, guidance_scale=5, guidance_rescale=0.75, ddim_steps=100, eta=1, random_seed=None,
+                       randomize_seed=False, attention_window=None, solver='ddim'):
+        """ONE clip of `length` seconds whose prompt changes over time (prompt timeline): `scene` is a list of (text, start_s, end_s[, weight]) entries, which
+        may overlap; every latent frame weights the entries by their trapezoid envelopes (`crossfade` seconds per edge, sampler.scene_weights) in every block's
+        cross-attention, so prompts switch, cross-fade or mix inside the one sample.  Returns (sr, waveform).  A scene of one entry is generate_audio of that
+        text.  The other arguments as in generate_audio (one value each).  ValueError as scene_weights: an uncovered frame, an entry outside the clip, more than
+        16 entries.  Audio quality on the real checkpoints -- whether a cross-fade of the softmax prior sounds like one, which fade length to choose -- is unmeasured."""
+        from .sampler import scene_weights
+        latent_sr = self.params['autoencoder']['latent_sr']
+        frames = int(round(length * latent_sr))
+        prompts, weights = scene_weights(scene, frames, latent_sr, crossfade)
+        if len(prompts) == 1:
+            return self.generate_audio(prompts[0], length, guidance_scale, guidance_rescale, ddim_steps, eta, random_seed, randomize_seed,
+                                       attention_window=attention_window, solver=solver)
+        check_solver(solver, eta)
+        radius = self._window_radius(attention_window)
+        for name, v in (('guidance_scale', guidance_scale), ('guidance_rescale', guidance_rescale), ('eta', eta), ('random_seed', random_seed)):
+            if isinstance(v, (list, tuple)):
+                raise ValueError(f'a scene is one clip: one {name}')
+        if randomize_seed:
+            random_seed = random.randint(0, MAX_SEED)
+        pred = inference(self.autoencoder, self.unet, None, None, self.tokenizer, self.text_encoder, self.params, self.noise_scheduler, [prompts], None,
+                         frames, guidance_scale, guidance_rescale, ddim_steps, eta, random_seed, self.device, solver=solver, attention_window=radius,
+                         prompt_weights=[weights])
+        return self.params['autoencoder']['sr'], pred.cpu().numpy().squeeze(0).squeeze(0)
+
     def generate_long_audio(self, text, length, window=10, overlap=2.5, guidance_scale=5, guidance_rescale=0.75, ddim_steps=100, eta=1,
                             random_seed=None, randomize_seed=False, solver='ddim'):
         """A clip of `length` seconds, longer than the `window` seconds the model was trained on: the latent canvas is covered by overlapping windows of

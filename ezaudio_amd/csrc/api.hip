@@ -118,6 +118,11 @@ struct ezdit_handle {
     Table<int> lens;     // [B] padded batch (ezdit_set_lengths, ezdit_sampler_set_pair_lengths): batch element b is valid on frames [0, lens[b])
     const int* lens_dev() const { return lens.read(); }
     Table<float> cns;    // [B] conditioning_scale per batch element of the attached ControlNet (ezdit_sampler_set_cn_scales), read by the row kernel
+    // prompt timeline (ezdit_set_context_weights): the context is tl_S prompts of 128 keys and every frame weights them.  The mirror is [B][S][L] score biases (k_attn TL,
+    // AttnArgs.tlb), which go to `dev`, then [B][S] frame supports as int pairs (bit copies in the float mirror), which go to tlsup.  Read by the cross-attention launch only
+    Table<float> tl;
+    int2* tlsup = nullptr;
+    int tl_S = 0;
     // ---- call-scoped: they belong to one sampler call and are cleared by reset_call_state ----
     // per-sample sampler settings (ezdit_sampler_set_sample_params), read by k_cfg_stats / k_cfg_apply: the mirror is [P][2] (guidance_scale, guidance_rescale),
     // which goes to `dev`, then [n_steps][P][8] DDIM coefficients, which go to p.spc.  Room for sp_cap(B) samples: the B / 2 of a CFG batch
@@ -521,6 +526,8 @@ size_t carve(const ezdit_handle* h, int B, int L, int Lc, int n_slots, std::map<
         add("cns", 256 * sizeof(float));   // per-batch-element conditioning_scale (B <= 240), behind `lens` and the sample tables for the same reason: no existing buffer moves
         add("start", 256 * sizeof(int));   // per-sample first step (ezdit_sampler_set_start; P <= B <= 240), at the very end for the same reason: 1 KB
         add("canvas", 256 * sizeof(int));  // per-window first canvas frame (ezdit_sampler_set_canvas; P <= B <= 240), behind `start` for the same reason: 1 KB
+        add("tlb", (size_t)B * (Lcp / 128) * L * 4);     // prompt timeline (ezdit_set_context_weights): one score bias per (batch element, prompt, frame) and the prompts' frame
+        add("tlsup", (size_t)B * (Lcp / 128) * 8);       // supports, behind `canvas` for the same reason: B L 4 bytes at one prompt
     }
     return off;
 }
@@ -704,6 +711,7 @@ void resolve_workspace(ezdit_handle* h) {
     p.zd = h->buf<float>("zd"); p.spc = h->buf<float>("spc");
     h->lens.dev = h->buf<int>("lens"); h->cns.dev = h->buf<float>("cns"); h->sp.dev = h->buf<float>("spg"); h->coef.dev = p.coef;
     h->start.dev = h->buf<int>("start"); h->canvas.dev = h->buf<int>("canvas");
+    h->tl.dev = h->buf<float>("tlb"); h->tlsup = h->buf<int2>("tlsup");
     p.zstat = h->buf<float2>("zstat"); p.zt_qkv = h->buf<float>("zt_qkv"); p.zt_geglu = h->buf<float>("zt_geglu"); p.zt_q2 = h->buf<float>("zt_q2");
     p.zstat_skip = h->buf<float2>("zstat_skip"); p.zt_skip = h->buf<float>("zt_skip"); p.ucat_z = h->buf<bf16_t>("ucat_z");
     if (h->is_cn) { p.cembed = h->buf<float>("cembed"); p.cnres = h->buf<float>("cnres"); p.skipbf = h->buf<bf16_t>("skipbf"); }
@@ -775,6 +783,50 @@ int expand_lengths(const ezdit_handle* h, const int32_t* lengths, int n, std::ve
     return EZDIT_OK;
 }
 
+// The prompt timeline of B batch elements (include/ezdit.h, ezdit_set_context_weights): natural weights w [B][S][L] -> the table the TL form of k_attn reads,
+// [B][S][L] biases log2(w / max_s w) (TL_OFF for a weight of 0; the dominant prompt of a frame has exactly 0) followed by [B][S] supports (first, last + 1 frame of
+// weight > 0) as bit copies.  lens (nullable, [B]): the frames that exist; a frame beyond takes the last existing frame's column, whatever the caller left there, and
+// stands in the supports with it: a workgroup whose queries are all padding then walks the prompts of the last frame and its rows stay FINITE (a padding row that meets no
+// weighted key would end as 0 / 0, and the next block's self-attention passes masked keys through P . V with P = 0: 0 * NaN = NaN).  The range of a workgroup that holds
+// the last existing frame is not widened by this.  mask (nullable = every key valid, [B][128 S]): every existing frame needs a weight > 0 on a prompt that has a valid key -- its softmax has no
+// term otherwise -- which covers the single-key batch elements of the shortcut as well (their constant output is their prompt at every frame)
+int timeline_table(const float* w, int B, int S, int L, const int* lens, const uint8_t* mask, std::vector<float>* out) {
+    const size_t nb = (size_t)B * S * L;
+    out->assign(nb + (size_t)B * S * 2, 0.f);
+    std::vector<int> sup((size_t)B * S * 2, 0);
+    for (int b = 0; b < B; ++b) {
+        const int len = lens ? lens[b] : L;
+        bool has_key[TL_MAXS];
+        for (int s = 0; s < S; ++s) {
+            has_key[s] = !mask;
+            for (int j = 0; mask && j < 128 && !has_key[s]; ++j) has_key[s] = mask[((size_t)b * S + s) * 128 + j] != 0;
+        }
+        for (int i = 0; i < L; ++i) {
+            const int f = i < len ? i : len - 1;   // (a frame beyond the length: the last one that exists)
+            double mx = 0.0;
+            bool seen = false;
+            for (int s = 0; s < S; ++s) {
+                const float x = w[((size_t)b * S + s) * L + f];
+                if (!std::isfinite(x) || x < 0.f) return fail(EZDIT_E_INVALID, "weights[%d][%d][%d] = %g: a weight is finite and >= 0", b, s, f, (double)x);
+                mx = x > mx ? x : mx;
+                seen = seen || (x > 0.f && has_key[s]);
+            }
+            if (!seen) return fail(EZDIT_E_INVALID, "frame %d of batch element %d weights no prompt that has a valid key", f, b);
+            for (int s = 0; s < S; ++s) {
+                const float x = w[((size_t)b * S + s) * L + f];
+                (*out)[((size_t)b * S + s) * L + i] = x > 0.f ? (float)std::log2((double)x / mx) : TL_OFF;
+                if (x > 0.f) {
+                    int* fs = &sup[((size_t)b * S + s) * 2];
+                    if (fs[1] == 0) fs[0] = i;
+                    fs[1] = i + 1;
+                }
+            }
+        }
+    }
+    memcpy(out->data() + nb, sup.data(), sup.size() * sizeof(int));
+    return EZDIT_OK;
+}
+
 // A ControlNet handle carries a length table only as half of an attached pair (ezdit_sampler_set_pair_lengths): when the pair ends -- detach, or the
 // backbone is destroyed -- the table goes, and with it the condition embed that was computed from it.  The backbone keeps its own table.
 void clear_cn_lengths(ezdit_handle* cn) {
@@ -796,6 +848,7 @@ void reset_call_state(ezdit_handle* h) {
 void reset_bind_state(ezdit_handle* h) {
     h->lens.set(h, false); h->lens.host.clear();
     h->cns.set(h, false);
+    h->tl.set(h, false); h->tl.host.clear(); h->tl_S = 0;
     h->coef.host.clear();
     h->latents = nullptr; h->noise = nullptr; h->s_gt = nullptr; h->s_gt_mask = nullptr;
     h->P = 0; h->n_steps = 0;
@@ -944,6 +997,8 @@ int ezdit_prepare_context(ezdit_handle* h, const float* ctx, const uint8_t* mask
     uint8_t* km = h->buf<uint8_t>("kmask");
     if (mask) HIPCHK(hipMemcpyAsync(km, mask, Mc, hipMemcpyDeviceToDevice, c.st));
     else HIPCHK(hipMemsetAsync(km, 1, Mc, c.st));
+    // (the context weights were checked against the old mask: a new context starts without them.  Behind the first copy: a call refused above changes nothing)
+    h->tl.set(h, false); h->tl.host.clear(); h->tl_S = 0;
     // single-key batch elements (opt_xkey1): their cross-attention output is a constant.  The mask is read back once per call (B Lc bytes)
     std::vector<int> key1(h->B, -1);   // the valid key of a single-key batch element, -1 otherwise
     const bool old_x1 = h->xkey1; const int old_b0 = h->act_b0, old_b1 = h->act_b1;
@@ -1130,6 +1185,15 @@ int ezdit_set_step(ezdit_handle* h, int step, ezdit_stream stream) {
 int ezdit_set_lengths(ezdit_handle* h, const int32_t* lengths, int n, ezdit_stream stream) {
     hipStream_t st = (hipStream_t)stream;
     if (int rc = setter_checks(h, "ezdit_set_lengths", Needs::Bound, st)) return rc;
+    // (the timeline's table was built for the frames that existed when it was set: padding frames carry the last frame's weights and stand in no support)
+    if (h->tl.on) {   // (a call that leaves the lengths as they are is let through)
+        bool same = (!lengths || n == 0) ? !h->lens.on : false;
+        if (lengths && n > 0 && h->lens.on && n <= h->B && h->B % n == 0) {
+            same = true;
+            for (int b = 0; b < h->B; ++b) same = same && h->lens.host[b] == lengths[b % n];
+        }
+        if (!same) return fail(EZDIT_E_STATE, "new lengths while the context weights are on: ezdit_set_context_weights(NULL), the lengths, then the weights again");
+    }
     if (!lengths || n == 0) {
         if (h->is_cn) clear_cn_lengths(h);   // (a table the pair call left on a ControlNet: its embed goes with it)
         else { h->lens.set(h, false); h->lens.host.clear(); }
@@ -1143,6 +1207,32 @@ int ezdit_set_lengths(ezdit_handle* h, const int32_t* lengths, int n, ezdit_stre
     if (int rc = expand_lengths(h, lengths, n, &v)) return rc;
     if (int rc = upload_table(h->lens, std::move(v), st)) return rc;
     h->lens.set(h, true);
+    return EZDIT_OK;
+}
+
+// Prompt timeline: per-frame weights of the S prompts of the bound context (Lc = 128 S; prompt s = context rows [128 s, 128 s + 128)).  The table is checked against the
+// key mask of the latest ezdit_prepare_context and the lengths that are set, then read by the cross-attention launch of every block (k_attn TL)
+int ezdit_set_context_weights(ezdit_handle* h, const float* weights, int S, ezdit_stream stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (h && weights && h->is_cn) return fail(EZDIT_E_UNSUPPORTED, "context weights on a ControlNet handle");   // (whatever its state: the ControlNet has no timeline)
+    if (int rc = setter_checks(h, "ezdit_set_context_weights", Needs::Bound, st)) return rc;
+    if (!weights) {
+        h->tl.set(h, false); h->tl.host.clear(); h->tl_S = 0;
+        return EZDIT_OK;
+    }
+    if (h->cn) return fail(EZDIT_E_UNSUPPORTED, "context weights with a ControlNet attached");
+    if (h->canvas.on) return fail(EZDIT_E_UNSUPPORTED, "context weights while the canvas is on (ezdit_sampler_set_canvas): a window has one prompt");
+    if (S < 1 || S > TL_MAXS) return fail(EZDIT_E_INVALID, "S = %d outside [1, %d]", S, TL_MAXS);
+    if (h->Lc != 128 * S) return fail(EZDIT_E_INVALID, "S = %d prompts need a context of %d tokens (128 each), the workspace is bound to Lc = %d", S, 128 * S, h->Lc);
+    if (!h->ctx_ready) return fail(EZDIT_E_STATE, "ezdit_prepare_context first: the weights are checked against its key mask");
+    std::vector<uint8_t> km((size_t)h->Mc);
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(km.data(), h->p.kmask, km.size(), hipMemcpyDeviceToHost));
+    std::vector<float> v;
+    if (int rc = timeline_table(weights, h->B, S, h->L, h->lens.on ? h->lens.host.data() : nullptr, km.data(), &v)) return rc;
+    if (int rc = upload_table(h->tl, std::move(v), st, (size_t)h->B * S * h->L, reinterpret_cast<float*>(h->tlsup))) return rc;
+    h->tl.set(h, true);
+    h->tl_S = S;
     return EZDIT_OK;
 }
 
@@ -1417,6 +1507,7 @@ static int forward_impl(ezdit_handle* h, const float* x, int in_ch, int x_rows, 
             at.k = p.kc + (size_t)b * h->B * h->H * h->Lcp * h->DQK;
             at.v = p.vc + (size_t)b * h->B * h->H * h->Lcp * h->DV;
             at.kmask = p.kmask; at.klen = nullptr; at.band = 0;   // (the key lengths and the band are self-attention's: context keys have their own mask and no time axis)
+            at.tlb = h->tl.read(); at.tlsup = h->tl.on ? h->tlsup : nullptr;   // ... unless the prompt timeline gives them one (ezdit_set_context_weights): the TL form, the same single launch
             at.Lk = h->Lc; at.Lkp = h->Lcp;
             STOPCHK();
             at.ts = c.stamps(); at.ts_cap = g_gemm_ts_cap;
@@ -1565,6 +1656,7 @@ int ezdit_sampler_attach_controlnet(ezdit_handle* h, ezdit_handle* cn, float con
     if (!h || h->is_cn) return fail(EZDIT_E_INVALID, "first argument must be a backbone handle");
     if (cn && !cn->is_cn) return fail(EZDIT_E_INVALID, "second argument must be a ControlNet handle");
     if (cn && h->canvas.on) return fail(EZDIT_E_UNSUPPORTED, "a ControlNet while the canvas is on (ezdit_sampler_set_canvas)");
+    if (cn && h->tl.on) return fail(EZDIT_E_UNSUPPORTED, "a ControlNet while the context weights are on (ezdit_set_context_weights)");
     if (cn && cn->attn_window != h->attn_window)
         return fail(EZDIT_E_INVALID, "attention windows differ: backbone %d, ControlNet %d frames (ezdit_set_attention_window on both)", h->attn_window, cn->attn_window);
     if (h->cn && h->cn != cn) {
@@ -1815,6 +1907,7 @@ static int set_canvas_table(ezdit_handle* h, const char* who, const int32_t* off
     if (h->start.on) return fail(EZDIT_E_UNSUPPORTED, "a canvas with a start table (ezdit_sampler_set_start)");
     if (h->s_gt) return fail(EZDIT_E_UNSUPPORTED, "a canvas with gt / gt_mask: long edits are not implemented");
     if (h->cn) return fail(EZDIT_E_UNSUPPORTED, "a canvas with a ControlNet attached");
+    if (h->tl.on) return fail(EZDIT_E_UNSUPPORTED, "a canvas with context weights (ezdit_set_context_weights): a window has one prompt");
     if (int rc = upload_table(h->canvas, std::vector<int>(offsets, offsets + P), st)) return rc;
     h->canvas.set(h, true, T != h->canvas_T || ramp != h->canvas_ramp || loop != h->canvas_loop);   // (T and the ramp are kernel arguments; the other form is another kernel)
     h->canvas_T = T; h->canvas_ramp = ramp; h->canvas_loop = loop;
@@ -2138,6 +2231,73 @@ int ezdit_test_attention_band(ezdit_handle* h, const void* q, const void* k, con
     a.klen = dev_klen;
     a.band = radius;
     return hook_launch("k_attn", "attention configuration", [&] { return launch_attention(a, (hipStream_t)stream); });
+}
+
+// the timeline form, stand-alone: what both hooks share.  The key mask is read back (a test hook may wait), the table is built and checked as the setter does it
+// (lens none), lives in device memory of the hook's own for the launch of the batch elements [b0, b0 + B), and goes when the launch is done
+static int timeline_hook(AttnArgs& a, const float* weights, int S, hipStream_t st) {
+    if (!weights) return fail(EZDIT_E_INVALID, "null weights");
+    if (S < 1 || S > TL_MAXS) return fail(EZDIT_E_INVALID, "S = %d outside [1, %d]", S, TL_MAXS);
+    if (a.Lk != 128 * S || a.Lkp != a.Lk) return fail(EZDIT_E_INVALID, "S = %d prompts are Lk = Lkp = %d keys, not Lk = %d, Lkp = %d", S, 128 * S, a.Lk, a.Lkp);
+    if (a.B <= 0 || a.b0 < 0 || a.Lq <= 0) return fail(EZDIT_E_INVALID, "bad shape B=%d b0=%d Lq=%d", a.B, a.b0, a.Lq);
+    std::vector<uint8_t> km;
+    HIPCHK(hipStreamSynchronize(st));
+    if (a.kmask) {
+        km.resize((size_t)a.B * a.Lk);
+        HIPCHK(hipMemcpy(km.data(), a.kmask + (size_t)a.b0 * a.Lk, km.size(), hipMemcpyDeviceToHost));
+    }
+    std::vector<float> v;
+    if (int rc = timeline_table(weights, a.B, S, a.Lq, nullptr, a.kmask ? km.data() : nullptr, &v)) return rc;
+    const size_t nb = (size_t)a.B * S * a.Lq, ns = (size_t)a.B * S * 2, skip_b = (size_t)a.b0 * S * a.Lq, skip_s = (size_t)a.b0 * S * 2;
+    float* dev = nullptr;   // [b0 + B][S][Lq] biases | [b0 + B][S] supports: launch_attention advances both by b0 batch elements
+    const size_t sup_at = (skip_b + nb + 1) & ~(size_t)1;   // (the supports are read as 8-byte pairs)
+    HIPCHK(hipMalloc(&dev, (sup_at + skip_s + ns) * sizeof(float)));
+    float* dsup = dev + sup_at;
+    hipError_t e = hipMemcpy(dev + skip_b, v.data(), nb * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dsup + skip_s, v.data() + nb, ns * sizeof(float), hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? EZDIT_OK : fail(EZDIT_E_HIP, "upload of the timeline table failed: %s", hipGetErrorString(e));
+    if (!rc) {
+        a.tlb = dev; a.tlsup = reinterpret_cast<const int2*>(dsup);
+        rc = hook_launch("k_attn (timeline)", "attention configuration", [&] { return launch_attention(a, st); });
+    }
+    const hipError_t es = hipStreamSynchronize(st);
+    (void)hipFree(dev);
+    if (!rc && es != hipSuccess) rc = fail(EZDIT_E_HIP, "k_attn (timeline) failed: %s", hipGetErrorString(es));
+    return rc;
+}
+
+// the timeline form of the plain 8-wave kernel (the q2_pp / q_raw paths of cross-attention).  ALWAYS the TL instantiation, also for S = 1 with every weight 1: that run
+// is what compares it with ezdit_test_attention on equal inputs
+int ezdit_test_attention_timeline(ezdit_handle* h, const void* q, const void* k, const void* v, const uint8_t* kmask, void* out, int B,
+                                  int Lq, int Lk, int Lqp, int Lkp, const float* weights, int S, ezdit_stream stream) {
+    if (int rc = attn_hook_refusals(h, q, k, v, kmask, out, B, Lq, Lk, Lqp, Lkp, (hipStream_t)stream)) return rc;
+    AttnArgs a;
+    memset(&a, 0, sizeof a);
+    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.kmask = kmask;
+    a.nkh = 4; a.xcd_map = h->opt_attn_xcd;
+    a.out = (bf16_t*)out; a.ldo = h->ldD;
+    a.B = B; a.H = h->H; a.Lq = Lq; a.Lk = Lk; a.Lqp = Lqp; a.Lkp = Lkp; a.dh = h->dh;
+    return timeline_hook(a, weights, S, (hipStream_t)stream);
+}
+
+// ... and of the fused-projection forms with the LayerNorm algebra: the arguments of ezdit_test_cross_attention, then weights [B][S][Lq] (HOST) of the launched batch elements
+int ezdit_test_cross_attention_timeline(const void* xu, int ldu, const void* xw, int ldw, int xw_rows, int xK, const float* qn_w, const float* qn_b,
+                                        const void* k, const void* v, const uint8_t* kmask, void* out, int ldo, int B, int b0, int H, int dh, int Lq, int Lk, int Lqp, int Lkp,
+                                        const void* zstat_in, long zs_stride, int zparts, int zD, int zw, const float* zG, const float* zC, float zeps,
+                                        int xk2, int qtile, int xcd_map, const float* weights, int S, ezdit_stream stream) {
+    if (!xu || !xw || xK <= 0 || xK % 64) return fail(EZDIT_E_INVALID, "the fused projection needs xu, xw and xK a multiple of 64");
+    if (!k || !v || !out || !zstat_in) return fail(EZDIT_E_INVALID, "null k, v, out or statistics");
+    if (qtile != 32 && qtile != 64) return fail(EZDIT_E_INVALID, "qtile = %d: 32 or 64", qtile);
+    if (qtile == 32 && (!xcd_map || (xK / 64) % 2)) return fail(EZDIT_E_INVALID, "qtile = 32 needs the XCD map and an even number of K tiles");
+    AttnArgs a;
+    memset(&a, 0, sizeof a);
+    a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.kmask = kmask;
+    a.out = (bf16_t*)out; a.ldo = ldo;
+    a.B = B; a.b0 = b0; a.H = H; a.Lq = Lq; a.Lk = Lk; a.Lqp = Lqp; a.Lkp = Lkp; a.dh = dh;
+    a.xu = (const bf16_t*)xu; a.ldu = ldu; a.xw = (const bf16_t*)xw; a.ldw = ldw; a.xw_rows = xw_rows; a.xK = xK;
+    a.qn_w = qn_w; a.qn_b = qn_b; a.nkh = 4; a.xk2 = xk2; a.qtile = qtile; a.xcd_map = xcd_map;
+    a.zstat_in = (const float2*)zstat_in; a.zs_stride = zs_stride; a.zparts = zparts; a.zD = zD; a.zw = zw; a.zG = zG; a.zC = zC; a.zeps = zeps;
+    return timeline_hook(a, weights, S, (hipStream_t)stream);
 }
 
 int ezdit_test_final_conv(const float* y, int ldy, const float* w, const float* b, float* out, int B, int C, int L, const int32_t* dev_lens,

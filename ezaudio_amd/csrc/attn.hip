@@ -62,8 +62,11 @@ struct HeadGeom<72> { static constexpr int DQK = 80, DV = 96; };
 // waves split K in the projection (one 16-wide k-step of a double stage each); the attention proper runs on waves 0 - 3 (one query sub-block x 4 key sub-blocks)
 // BAND: sliding-window self-attention (AttnArgs.band): key j exists for query i iff |i - j| <= band.  A template switch like ZQ: the plain kernel carries neither
 // its registers nor its code.  Plain self-attention only (no query prologue, no key mask, Lq == Lk); what changes is marked "band:" below
-template <int DH, int NKH, bool ZQ = false, int QT = 64, bool BAND = false>
+// TL: prompt timeline of cross-attention (AttnArgs.tlb / tlsup): key tile t IS prompt t (128 keys), and query i sees it under the additive score bias
+// tlb[b][t][i] = log2(w / max_s w) -- or not at all (weight 0).  A template switch like ZQ and BAND; the 8-wave form only (128-key tiles); what changes is marked "timeline:" below
+template <int DH, int NKH, bool ZQ = false, int QT = 64, bool BAND = false, bool TL = false>
 __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
+    static_assert(!TL || (NKH == 4 && !BAND), "the timeline: one prompt per 128-key tile, cross-attention only");
     static_assert(QT == 64 || (QT == 32 && NKH == 4), "32-query tiles: the 8-wave fused-projection form only");
     static_assert(!BAND || (!ZQ && QT == 64), "the band exists in the plain self-attention form only");
     constexpr int NQS = QT / 32;   // query sub-blocks (of 32 rows) per workgroup
@@ -517,6 +520,27 @@ __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
     // band: the tile loop and its register prefetch run over [t_lo, t_hi), the key tiles that hold a key within `band` of one of the workgroup's 64 queries
     // (workgroup-uniform; qt * QT < Lk here, so t_lo < t_hi <= ntiles).  The LDS double-buffer parity follows t - t_lo: tile t_lo is staged into buffer 0
     int band = 0, t_lo = 0, t_hi = ntiles;
+    // timeline: [t_lo, t_hi) = the first to the last prompt whose frame support (tlsup[b][t] = first, last + 1 frame of weight > 0) meets the existing queries of this
+    // workgroup (rows >= Lq are padding).  Workgroup-uniform, scalar loads, before the first tile is staged.  The setter guarantees every existing frame a weighted prompt,
+    // (padding frames behind a length included: they carry the last frame's weights), so the range is never empty; a table that leaves it empty walks tile 0 at
+    // bias 0, so that no row ends as 0 / 0 (no address depends on the table's values)
+    [[maybe_unused]] const float* tlrow = nullptr;   // timeline: &tlb[b][0][this lane's query]; padding queries take the last existing query's weights, so they are in no class
+    [[maybe_unused]] float tbias = 0.f, tbias_nx = 0.f;
+    if constexpr (TL) {
+        const int qa = qt * QT, qb = qa + QT < Lq_ ? qa + QT : Lq_;
+        const int2* sup = a.tlsup + (long)b * ntiles;
+        int lo = ntiles, up = 0;
+        for (int s = 0; s < ntiles; ++s) {
+            const int2 fs = sup[s];
+            if (fs.x < qb && fs.y > qa) { lo = lo < s ? lo : s; up = s + 1; }
+        }
+        t_lo = __builtin_amdgcn_readfirstlane(lo); t_hi = __builtin_amdgcn_readfirstlane(up);
+        const bool none = t_lo >= t_hi;
+        if (none) { t_lo = 0; t_hi = 1; }
+        const int qi = q0 + r32 < Lq_ ? q0 + r32 : Lq_ - 1;
+        tlrow = a.tlb + (long)b * ntiles * Lq_ + qi;
+        tbias = none ? 0.f : tlrow[(long)t_lo * Lq_];
+    }
     if constexpr (BAND) {
         band = a.band;
         // (queries >= Lk are padding: the range ends with the last query that exists.  launch_attention bounds band by Lk: no overflow)
@@ -529,7 +553,10 @@ __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
     __syncthreads();
     if (ts && lane == 0) ts[1] = __builtin_readcyclecounter();
     for (int t = t_lo; t < t_hi; ++t) {
-        if (t + 1 < t_hi) LOAD_TILE(t + 1);
+        if (t + 1 < t_hi) {
+            LOAD_TILE(t + 1);
+            if constexpr (TL) tbias_nx = tlrow[(long)(t + 1) * Lq_];   // timeline: the lane's bias of the next tile rides with its K / V
+        }
         const char* kb = smem + ((t - t_lo) & 1) * BUF;
         const char* vb = kb + KBYTES;
         const char* vtr = vb + (32 * kh + 4 * hi + ((lane & 15) >> 2)) * VSTR + ((lane & 16) + 4 * (lane & 3)) * 2;   // this lane's corner of the transposing reads
@@ -538,6 +565,9 @@ __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
         bool run = active && key0 < Lk;  // wave-uniform: the whole 32-key sub-tile may lie beyond Lk (32-query tiles: waves 4 - 7 only stage)
         const int qlast = q0 + 31 < Lk ? q0 + 31 : Lk - 1;   // band: the last query of the wave that exists (rows >= Lk are padding: never stored, or stored as zeros)
         if constexpr (BAND) run = run && key0 - qlast <= band && q0 - (key0 + 31) <= band;
+        // timeline: the lane's query weights this prompt above 0 (the stored bias of a zero weight is TL_OFF).  A tile that none of the wave's 32 queries weights is skipped (wave-uniform)
+        [[maybe_unused]] bool wpos = true;
+        if constexpr (TL) { wpos = tbias > 0.5f * TL_OFF; run = run && __ballot(wpos) != 0; }
         if (run) {
             uint32_t tmask;
             bool full;
@@ -566,6 +596,8 @@ __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
             // by VALU issue (~300 instructions per wave and tile against 11 MFMAs, tools/microbench/attn_bench.cpp), so the common case
             // drops the per-element mask selects and folds scale and reference max into one FMA feeding exp2.
             full = ball == 0xffffffffu;
+            // timeline: a zero weight takes P = 0 through the validity select, never through the exponent (the band's rule above); the mask-free path needs every query weighted
+            if constexpr (TL) { tmask = wpos ? tmask : 0u; full = full && __all(wpos); }
             }
             // S^T in VGPRs (the softmax reads every element once: through AGPRs that is 16 v_accvgpr_read per tile), written by inline-asm
             // MFMAs so that the register class is ours to choose.  The wait states hipcc would insert are inside the strings: 2 in front
@@ -588,11 +620,13 @@ __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, s[r]);
                 tmax *= c;   // c > 0: max(c s) == c max(s), rounding included
+                if constexpr (TL) tmax += tbias;   // timeline: the bias is per (query, tile): one add behind the maximum (a bias of 0 changes no bit)
             } else {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const bool v = (tmask >> ((r & 3) + 8 * (r >> 2))) & 1u;
-                    s[r] = v ? s[r] * c : -1e30f;
+                    if constexpr (TL) s[r] = v ? s[r] * c + tbias : -1e30f;
+                    else s[r] = v ? s[r] * c : -1e30f;
                     tmax = fmaxf(tmax, s[r]);
                 }
             }
@@ -613,7 +647,8 @@ __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
             float psum = 0.f;
             float p[16];
             if (full) {
-                const f32x2 c2 = {c, c}, nm2 = {-m, -m};
+                const float nm = TL ? tbias - m : -m;   // timeline: the bias folds into the FMA that feeds exp2
+                const f32x2 c2 = {c, c}, nm2 = {nm, nm};
                 f32x2 ps2 = {0.f, 0.f};
 #pragma unroll
                 for (int r = 0; r < 16; r += 2) {
@@ -657,6 +692,7 @@ __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
             }
         }
         if (t + 1 < t_hi) WRITE_TILE((t + 1 - t_lo) & 1);
+        if constexpr (TL) tbias = tbias_nx;
         __syncthreads();
     }
 
@@ -744,6 +780,7 @@ int launch_attention(const AttnArgs& a0, hipStream_t st) {
         if (a.xu) a.xu += b0 * a.Lq * a.ldu;
         if (a.zstat_in) a.zstat_in += b0 * a.Lq;
         if (a.klen) a.klen += b0;
+        if (a.tlb) { a.tlb += b0 * (a.Lkp / 128) * a.Lq; a.tlsup += b0 * (a.Lkp / 128); }
         a.b0 = 0;
     }
     const long nwg64 = (long)((a.Lq + 63) / 64) * a.H * a.B;
@@ -754,6 +791,10 @@ int launch_attention(const AttnArgs& a0, hipStream_t st) {
     if (a.dh != 64 && a.dh != 72) return 1;
     if (a.klen && (a.xu || a.q_raw || a.Lq != a.Lk)) return 1;   // per-batch-element lengths: plain self-attention only
     if (a.band < 0 || (a.band > 0 && (a.xu || a.q_raw || a.kmask || a.Lq != a.Lk))) return 1;   // the band: plain self-attention only
+    // the timeline: cross-attention over whole 128-key prompts, the 8-wave form
+    if ((a.tlb != nullptr) != (a.tlsup != nullptr)) return 1;
+    if (a.tlb && (a.klen || a.band > 0 || a.Lk != a.Lkp || a.Lkp % 128 || a.Lkp / 128 > TL_MAXS)) return 1;
+    if (a.tlb) nkh = 4;
     if (a.band > a.Lk) a.band = a.Lk;   // (the same mask: keeps the kernel's tile-range arithmetic far from overflow)
     const bool zq = a.xu && a.zstat_in;
     if (zq && !(a.zG && a.zC && a.zparts > 0 && a.zparts <= Z_MAXP && a.zs_stride > 0 && a.zw > 0)) return 1;
@@ -767,6 +808,19 @@ int launch_attention(const AttnArgs& a0, hipStream_t st) {
     dim3 grid(a.nq, a.H, a.B);
     if (a.xcd_map) grid = dim3(8 * a.ppx * a.nq, 1, 1);
     if (a.ts && (long)grid.x * grid.y * grid.z > a.ts_cap) a.ts = nullptr;   // the stamp buffer has no room for this grid
+    if (a.tlb) {
+        if (q32) {
+            if (a.dh == 64) hipLaunchKernelGGL((k_attn<64, 4, true, 32, false, true>), grid, dim3(512), 0, st, a);
+            else hipLaunchKernelGGL((k_attn<72, 4, true, 32, false, true>), grid, dim3(512), 0, st, a);
+        } else if (zq) {
+            if (a.dh == 64) hipLaunchKernelGGL((k_attn<64, 4, true, 64, false, true>), grid, dim3(512), 0, st, a);
+            else hipLaunchKernelGGL((k_attn<72, 4, true, 64, false, true>), grid, dim3(512), 0, st, a);
+        } else {
+            if (a.dh == 64) hipLaunchKernelGGL((k_attn<64, 4, false, 64, false, true>), grid, dim3(512), 0, st, a);
+            else hipLaunchKernelGGL((k_attn<72, 4, false, 64, false, true>), grid, dim3(512), 0, st, a);
+        }
+        return 0;
+    }
     if (q32) {
         if (a.dh == 64) hipLaunchKernelGGL((k_attn<64, 4, true, 32>), grid, dim3(512), 0, st, a);
         else hipLaunchKernelGGL((k_attn<72, 4, true, 32>), grid, dim3(512), 0, st, a);

@@ -308,7 +308,14 @@ struct AttnArgs {
     // sliding-window self-attention (0 = off): key j exists for query i iff |i - j| <= band (and j < klen[b] / Lk).  Another instantiation of k_attn (BAND), which
     // walks only the key tiles that reach the band of its 64 queries.  Plain self-attention only: no kmask, no query prologue, Lq == Lk.  Behind klen, for the same reason
     int band;
+    // prompt timeline of cross-attention (null = off; both or neither): the context is S = Lkp / 128 prompts of 128 keys each (Lk == Lkp), key tile t is prompt t.
+    // tlb [B][S][Lq] fp32: the score bias log2(w / max_s w) of query frame i on prompt t in log2 units, TL_OFF for a weight of 0 (that prompt does not exist for the frame);
+    // tlsup [B][S] = (first, last + 1) frame with a weight > 0 ((0, 0): none): a workgroup walks only the prompts whose support meets its queries.  Another instantiation
+    // of k_attn (TL), the 8-wave form.  Read at run time: one captured graph serves every set of weights.  Behind band, for the same reason
+    const float* tlb; const int2* tlsup;
 };
+constexpr float TL_OFF = -1e30f;   // stored bias of a zero weight (never added to a score: the validity select takes it)
+constexpr int TL_MAXS = 16;        // prompts of a timeline
 int launch_attention(const AttnArgs& a, hipStream_t st);   // 0 = launched, nonzero = configuration not supported
 
 void launch_row(const RowArgs& a, hipStream_t st);

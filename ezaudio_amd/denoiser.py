@@ -127,6 +127,22 @@ class MaskDiT:
         arr = (C.c_int32 * len(vals))(*vals)
         _lib.check(self.lib.ezdit_set_lengths(self._h, arr, len(vals), st))
 
+    def set_context_weights(self, weights, stream=None):
+        """Prompt timeline (ezdit_set_context_weights): ``weights`` [B, S, L] >= 0, the weight of prompt s (context rows [128 s, 128 s + 128) of the bound
+        context, Lc = 128 S) at latent frame i of batch row b; None switches it off.  After prepare_context and set_lengths, which it is checked against."""
+        st = _stream() if stream is None else stream
+        if weights is None:
+            _lib.check(self.lib.ezdit_set_context_weights(self._h, None, 0, st))
+            return
+        w = torch.as_tensor(weights, dtype=torch.float32).cpu().contiguous()
+        if w.dim() != 3:
+            raise ValueError(f'context weights must be [B, S, L], got {tuple(w.shape)}')
+        B, L, Lc, _ = self._ws_key or (0, 0, 0, 0)
+        if w.shape[0] != B or w.shape[2] != L:
+            raise ValueError(f'context weights {tuple(w.shape)} for a binding of B = {B} rows and L = {L} frames')
+        arr = C.cast(C.c_void_p(w.data_ptr()), C.POINTER(C.c_float))   # (the call reads the host tensor and waits: `w` outlives it)
+        _lib.check(self.lib.ezdit_set_context_weights(self._h, arr, int(w.shape[1]), st))
+
     def set_attention_window(self, frames):
         """Sliding-window self-attention (ezdit_set_attention_window): every frame attends to the frames within ``frames`` of it, on either side.  None or 0
         switches it off.  Stays with the model until it is changed; a window that covers the bound row runs the plain kernels, bit for bit."""
@@ -147,7 +163,7 @@ class MaskDiT:
         return t if shape is None else t[:int(np.prod(shape))].reshape(shape)
 
     # -- forward ------------------------------------------------------------------------------------
-    def _run(self, x, timesteps, context, context_mask, gt, gt_mask, controlnet_skips, in_ch, x_lens=None):
+    def _run(self, x, timesteps, context, context_mask, gt, gt_mask, controlnet_skips, in_ch, x_lens=None, context_weights=None):
         B, _, L = x.shape
         Lc = context.shape[1]
         if context.shape[0] != B:
@@ -161,6 +177,8 @@ class MaskDiT:
         self.prepare_context(context, context_mask)
         self.prepare_timesteps(t_list, per_row)
         self.set_lengths(x_lens)
+        if context_weights is not None:   # (prepare_context above switched an earlier call's table off)
+            self.set_context_weights(context_weights)
         x = x.to(self.device, torch.float32).contiguous()
         gt_d = None if gt is None else gt.to(self.device, torch.float32).contiguous()
         gm_d = None if gt_mask is None else gt_mask.to(self.device).expand(B, self.C, L).to(torch.uint8).contiguous()
@@ -176,10 +194,13 @@ class MaskDiT:
         return out
 
     def forward(self, x, timesteps, context, x_mask=None, context_mask=None, cls_token=None, gt=None,
-                mae_mask_infer=None, forward_model=True, x_lens=None):
+                mae_mask_infer=None, forward_model=True, x_lens=None, context_weights=None):
         """``x_lens`` (list / int tensor [B]): x, gt and mae_mask_infer are padded to L = max(x_lens) frames, row b is valid on [0, x_lens[b]); its
         valid output frames are what a call with that row alone computes, output frames beyond are exactly 0, and whatever the padded
-        region of the inputs holds is ignored (include/ezdit.h ezdit_set_lengths)."""
+        region of the inputs holds is ignored (include/ezdit.h ezdit_set_lengths).
+
+        ``context_weights`` [B, S, L] (prompt timeline, include/ezdit.h ezdit_set_context_weights): ``context`` is [B, 128 S, Cctx], S prompts of 128 rows
+        each (sampler.timeline_context builds it), and frame i of row b weights prompt s by context_weights[b, s, i] in every block's cross-attention."""
         if x_mask is not None:
             raise NotImplementedError(_X_MASK_MSG)
         if cls_token is not None:
@@ -191,7 +212,7 @@ class MaskDiT:
             me = self._mask_embed.view(1, -1, 1).to(x.device).expand_as(x)
             g = me if gt is None else torch.where(mae_mask_infer.expand_as(gt), me, gt)
             return torch.cat([x, g, mae_mask[:, 0:1, :]], dim=1), mae_mask
-        pred = self._run(x, timesteps, context, context_mask, gt, mae_mask_infer, None, in_ch=self.C, x_lens=x_lens)
+        pred = self._run(x, timesteps, context, context_mask, gt, mae_mask_infer, None, in_ch=self.C, x_lens=x_lens, context_weights=context_weights)
         return pred, mae_mask
 
     __call__ = forward

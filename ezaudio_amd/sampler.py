@@ -46,6 +46,65 @@ def _collapse(value, n_prompts, name):
     return None, vals
 
 
+TIMELINE_SEG = 128     # context rows of one prompt of a timeline: one key tile of the cross-attention kernel (csrc/attn.hip TL)
+TIMELINE_MAX = 16      # prompts of one timeline
+
+
+def scene_weights(scene, frames, latent_sr, crossfade):
+    """The prompt timeline of a scene: ``scene`` is a list of (text, start_s, end_s[, weight]) entries, which may overlap; the clip has ``frames`` latent frames at
+    ``latent_sr`` frames per second.  Each entry gets a trapezoid envelope of height ``weight`` (default 1) whose edges rise and fall linearly over ``crossfade``
+    seconds, centred on start_s and end_s -- so two entries that meet cross-fade with a constant sum -- except an edge that sits on the clip's own edge, which is
+    not ramped.  Envelopes are sampled at the frame centres (i + 0.5) / latent_sr; a frame's weights are the envelopes divided by their sum.
+    Returns (prompts, W): the S texts and a float32 tensor [S, frames] whose columns sum to 1.  ValueError: a frame that no entry covers, an entry outside the
+    clip (or empty, or of weight <= 0), more than TIMELINE_MAX entries.  Whether a cross-fade of the softmax prior sounds like one is unmeasured."""
+    frames, sr, cf = int(frames), float(latent_sr), float(crossfade)
+    if frames < 1 or sr <= 0 or cf < 0:
+        raise ValueError(f'frames={frames}, latent_sr={latent_sr}, crossfade={crossfade}: a clip has frames, a rate above 0 and a crossfade of at least 0')
+    if not scene or len(scene) > TIMELINE_MAX:
+        raise ValueError(f'a scene has between 1 and {TIMELINE_MAX} entries, got {len(scene) if scene else 0}')
+    dur = frames / sr
+    eps = 0.5 / sr      # an edge within half a frame of the clip's edge sits on it
+    t = (torch.arange(frames, dtype=torch.float64) + 0.5) / sr
+    prompts, env = [], []
+    for n, e in enumerate(scene):
+        if len(e) not in (3, 4):
+            raise ValueError(f'scene entry {n}: (text, start_s, end_s[, weight]), got {e!r}')
+        text, a, b, wt = e[0], float(e[1]), float(e[2]), float(e[3]) if len(e) == 4 else 1.0
+        if a < -eps or b > dur + eps or b <= a:
+            raise ValueError(f'scene entry {n} [{a:g} s, {b:g} s) lies outside the clip of {dur:g} s or is empty')
+        if not wt > 0 or wt == float('inf'):
+            raise ValueError(f'scene entry {n}: weight {wt!r} must be positive and finite')
+        if cf > 0:
+            rise = torch.ones_like(t) if a <= eps else ((t - a) / cf + 0.5).clamp(0, 1)
+            fall = torch.ones_like(t) if b >= dur - eps else ((b - t) / cf + 0.5).clamp(0, 1)
+        else:
+            rise, fall = (t >= a - 1e-9).double(), (t < b - 1e-9).double() if b < dur - eps else torch.ones_like(t)
+        prompts.append(text)
+        env.append(wt * torch.minimum(rise, fall))
+    env = torch.stack(env)
+    tot = env.sum(0)
+    if bool((tot <= 0).any()):
+        i = int((tot <= 0).nonzero()[0])
+        raise ValueError(f'no scene entry covers frame {i} ({(i + 0.5) / sr:g} s)')
+    return prompts, (env / tot).float()
+
+
+def timeline_context(text, text_mask):
+    """The 128-aligned context of a timeline: text [.., S, Lt, Cctx] and its mask [.., S, Lt] (Lt <= TIMELINE_SEG tokens per prompt) -> ([.., 128 S, Cctx],
+    [.., 128 S]): prompt s occupies the rows [128 s, 128 s + Lt), the rows behind are zeros with mask 0."""
+    S, Lt = text.shape[-3], text.shape[-2]
+    if Lt > TIMELINE_SEG:
+        raise ValueError(f'{Lt} tokens per prompt: a timeline holds at most {TIMELINE_SEG}')
+    if S > TIMELINE_MAX or tuple(text_mask.shape) != tuple(text.shape[:-1]):
+        raise ValueError(f'text {tuple(text.shape)} / mask {tuple(text_mask.shape)}: at most {TIMELINE_MAX} prompts, one mask entry per token')
+    lead = tuple(text.shape[:-3])
+    ctx = torch.zeros(lead + (S, TIMELINE_SEG, text.shape[-1]), dtype=text.dtype, device=text.device)
+    msk = torch.zeros(lead + (S, TIMELINE_SEG), dtype=torch.bool, device=text.device)
+    ctx[..., :Lt, :] = text
+    msk[..., :Lt] = text_mask.bool()
+    return ctx.reshape(lead + (S * TIMELINE_SEG, text.shape[-1])), msk.reshape(lead + (S * TIMELINE_SEG,))
+
+
 SOLVERS = ('ddim', 'dpmpp_2m')
 
 
@@ -70,7 +129,7 @@ class LatentSampler:
 
     def prepare(self, text, text_mask, uncond_text, uncond_mask, init_noise, step_noises, guidance_scale,
                 guidance_rescale, ddim_steps, eta, gt=None, gt_mask=None, controlnet=None, condition=None,
-                conditioning_scale=1.0, lengths=None, init_latents=None, start_steps=None, latent_scale=1.0, latent_shift=0.0, canvas=None,
+                conditioning_scale=1.0, lengths=None, init_latents=None, start_steps=None, latent_scale=1.0, latent_shift=0.0, context_weights=None, canvas=None,
                 canvas_loop=None, solver='ddim'):
         """``lengths`` (list of P ints): init_noise / step_noises / gt / gt_mask are padded to L = max(lengths) frames and sample p is valid on
         [0, lengths[p]) -- its final latent is what a call with that sample alone at its own length gives, zero beyond (include/ezdit.h
@@ -104,8 +163,26 @@ class LatentSampler:
         ``canvas_loop=(offsets, T, ramp)`` (seamless loops; not together with ``canvas``): the canvas is a RING of T >= L frames, window p holding the frames
         (offsets[p] + r) mod T for r in [0, L), so the last window runs into the first (loop_windows() chooses such offsets; draw_noises(canvas_loop=) cuts
         one ring noise for them).  The step ends with the wrap blend (ezdit_sampler_set_canvas_loop: the same table as ``canvas``, the same refusals), and
-        canvas_latents() reads the [1, C, T] ring, whose last frame continues into its first."""
+        canvas_latents() reads the [1, C, T] ring, whose last frame continues into its first.
+
+        ``context_weights`` [P, S, L] (prompt timeline, include/ezdit.h ezdit_set_context_weights): ``text`` is then [P, S, Lt, Cctx] and ``text_mask`` [P, S, Lt],
+        S prompts per sample, and frame i of sample p weights prompt s by context_weights[p, s, i] in every block's cross-attention (scene_weights() makes such
+        weights).  The 128-aligned context is built here; the unconditional rows keep their tokens in prompt 0 and weight it alone.  Not with a canvas, a loop or a
+        ControlNet."""
         check_solver(solver, eta)
+        if context_weights is not None:
+            if canvas is not None or canvas_loop is not None or controlnet is not None:
+                raise ValueError('a prompt timeline does not combine with a canvas, a loop or a ControlNet')
+            context_weights = torch.as_tensor(context_weights, dtype=torch.float32).cpu()
+            if text.dim() != 4 or context_weights.dim() != 3 or tuple(context_weights.shape) != (text.shape[0], text.shape[1], init_noise.shape[2]):
+                raise ValueError(f'context_weights {tuple(context_weights.shape)} with text {tuple(text.shape)}: expected [P, S, L] and [P, S, Lt, Cctx]')
+            n_seg = text.shape[1]
+            text, text_mask = timeline_context(text, text_mask)
+            # the unconditional rows: their tokens in prompt 0, nothing behind (the encoding of '' keeps its single valid key, and with it the single-key shortcut)
+            pad = (n_seg - 1) * TIMELINE_SEG
+            uncond_text, uncond_mask = timeline_context(uncond_text[:, None], uncond_mask[:, None])
+            uncond_text = torch.nn.functional.pad(uncond_text, (0, 0, 0, pad))
+            uncond_mask = torch.nn.functional.pad(uncond_mask, (0, pad))
         if (init_latents is None) != (start_steps is None):
             raise ValueError('init_latents and start_steps must be given together')
         u = self.unet
@@ -212,6 +289,13 @@ class LatentSampler:
                 cond = condition.to(dev, torch.float32).expand(P, -1, -1)
                 cond = torch.cat([cond, cond], dim=0) if use_cfg else cond   # src/inference_controlnet.py:78-99: duplicated for the CFG pair
                 controlnet.prepare_condition(cond)
+            if context_weights is not None:   # behind the context and the lengths, which the table is checked against (prepare_context switched an earlier call's off)
+                wt = context_weights
+                if use_cfg:
+                    one = torch.zeros_like(wt)
+                    one[:, 0] = 1.0
+                    wt = torch.cat([wt, one], dim=0)
+                u.set_context_weights(wt, st)
             arr = (_lib.EzditDdimCoef * ddim_steps)(*[_lib.EzditDdimCoef(*c) for c in coefs])
             _lib.check(u.lib.ezdit_sampler_begin(u._h, _ptr(self.latents), P, _ptr(self.noise), arr, ddim_steps,
                                                  float(guidance_scale or 0.0), float(guidance_rescale or 0.0),
@@ -555,6 +639,33 @@ def draw_noises(codec_dim, audio_frames, ddim_steps, eta, random_seed, device, n
     return init, step
 
 
+def _timeline_entries(text_raw, prompt_weights, frames):
+    """(entries, W): every entry of text_raw as its list of prompts, and the weights of the call [N, S, max(frames)] with S the largest number of prompts of an
+    entry: entry i's own [S_i, frames_i] array in the corner, zeros behind (prompts it does not have, frames beyond its length).  A plain entry (one prompt,
+    weights None) weights its prompt 1 at every frame."""
+    n = len(text_raw)
+    entries = [list(t) if isinstance(t, (list, tuple)) else [t] for t in text_raw]
+    if prompt_weights is None:
+        prompt_weights = [None] * n
+    if len(prompt_weights) != n:
+        raise ValueError(f'{len(prompt_weights)} entries of prompt_weights for {n} entries of text_raw')
+    n_seg = max(len(e) for e in entries)
+    if min(len(e) for e in entries) < 1 or n_seg > TIMELINE_MAX:
+        raise ValueError(f'an entry of text_raw holds between 1 and {TIMELINE_MAX} prompts')
+    W = torch.zeros(n, n_seg, max(frames))
+    for i, (e, w) in enumerate(zip(entries, prompt_weights)):
+        if w is None:
+            if len(e) != 1:
+                raise ValueError(f'entry {i} of text_raw has {len(e)} prompts and no prompt_weights')
+            W[i, 0, :frames[i]] = 1.0
+            continue
+        w = torch.as_tensor(w, dtype=torch.float32)
+        if tuple(w.shape) != (len(e), frames[i]):
+            raise ValueError(f'prompt_weights[{i}] has shape {tuple(w.shape)}; expected [{len(e)} prompts, {frames[i]} frames]')
+        W[i, :len(e), :frames[i]] = w
+    return entries, W
+
+
 @torch.no_grad()
 def inference_controlnet(autoencoder, unet, controlnet, gt, gt_mask, condition, tokenizer, text_encoder, params,
                          noise_scheduler, text_raw, neg_text=None, audio_frames=500, guidance_scale=3,
@@ -572,7 +683,7 @@ def inference_controlnet(autoencoder, unet, controlnet, gt, gt_mask, condition, 
 def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, noise_scheduler, text_raw,
               neg_text=None, audio_frames=500, guidance_scale=3, guidance_rescale=0.0, ddim_steps=50, eta=1,
               random_seed=2024, device='cuda', use_graph=True, controlnet=None, condition=None, conditioning_scale=1.0,
-              first_index=None, init_latents=None, strength=None, attention_window=None, canvas_loop=None, decode_context=None, canvas_offsets=None, canvas_ramp=None,
+              first_index=None, init_latents=None, strength=None, attention_window=None, prompt_weights=None, canvas_loop=None, decode_context=None, canvas_offsets=None, canvas_ramp=None,
               solver='ddim'):
     """Same signature and semantics as the reference's ``inference`` (src/inference.py:26-107).
 
@@ -616,7 +727,13 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
     Extension (seamless loops): ``canvas_loop=T`` with ``canvas_offsets`` (loop_windows() chooses them) makes the canvas a RING of T >= audio_frames latent
     frames: window p holds the frames (canvas_offsets[p] + r) mod T, the last window runs into the first, and the default ramp is the smallest cyclic overlap.
     The ring is decoded as a ring (decode_circular, with ``decode_context`` wrapped frames on either side; None asks the autoencoder): the result is
-    [1, 1, T * ratio], and its end continues into its beginning.  Everything else as with the line; audio quality on the real checkpoints is unmeasured."""
+    [1, 1, T * ratio], and its end continues into its beginning.  Everything else as with the line; audio quality on the real checkpoints is unmeasured.
+
+    Extension (prompt timeline): an entry of ``text_raw`` may be a LIST of prompts, and ``prompt_weights`` a list with one [S_i, frames_i] array (or None for a plain
+    entry) per entry of ``text_raw``: frame j of sample i weights its prompt s by prompt_weights[i][s][j] in every block's cross-attention (scene_weights() makes
+    such weights from a scene with times), so prompts switch, cross-fade or mix inside ONE sample.  Entries with fewer prompts than the largest are padded with
+    prompts of weight 0.  It combines with ``audio_frames`` lists, per-prompt settings, ``solver``, gt / gt_mask, ``init_latents`` and ``attention_window``;
+    ValueError with a canvas, a ControlNet, or a call that would be sharded over ranks.  Audio quality on the real checkpoints is unmeasured."""
     if attention_window is not None:
         if isinstance(attention_window, bool) or int(attention_window) != attention_window or int(attention_window) < 1:
             raise ValueError(f'attention_window is a radius in latent frames, a whole number >= 1: got {attention_window!r}')
@@ -628,7 +745,7 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
             return inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, noise_scheduler, text_raw, neg_text, audio_frames, guidance_scale,
                              guidance_rescale, ddim_steps, eta, random_seed, device, use_graph, controlnet, condition, conditioning_scale, first_index=first_index,
                              init_latents=init_latents, strength=strength, canvas_loop=canvas_loop, decode_context=decode_context, canvas_offsets=canvas_offsets,
-                             canvas_ramp=canvas_ramp, solver=solver)
+                             canvas_ramp=canvas_ramp, solver=solver, prompt_weights=prompt_weights)
         finally:
             for m, prev in zip(models, previous):
                 m.set_attention_window(prev)
@@ -676,6 +793,14 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
     check_solver(solver, eta)
     import torch.distributed as dist
     frames = _frames_list(audio_frames, len(text_raw))
+    timeline = None
+    if prompt_weights is not None or any(isinstance(t, (list, tuple)) for t in text_raw):
+        if canvas_offsets is not None or controlnet is not None:
+            raise ValueError('a prompt timeline does not combine with a canvas or a ControlNet')
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and len(text_raw) > 1 and first_index is None:
+            raise ValueError('a prompt timeline is not sharded over ranks: call it with one rank\'s prompts')
+        timeline = _timeline_entries(text_raw, prompt_weights, frames if frames is not None else [int(audio_frames)] * len(text_raw))
+        text_raw = [p for entry in timeline[0] for p in entry]      # every prompt of every entry, encoded in one batch below
     if controlnet is not None:
         condition = pad_conditions(condition, frames if frames is not None else audio_frames, len(text_raw))
     if canvas_offsets is None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and len(text_raw) > 1 and first_index is None:
@@ -711,6 +836,16 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
         tb = tokenizer(text_raw, max_length=max_len, padding="max_length", truncation=True, return_tensors="pt")
         text, text_mask = tb.input_ids.to(device), tb.attention_mask.to(device).bool()
         text = text_encoder(input_ids=text, attention_mask=text_mask).last_hidden_state
+        if timeline is not None:      # [N, S, Lt, Cctx]: entry i's prompts in its first S_i places, the places behind empty (all masked, weight 0)
+            entries, tl_w = timeline
+            n_prompts, n_seg = len(entries), tl_w.shape[1]
+            t4 = torch.zeros((n_prompts, n_seg) + tuple(text.shape[1:]), dtype=text.dtype, device=text.device)
+            m4 = torch.zeros((n_prompts, n_seg, text.shape[1]), dtype=torch.bool, device=text.device)
+            at = 0
+            for i, entry in enumerate(entries):
+                t4[i, :len(entry)], m4[i, :len(entry)] = text[at:at + len(entry)], text_mask[at:at + len(entry)]
+                at += len(entry)
+            text, text_mask = t4, m4
         ub = tokenizer(neg_text * n_prompts if len(neg_text) == 1 else neg_text, max_length=max_len,
                        padding="max_length", truncation=True, return_tensors="pt")
         uncond_text, uncond_mask = ub.input_ids.to(device), ub.attention_mask.to(device).bool()
@@ -737,6 +872,8 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
     kw = dict(lengths=frames) if ragged else {}
     if solver != 'ddim':
         kw['solver'] = solver
+    if timeline is not None:
+        kw['context_weights'] = timeline[1]
     if canvas_loop is not None:
         kw['canvas_loop'] = (canvas_offsets, canvas_loop, canvas_ramp)
     elif long_form:

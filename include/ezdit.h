@@ -17,7 +17,7 @@
  *     ezdit_prepare_context (reads the context mask back to find single-key batch elements when `xkey1` is on),
  *     ezdit_prepare_timesteps, ezdit_sampler_begin, ezdit_sampler_set_sample_params, ezdit_sampler_set_multistep, ezdit_sampler_set_start, ezdit_sampler_set_canvas and ezdit_sampler_set_canvas_loop (host staging
  *     buffers of the timestep / coefficient tables), ezdit_set_lengths, ezdit_sampler_set_pair_lengths and ezdit_sampler_set_cn_scales
- *     (host mirrors of the length / scale tables).
+ *     (host mirrors of the length / scale tables), ezdit_set_context_weights (host mirror of the prompt timeline; reads the context mask back).
  *   - return 0 = OK, negative = error; ezdit_last_error() gives a thread-local message.  No C++
  *     exception crosses the ABI.
  *   - a handle is bound to the device that was current at ezdit_create() and is NOT thread-safe:
@@ -131,6 +131,7 @@ int    ezdit_bind_workspace(ezdit_handle* h, void* dev_ws, size_t bytes, int B, 
  *                                                   the condition embed
  *       ControlNet scales (.._set_cn_scales)      off <-> on                          ezdit_bind_workspace, ezdit_sampler_attach_controlnet,
  *                                                                                       ezdit_destroy of the ControlNet
+ *       context weights (ezdit_set_context_weights) off <-> on                        ezdit_bind_workspace, ezdit_prepare_context
  *       sample settings (.._set_sample_params)    off <-> on                          ezdit_bind_workspace, ezdit_sampler_begin
  *       multistep (.._set_multistep)              off <-> on, another history buffer  ezdit_bind_workspace, ezdit_sampler_begin
  *       start (.._set_start)                      off <-> on (also moves the step     ezdit_bind_workspace, ezdit_sampler_begin
@@ -604,6 +605,33 @@ int ezdit_set_attention_window(ezdit_handle* h, int radius);
  * launches the band instantiation, also for radius >= L - 1 where nothing is masked: that launch must equal ezdit_test_attention bit for bit. */
 int ezdit_test_attention_band(ezdit_handle* h, const void* dev_q, const void* dev_k, const void* dev_v, void* dev_out, int B, int L, int Lp,
                               const int32_t* dev_klen, int radius, ezdit_stream stream);
+
+/* ---- Prompt timeline: time-varying prompts in one row's cross-attention -----------------------------------------------------------------------------------
+ * The bound context holds S prompts of 128 tokens each (Lc = 128 S: prompt s occupies the context rows [128 s, 128 s + 128) of ezdit_prepare_context, its unused rows
+ * zero with mask 0) and every latent frame i of batch row b weights them, weights[b][s][i] >= 0 (HOST, [B][S][L], natural weights):
+ *     out_i = sum_s sum_{j in K_s} w_si exp(q_i k_j / sqrt(dh)) v_j  /  sum_s sum_{j in K_s} w_si exp(q_i k_j / sqrt(dh))          (K_s: the valid keys of prompt s)
+ * -- attention over all prompts' tokens with the bias ln w_si on the scores of prompt s.  A weight of 0 removes the prompt for that frame; only the ratios of a
+ * frame's weights matter (the table stores log2(w / max_s w)); a frame that weights one prompt gets that prompt's plain cross-attention.  Applied inside the
+ * cross-attention launch of every block (csrc/attn.hip TL: a workgroup walks only the prompts its frames weight): the launch count of a step does not change.
+ * Self-attention, the MLP, AdaLN and RoPE are untouched.  A row that needs no timeline carries weight 1 on prompt 0 and 0 elsewhere.
+ * A run-time table of the step (contract above), bind-scoped; it serves ezdit_forward and the sampler step alike.  Call it after ezdit_prepare_context (the weights
+ * are checked against its key mask; a new ezdit_prepare_context switches the table off) and after ezdit_set_lengths (frames beyond a row's length are neither checked nor
+ * read: they take the last frame's weights, so padding rows stay finite; ezdit_set_lengths with OTHER lengths returns EZDIT_E_STATE while the table is on).  S = 1 with every weight 1 gives the bits of the call without the table.
+ * EZDIT_E_INVALID: S outside [1, 16]; Lc != 128 S; a negative or non-finite weight; a frame that weights no prompt with a valid key (which covers a single-key row
+ * -- the unconditional row of classifier-free guidance -- whose key's prompt is weighted 0 at some frame).  EZDIT_E_UNSUPPORTED: a ControlNet handle, a backbone with
+ * a ControlNet attached, a canvas that is on; ezdit_sampler_attach_controlnet and the canvas setters refuse likewise while the table is on.  EZDIT_E_STATE: no
+ * prepared context.  Audio quality on the released checkpoints is unmeasured: whether a cross-fade of the softmax prior sounds like one, and which fade length to use. */
+int ezdit_set_context_weights(ezdit_handle* h, const float* weights, int S, ezdit_stream stream);
+/* unit-test hooks of the timeline form.  ezdit_test_attention_timeline: the layouts and refusals of ezdit_test_attention plus weights (HOST, [B][S][Lq]) and
+ * Lk = Lkp = 128 S; the weights are checked as the setter checks them.  It ALWAYS launches the TL instantiation of the plain 8-wave kernel, and waits for it.
+ * ezdit_test_cross_attention_timeline: the arguments of ezdit_test_cross_attention, then weights (HOST, [B][S][Lq], for the launched batch elements) and S;
+ * qtile 32 or 64 (EZDIT_E_INVALID otherwise). */
+int ezdit_test_attention_timeline(ezdit_handle* h, const void* dev_q, const void* dev_k, const void* dev_v, const uint8_t* dev_kmask, void* dev_out, int B,
+                                  int Lq, int Lk, int Lqp, int Lkp, const float* weights, int S, ezdit_stream stream);
+int ezdit_test_cross_attention_timeline(const void* dev_xu, int ldu, const void* dev_xw, int ldw, int xw_rows, int xK, const float* dev_qn_w, const float* dev_qn_b,
+                                        const void* dev_k, const void* dev_v, const uint8_t* dev_kmask, void* dev_out, int ldo, int B, int b0, int H, int dh, int Lq, int Lk,
+                                        int Lqp, int Lkp, const void* dev_zstat_in, long zs_stride, int zparts, int zD, int zw, const float* dev_zG, const float* dev_zC,
+                                        float zeps, int xk2, int qtile, int xcd_map, const float* weights, int S, ezdit_stream stream);
 
 /* ---- T5 text encoder (csrc/t5.hip): stands in for transformers' T5EncoderModel in the `text_encoder` slot (api/ezaudio.py:80-82, src/inference.py:42-50) --------
  * Encoder stacks of the flan-t5 / T5 v1.1 family only: gated gelu_new feed-forward, head dim 64, no biases, T5LayerNorm (RMS), the bidirectional
