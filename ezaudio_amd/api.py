@@ -97,7 +97,7 @@ class EzAudio:
         return radius
 
     def generate_audio(self, text, length=10, guidance_scale=5, guidance_rescale=0.75, ddim_steps=100, eta=1,
-                       random_seed=None, randomize_seed=False, attention_window=None, solver='ddim'):
+                       random_seed=None, randomize_seed=False, attention_window=None, compose=None, solver='ddim'):
         """api/ezaudio.py:101-130.  `text` may also be a list of prompts (batched extension): the result is then
         an array [N, T].  With a list of prompts `length` may be a list too, one duration in seconds per prompt (mixed-length
         batch, one call): the result is then (sr, [one 1-D array per prompt]), each trimmed to its own duration.
@@ -109,8 +109,15 @@ class EzAudio:
         `attention_window` (seconds; one value): sliding-window self-attention -- every latent frame attends to the frames inside a span of that many seconds
         centred on it (radius round(seconds * latent_sr / 2) frames), so a `length` beyond the trained 10 s keeps every pair of frames inside the trained range
         of relative positions: attention_window=10 gives each frame the 501 keys of the trained row.  A span that covers the clip is the plain call, bit for
-        bit.  Audio quality of windowed sampling on the real checkpoints is unmeasured."""
+        bit.  Audio quality of windowed sampling on the real checkpoints is unmeasured.
+        `compose` (composed guidance): further prompts with weights next to `text`, each guided against the empty prompt with its own weight -- "both sounds
+        must be there, and less of that one": compose=[('distant thunder', 0.8), ('wind', -0.5)].  `text` has weight 1 and is the reference of the guidance
+        rescale; a negative weight steers away from its prompt.  With a list of prompts, one such list (or None) per prompt.  The batch grows to K + 1 rows per
+        prompt.  ValueError for a prompt list of another size, a non-finite weight, more than 7 extra prompts, or a call without guidance (text '').  No extra
+        prompt is the plain call, bit for bit.  Audio quality on the real checkpoints -- which weights sound like "both" or "less of" -- is unmeasured."""
         neg_text = None
+        if compose is not None and not isinstance(text, str) and len(compose) != len(text):
+            raise ValueError('compose for a list of prompts is a list of the same size: one list of (text, weight) pairs, or None, per prompt')
         check_solver(solver, eta)
         radius = self._window_radius(attention_window)
         for name, v in (('guidance_scale', guidance_scale), ('guidance_rescale', guidance_rescale), ('eta', eta), ('random_seed', random_seed)):
@@ -138,7 +145,7 @@ class EzAudio:
             random_seed = random.randint(0, MAX_SEED) if isinstance(text, str) else [random.randint(0, MAX_SEED) for _ in text]
         pred = inference(self.autoencoder, self.unet, gt, gt_mask, self.tokenizer, self.text_encoder, self.params,
                          self.noise_scheduler, text, neg_text, length, guidance_scale, guidance_rescale, ddim_steps,
-                         eta, random_seed, self.device, solver=solver, attention_window=radius)
+                         eta, random_seed, self.device, solver=solver, attention_window=radius, **({} if compose is None else dict(compose=compose)))
         pred = pred.cpu().numpy()
         if per_prompt:
             ratio = self.params['autoencoder']['sr'] // latent_sr

@@ -141,6 +141,10 @@ struct ezdit_handle {
     Table<int> canvas;
     int canvas_T = 0, canvas_ramp = 1;
     bool canvas_loop = false;
+    // [P][cw_K] weights of composed guidance (ezdit_sampler_begin_composed switches it on, ezdit_sampler_set_compose_weights replaces the values): the batch is
+    // [c_0 | .. | c_{K-1} | u], B = (cw_K + 1) P, and the last two kernels of the step run their composed instantiations (launch_cfg_compose).  K is a kernel argument
+    Table<float> cw;
+    int cw_K = 1;
 
     int launches = 0;
     bool is_cn = false;          // ControlNet variant (cfg.controlnet)
@@ -528,6 +532,7 @@ size_t carve(const ezdit_handle* h, int B, int L, int Lc, int n_slots, std::map<
         add("canvas", 256 * sizeof(int));  // per-window first canvas frame (ezdit_sampler_set_canvas; P <= B <= 240), behind `start` for the same reason: 1 KB
         add("tlb", (size_t)B * (Lcp / 128) * L * 4);     // prompt timeline (ezdit_set_context_weights): one score bias per (batch element, prompt, frame) and the prompts' frame
         add("tlsup", (size_t)B * (Lcp / 128) * 8);       // supports, behind `canvas` for the same reason: B L 4 bytes at one prompt
+        add("cw", (size_t)B * sizeof(float));            // weights of composed guidance [P][K], P K < B = (K + 1) P; at the very end for the same reason
     }
     return off;
 }
@@ -712,6 +717,7 @@ void resolve_workspace(ezdit_handle* h) {
     h->lens.dev = h->buf<int>("lens"); h->cns.dev = h->buf<float>("cns"); h->sp.dev = h->buf<float>("spg"); h->coef.dev = p.coef;
     h->start.dev = h->buf<int>("start"); h->canvas.dev = h->buf<int>("canvas");
     h->tl.dev = h->buf<float>("tlb"); h->tlsup = h->buf<int2>("tlsup");
+    h->cw.dev = h->buf<float>("cw");
     p.zstat = h->buf<float2>("zstat"); p.zt_qkv = h->buf<float>("zt_qkv"); p.zt_geglu = h->buf<float>("zt_geglu"); p.zt_q2 = h->buf<float>("zt_q2");
     p.zstat_skip = h->buf<float2>("zstat_skip"); p.zt_skip = h->buf<float>("zt_skip"); p.ucat_z = h->buf<bf16_t>("ucat_z");
     if (h->is_cn) { p.cembed = h->buf<float>("cembed"); p.cnres = h->buf<float>("cnres"); p.skipbf = h->buf<bf16_t>("skipbf"); }
@@ -841,6 +847,18 @@ void reset_call_state(ezdit_handle* h) {
     h->coef.set(h, false); h->ms_hist = nullptr;
     h->start.set(h, false); h->start_min = 0;
     h->canvas.set(h, false); h->canvas_loop = false;
+    h->cw.set(h, false); h->cw_K = 1;
+}
+
+// the values of a composed call's weight table [P][K]: finite, the primary condition's above 0
+int check_compose_weights(const float* w, int P, int K) {
+    for (int p = 0; p < P; ++p)
+        for (int k = 0; k < K; ++k) {
+            const float x = w[(size_t)p * K + k];
+            if (!std::isfinite(x)) return fail(EZDIT_E_INVALID, "weights[%d][%d] is not finite", p, k);
+            if (k == 0 && !(x > 0.f)) return fail(EZDIT_E_INVALID, "weights[%d][0] = %g: the primary condition's weight is above 0", p, (double)x);
+        }
+    return EZDIT_OK;
 }
 
 // ... bind-scoped ones, and the sampler call itself, belong to one binding of the workspace: a new one zeroes the device arrays and may have another shape, so
@@ -1222,6 +1240,7 @@ int ezdit_set_context_weights(ezdit_handle* h, const float* weights, int S, ezdi
     }
     if (h->cn) return fail(EZDIT_E_UNSUPPORTED, "context weights with a ControlNet attached");
     if (h->canvas.on) return fail(EZDIT_E_UNSUPPORTED, "context weights while the canvas is on (ezdit_sampler_set_canvas): a window has one prompt");
+    if (h->cw.on) return fail(EZDIT_E_UNSUPPORTED, "context weights while composed guidance is on (ezdit_sampler_begin_composed)");
     if (S < 1 || S > TL_MAXS) return fail(EZDIT_E_INVALID, "S = %d outside [1, %d]", S, TL_MAXS);
     if (h->Lc != 128 * S) return fail(EZDIT_E_INVALID, "S = %d prompts need a context of %d tokens (128 each), the workspace is bound to Lc = %d", S, 128 * S, h->Lc);
     if (!h->ctx_ready) return fail(EZDIT_E_STATE, "ezdit_prepare_context first: the weights are checked against its key mask");
@@ -1657,6 +1676,7 @@ int ezdit_sampler_attach_controlnet(ezdit_handle* h, ezdit_handle* cn, float con
     if (cn && !cn->is_cn) return fail(EZDIT_E_INVALID, "second argument must be a ControlNet handle");
     if (cn && h->canvas.on) return fail(EZDIT_E_UNSUPPORTED, "a ControlNet while the canvas is on (ezdit_sampler_set_canvas)");
     if (cn && h->tl.on) return fail(EZDIT_E_UNSUPPORTED, "a ControlNet while the context weights are on (ezdit_set_context_weights)");
+    if (cn && h->cw.on) return fail(EZDIT_E_UNSUPPORTED, "a ControlNet while composed guidance is on (ezdit_sampler_begin_composed)");
     if (cn && cn->attn_window != h->attn_window)
         return fail(EZDIT_E_INVALID, "attention windows differ: backbone %d, ControlNet %d frames (ezdit_set_attention_window on both)", h->attn_window, cn->attn_window);
     if (h->cn && h->cn != cn) {
@@ -1684,20 +1704,9 @@ int ezdit_set_cn_scale(ezdit_handle* h, float scale) {
 }
 
 // ------------------------------------------------------------------------------------------------------
-int ezdit_sampler_begin(ezdit_handle* h, float* latents, int P, const float* noise, const ezdit_ddim_coef* coefs, int n_steps,
-                        float guidance_scale, float guidance_rescale, const float* gt, const uint8_t* gt_mask,
-                        ezdit_stream stream) {
-    if (!h || !latents || !coefs) return fail(EZDIT_E_INVALID, "null argument");
-    if (!h->ws || !h->wblob) return fail(EZDIT_E_STATE, "bind weights and workspace first");
-    if (n_steps <= 0 || n_steps > h->n_slots) return fail(EZDIT_E_INVALID, "n_steps %d > workspace slots %d", n_steps, h->n_slots);
-    const int needB = guidance_scale > 0.f ? 2 * P : P;
-    if (P <= 0 || needB != h->B) return fail(EZDIT_E_INVALID, "P=%d with guidance %g needs B=%d, workspace has B=%d", P, (double)guidance_scale, needB, h->B);
-    if ((gt == nullptr) != (gt_mask == nullptr)) return fail(EZDIT_E_INVALID, "gt and gt_mask must be given together");
-    if (h->lens.on && needB == 2 * P)
-        for (int p = 0; p < P; ++p)
-            if (h->lens.host[p] != h->lens.host[P + p])
-                return fail(EZDIT_E_INVALID, "lengths of the CFG pair of sample %d differ (%d, %d)", p, h->lens.host[p], h->lens.host[P + p]);
-    hipStream_t st = (hipStream_t)stream;
+// what ezdit_sampler_begin and ezdit_sampler_begin_composed do once their arguments are accepted: the call's coefficient rows, step 0, no call-scoped table
+static int begin_call(ezdit_handle* h, float* latents, int P, const float* noise, const ezdit_ddim_coef* coefs, int n_steps, float guidance_scale,
+                      float guidance_rescale, const float* gt, const uint8_t* gt_mask, hipStream_t st) {
     h->last_stream = st;
     std::vector<float> cf((size_t)n_steps * 8, 0.f);
     for (int i = 0; i < n_steps; ++i) {
@@ -1713,6 +1722,64 @@ int ezdit_sampler_begin(ezdit_handle* h, float* latents, int P, const float* noi
     reset_call_state(h);
     drop_graph(h);   // (another latents pointer, other scalars: whatever the tables were)
     return EZDIT_OK;
+}
+
+int ezdit_sampler_begin(ezdit_handle* h, float* latents, int P, const float* noise, const ezdit_ddim_coef* coefs, int n_steps,
+                        float guidance_scale, float guidance_rescale, const float* gt, const uint8_t* gt_mask,
+                        ezdit_stream stream) {
+    if (!h || !latents || !coefs) return fail(EZDIT_E_INVALID, "null argument");
+    if (!h->ws || !h->wblob) return fail(EZDIT_E_STATE, "bind weights and workspace first");
+    if (n_steps <= 0 || n_steps > h->n_slots) return fail(EZDIT_E_INVALID, "n_steps %d > workspace slots %d", n_steps, h->n_slots);
+    const int needB = guidance_scale > 0.f ? 2 * P : P;
+    if (P <= 0 || needB != h->B) return fail(EZDIT_E_INVALID, "P=%d with guidance %g needs B=%d, workspace has B=%d", P, (double)guidance_scale, needB, h->B);
+    if ((gt == nullptr) != (gt_mask == nullptr)) return fail(EZDIT_E_INVALID, "gt and gt_mask must be given together");
+    if (h->lens.on && needB == 2 * P)
+        for (int p = 0; p < P; ++p)
+            if (h->lens.host[p] != h->lens.host[P + p])
+                return fail(EZDIT_E_INVALID, "lengths of the CFG pair of sample %d differ (%d, %d)", p, h->lens.host[p], h->lens.host[P + p]);
+    return begin_call(h, latents, P, noise, coefs, n_steps, guidance_scale, guidance_rescale, gt, gt_mask, (hipStream_t)stream);
+}
+
+// The composed call (include/ezdit.h, "composed guidance"): K conditions per sample, B = (K + 1) P.  Every check comes before the first change of state
+int ezdit_sampler_begin_composed(ezdit_handle* h, float* latents, int P, const float* noise, const ezdit_ddim_coef* coefs, int n_steps,
+                                 float guidance_scale, float guidance_rescale, const float* gt, const uint8_t* gt_mask, int K, const float* weights,
+                                 ezdit_stream stream) {
+    if (!h || !latents || !coefs || !weights) return fail(EZDIT_E_INVALID, "null argument");
+    if (!h->ws || !h->wblob) return fail(EZDIT_E_STATE, "bind weights and workspace first");
+    if (n_steps <= 0 || n_steps > h->n_slots) return fail(EZDIT_E_INVALID, "n_steps %d > workspace slots %d", n_steps, h->n_slots);
+    if (!(guidance_scale > 0.f)) return fail(EZDIT_E_INVALID, "guidance_scale = %g: composed guidance needs guidance", (double)guidance_scale);
+    if (K < 1 || K > CFG_KMAX) return fail(EZDIT_E_INVALID, "K = %d outside [1, %d]", K, CFG_KMAX);
+    if (P <= 0 || (long)(K + 1) * P != h->B) return fail(EZDIT_E_INVALID, "P=%d with K=%d conditions needs B=%ld, workspace has B=%d", P, K, (long)(K + 1) * P, h->B);
+    if ((gt == nullptr) != (gt_mask == nullptr)) return fail(EZDIT_E_INVALID, "gt and gt_mask must be given together");
+    if (int rc = check_compose_weights(weights, P, K)) return rc;
+    if (h->lens.on)
+        for (int b = P; b < h->B; ++b)
+            if (h->lens.host[b] != h->lens.host[b % P])
+                return fail(EZDIT_E_INVALID, "lengths of the rows of sample %d differ (%d, %d at batch row %d)", b % P, h->lens.host[b % P], h->lens.host[b], b);
+    if (h->cn) return fail(EZDIT_E_UNSUPPORTED, "composed guidance with a ControlNet attached");
+    if (h->tl.on) return fail(EZDIT_E_UNSUPPORTED, "composed guidance with context weights (ezdit_set_context_weights)");
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    if (cs != hipStreamCaptureStatusNone) return fail(EZDIT_E_STATE, "ezdit_sampler_begin_composed inside a stream capture (it uploads from host memory and waits)");
+    if (int rc = begin_call(h, latents, P, noise, coefs, n_steps, guidance_scale, guidance_rescale, gt, gt_mask, st)) return rc;
+    if (int rc = upload_table(h->cw, std::vector<float>(weights, weights + (size_t)P * K), st)) return rc;
+    h->cw.set(h, true); h->cw_K = K;
+    return EZDIT_OK;
+}
+
+int ezdit_sampler_set_compose_weights(ezdit_handle* h, const float* weights, int P, int K, ezdit_stream stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = setter_checks(h, "ezdit_sampler_set_compose_weights", Needs::Begun, st)) return rc;
+    if (!weights || P == 0) {   // off.  K = 1 is the layout of the plain call, which goes on; with K > 1 the batch has no plain reading and the call ends here
+        if (h->cw.on && h->cw_K > 1) { h->latents = nullptr; h->noise = nullptr; h->s_gt = nullptr; h->s_gt_mask = nullptr; }
+        h->cw.set(h, false); h->cw_K = 1;
+        return EZDIT_OK;
+    }
+    if (!h->cw.on) return fail(EZDIT_E_STATE, "the call was not begun composed (ezdit_sampler_begin_composed): composition is another batch layout");
+    if (P != h->P || K != h->cw_K) return fail(EZDIT_E_INVALID, "P = %d, K = %d: the call was begun with P = %d, K = %d", P, K, h->P, h->cw_K);
+    if (int rc = check_compose_weights(weights, P, K)) return rc;
+    return upload_table(h->cw, std::vector<float>(weights, weights + (size_t)P * K), st);
 }
 
 static int sampler_step(ezdit_handle* h, hipStream_t st) {
@@ -1759,6 +1826,10 @@ static int sampler_step(ezdit_handle* h, hipStream_t st) {
     a.sp_g = h->sp.read(); a.sp_c = h->sp.on ? h->p.spc : nullptr; a.sp_g_stride = 2;
     a.x0_hist = h->coef.on ? h->ms_hist : nullptr;
     a.start = h->start.read();
+    if (h->cw.on) {   // composed guidance: the same arguments plus the weight table, the composed instantiations
+        a.K = h->cw_K; a.cw = h->cw.dev;
+        if (launch_cfg_compose(a, h->p.cfgpart, st)) return fail(EZDIT_E_STATE, "composed guidance with K = %d", h->cw_K);
+    } else
     launch_cfg_ddim(a, h->p.cfgpart, st);   // its last kernel also advances the device step counter
     h->launches += (h->sp.on || (h->gscale > 0.f && h->grescale > 0.f)) ? 2 : 1;
     if (h->canvas.on) {   // long-form canvas: the windows' shared frames are averaged on the updated latents (x0_hist stays per window)
@@ -1808,6 +1879,21 @@ int ezdit_cfg_multistep_step(const float* pred, float* latents, float* x0_hist, 
     a.sp_g = params; a.sp_c = params + 2; a.sp_g_stride = 8;
     a.x0_hist = x0_hist;
     return hook_launch("k_cfg_*", "", [&] { launch_cfg_ddim(a, scratch, (hipStream_t)stream); return 0; });
+}
+
+// The composed form of the two operators above (include/ezdit.h, "composed guidance"): pred [(K + 1) P][n], weights [P][K] on the device
+int ezdit_cfg_compose_step(const float* pred, float* latents, const float* noise, float* x0_hist, const float* params, const float* weights, int K,
+                           const int32_t* lens, int L, int P, int n, float* scratch, ezdit_stream stream) {
+    if (!pred || !latents || !params || !weights || P < 1 || n < 2) return fail(EZDIT_E_INVALID, "bad argument");
+    if (K < 1 || K > CFG_KMAX) return fail(EZDIT_E_INVALID, "K = %d outside [1, %d]", K, CFG_KMAX);
+    if (!scratch) return fail(EZDIT_E_INVALID, "the composed step needs %d scratch floats", P * 256);
+    if (lens && (L < 1 || n % L)) return fail(EZDIT_E_INVALID, "lens given: L = %d must divide n = %d", L, n);
+    if (noise && x0_hist) return fail(EZDIT_E_INVALID, "noise together with a history: the multistep form is deterministic");
+    CfgDdimArgs a = standalone_step(pred, latents, noise, P, n, lens, L);
+    a.sp_g = params; a.sp_c = params + 2; a.sp_g_stride = 8;
+    a.x0_hist = x0_hist;
+    a.K = K; a.cw = weights;
+    return hook_launch("k_cfg_*", "composed guidance", [&] { return launch_cfg_compose(a, scratch, (hipStream_t)stream); });
 }
 
 int ezdit_sampler_set_multistep(ezdit_handle* h, const float* c_hist, int n_steps, float* x0_hist, ezdit_stream stream) {
@@ -1908,6 +1994,7 @@ static int set_canvas_table(ezdit_handle* h, const char* who, const int32_t* off
     if (h->s_gt) return fail(EZDIT_E_UNSUPPORTED, "a canvas with gt / gt_mask: long edits are not implemented");
     if (h->cn) return fail(EZDIT_E_UNSUPPORTED, "a canvas with a ControlNet attached");
     if (h->tl.on) return fail(EZDIT_E_UNSUPPORTED, "a canvas with context weights (ezdit_set_context_weights): a window has one prompt");
+    if (h->cw.on) return fail(EZDIT_E_UNSUPPORTED, "a canvas with composed guidance (ezdit_sampler_begin_composed)");
     if (int rc = upload_table(h->canvas, std::vector<int>(offsets, offsets + P), st)) return rc;
     h->canvas.set(h, true, T != h->canvas_T || ramp != h->canvas_ramp || loop != h->canvas_loop);   // (T and the ramp are kernel arguments; the other form is another kernel)
     h->canvas_T = T; h->canvas_ramp = ramp; h->canvas_loop = loop;
@@ -1949,7 +2036,7 @@ int ezdit_sampler_set_sample_params(ezdit_handle* h, const float* guidance_scale
     std::vector<float> v((size_t)P * 2 + (size_t)ns * P * 8, 0.f);
     for (int p = 0; p < P; ++p) {
         if (!std::isfinite(guidance_scale[p]) || !std::isfinite(guidance_rescale[p])) return fail(EZDIT_E_INVALID, "non-finite guidance of sample %d", p);
-        if (guidance_scale[p] > 0.f && h->B != 2 * P)
+        if (guidance_scale[p] > 0.f && h->B != (h->cw.on ? h->cw_K + 1 : 2) * P)
             return fail(EZDIT_E_INVALID, "guidance_scale[%d] = %g on a sampler begun without CFG rows (B = P = %d)", p, (double)guidance_scale[p], P);
         v[p * 2 + 0] = guidance_scale[p]; v[p * 2 + 1] = guidance_rescale[p];
     }

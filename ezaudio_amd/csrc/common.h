@@ -393,8 +393,15 @@ struct CfgDdimArgs {   // (the defaults are the stand-alone operator with everyt
     // the device step < start[p]: k_cfg_stats returns for it, k_cfg_apply makes no read of pred / noise / x0_hist and no write of latents / x0_hist for it
     // (its workgroups still arrive at `done`), and at step == start[p] its c_hist is 0 (its first step is first-order and does not read the history)
     const int* start = nullptr;
+    // composed guidance (null cw = off: one conditional row per sample, the kernels they have always been; launch_cfg_compose).  On: sample p has K conditions, pred is
+    // [(K + 1) P][n] = [c_0 (P rows) | c_1 | ... | c_{K-1} | u], and cw fp32 [P][K] (device) weights them: d = w_0 (c_0 - u) + sum_k w_k (c_k - u) in fp32 with k
+    // ascending, v = u + guidance_scale d; everything behind v is the body it has always been, the rescale reference is c_0.  A weight of exactly 0: row k P + p is
+    // not read; guidance_scale <= 0: only c_0 is.  Read at run time: one captured step serves every set of weights.  At the END of the struct: the offsets above stay
+    int K = 1; const float* cw = nullptr;
 };
+constexpr int CFG_KMAX = 8;   // conditions per sample of composed guidance: 1 <= CfgDdimArgs.K <= CFG_KMAX (the weights of a sample ride in registers)
 void launch_cfg_ddim(const CfgDdimArgs& a, float* partial /* [P][64][4] scratch */, hipStream_t st);
+int launch_cfg_compose(const CfgDdimArgs& a, float* partial /* [P][64][4] scratch */, hipStream_t st);   // the composed form (a.cw given); non-zero = refused, nothing launched
 void launch_set_int(int* p, int v, int add, hipStream_t st);  // *p = add ? *p + v : v
 struct AddNoiseArgs {  // latents[p][i] = sa_p * ((clean[p][i] + shift) * scale) + sb_p * latents[p][i]: a clean VAE latent noised to sample p's start step
     const float* clean;   // [P][n] in VAE space (before scale_shift); row p is not read when params[p] is exactly (0, 1)

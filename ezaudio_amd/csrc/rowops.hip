@@ -477,9 +477,25 @@ __global__ void k_rope_table(float* cosT, float* sinT, int max_len, int dh) {
 //                 the DDIM kernel as it was, instruction for instruction.
 //   ST (CfgDdimArgs.start given): sample p is HELD while step < start[p] -- no statistics, no update, no read of pred / noise / history, no write -- and its
 //                 first step (step == start[p]) is first-order.  ST = false is the source as it was.
+//   CP (CfgDdimArgs.cw given): composed guidance.  Sample p has K conditional rows k P + p and its unconditional row at K P + p; the guided direction is
+//                 d = w_0 (c_0 - u) + w_1 (c_1 - u) + ... in fp32, k ascending, g = u + s d, and the rescale reference stays c_0.  A weight of exactly 0 skips the
+//                 read of its row (workgroup-uniform: the weights belong to the sample).  CP = false is the source as it was.
 constexpr int CFG_NB = 64;
 
-template <bool ST>
+// the K weights of sample p in registers (uniform: scalar loads), 0 behind K -- so `w[k] != 0` alone decides whether row k P + p is read
+__device__ __forceinline__ void compose_weights(const CfgDdimArgs& a, int p, float (&w)[CFG_KMAX]) {
+#pragma unroll
+    for (int k = 0; k < CFG_KMAX; ++k) w[k] = k < a.K ? a.cw[(long)p * a.K + k] : 0.f;
+}
+__device__ __forceinline__ float compose_dir(const CfgDdimArgs& a, const float (&w)[CFG_KMAX], float c0, float u, int p, int i) {
+    float d = w[0] * (c0 - u);
+#pragma unroll
+    for (int k = 1; k < CFG_KMAX; ++k)
+        if (w[k] != 0.f) d += w[k] * (a.pred[((long)k * a.P + p) * a.n + i] - u);
+    return d;
+}
+
+template <bool ST, bool CP>
 __global__ __launch_bounds__(256) void k_cfg_stats(CfgDdimArgs a, float* partial) {
     __shared__ float red[4];
     const int p = blockIdx.y, blk = blockIdx.x;
@@ -489,6 +505,7 @@ __global__ __launch_bounds__(256) void k_cfg_stats(CfgDdimArgs a, float* partial
     }
     const float* pc = a.pred + (long)p * n;
     const float* pu = a.pred + (long)(a.P + p) * n;
+    if constexpr (CP) pu = a.pred + ((long)a.K * a.P + p) * n;
     float gs = a.guidance_scale;
     if (a.sp_g) {   // per-sample settings: a sample without guidance or without rescale needs no statistics (workgroup-uniform)
         const float* g = a.sp_g + (long)p * a.sp_g_stride;
@@ -497,10 +514,14 @@ __global__ __launch_bounds__(256) void k_cfg_stats(CfgDdimArgs a, float* partial
     }
     float s1 = 0.f, q1 = 0.f, s2 = 0.f, q2 = 0.f;
     const int len = a.lens ? a.lens[p] : 0;
+    float cw[CFG_KMAX];
+    if constexpr (CP) compose_weights(a, p, cw);
     for (int i = blk * 256 + threadIdx.x; i < n; i += CFG_NB * 256) {
         if (a.lens && i % a.L >= len) continue;   // padded frame: not part of the sample
         const float c = pc[i], u = pu[i];
-        const float g = u + gs * (c - u);
+        float g;
+        if constexpr (CP) g = u + gs * compose_dir(a, cw, c, u, p, i);
+        else g = u + gs * (c - u);
         s1 += c; q1 += c * c; s2 += g; q2 += g * g;
     }
     s1 = block_sum4(s1, red); q1 = block_sum4(q1, red); s2 = block_sum4(s2, red); q2 = block_sum4(q2, red);
@@ -510,7 +531,7 @@ __global__ __launch_bounds__(256) void k_cfg_stats(CfgDdimArgs a, float* partial
     }
 }
 
-template <bool MS, bool ST>
+template <bool MS, bool ST, bool CP>
 __global__ __launch_bounds__(256) void k_cfg_apply(CfgDdimArgs a, const float* partial) {
     const int p = blockIdx.y, blk = blockIdx.x;
     const int n = a.n;
@@ -547,6 +568,10 @@ __global__ __launch_bounds__(256) void k_cfg_apply(CfgDdimArgs a, const float* p
     }
     const float* pc = a.pred + (long)p * n;
     const float* pu = cfg ? a.pred + (long)(a.P + p) * n : nullptr;
+    float cw[CFG_KMAX];
+    if constexpr (CP) {
+        if (cfg) { pu = a.pred + ((long)a.K * a.P + p) * n; compose_weights(a, p, cw); }   // (a sample without guidance reads c_0 alone, not even its weights)
+    }
     float* lat = a.latents + (long)p * n;
     // (per-sample settings: a sample whose sigma is 0 at this step draws no noise, its slice is not read)
     const float* z = a.noise && !(a.sp_g && sigma == 0.f) ? a.noise + ((long)step * a.P + p) * n : nullptr;
@@ -570,7 +595,8 @@ __global__ __launch_bounds__(256) void k_cfg_apply(CfgDdimArgs a, const float* p
         float v = pc[i];
         if (cfg) {
             const float u = pu[i];
-            v = u + gs * (v - u);
+            if constexpr (CP) v = u + gs * compose_dir(a, cw, v, u, p, i);
+            else v = u + gs * (v - u);
             if (rescale) v = phi * (v * ratio) + (1.f - phi) * v;
         }
         const float x = lat[i];
@@ -795,14 +821,30 @@ void launch_cfg_ddim(const CfgDdimArgs& a, float* partial, hipStream_t st) {
     // per-sample settings: always both launches (which samples rescale is a run-time value of the table)
     const dim3 grid(CFG_NB, a.P);
     if (a.sp_g || (a.guidance_scale > 0.f && a.guidance_rescale > 0.f)) {
-        if (a.start) hipLaunchKernelGGL(k_cfg_stats<true>, grid, dim3(256), 0, st, a, partial);
-        else hipLaunchKernelGGL(k_cfg_stats<false>, grid, dim3(256), 0, st, a, partial);
+        if (a.start) hipLaunchKernelGGL((k_cfg_stats<true, false>), grid, dim3(256), 0, st, a, partial);
+        else hipLaunchKernelGGL((k_cfg_stats<false, false>), grid, dim3(256), 0, st, a, partial);
     }
     if (a.start) {   // the start table: instantiations of their own, the ones without it keep their code
-        if (a.x0_hist) hipLaunchKernelGGL((k_cfg_apply<true, true>), grid, dim3(256), 0, st, a, partial);
-        else hipLaunchKernelGGL((k_cfg_apply<false, true>), grid, dim3(256), 0, st, a, partial);
-    } else if (a.x0_hist) hipLaunchKernelGGL((k_cfg_apply<true, false>), grid, dim3(256), 0, st, a, partial);
-    else hipLaunchKernelGGL((k_cfg_apply<false, false>), grid, dim3(256), 0, st, a, partial);
+        if (a.x0_hist) hipLaunchKernelGGL((k_cfg_apply<true, true, false>), grid, dim3(256), 0, st, a, partial);
+        else hipLaunchKernelGGL((k_cfg_apply<false, true, false>), grid, dim3(256), 0, st, a, partial);
+    } else if (a.x0_hist) hipLaunchKernelGGL((k_cfg_apply<true, false, false>), grid, dim3(256), 0, st, a, partial);
+    else hipLaunchKernelGGL((k_cfg_apply<false, false, false>), grid, dim3(256), 0, st, a, partial);
+}
+
+// composed guidance (CfgDdimArgs.cw): the CP instantiations, a launcher of their own -- launch_cfg_ddim is what it was.  Non-zero: nothing launched
+int launch_cfg_compose(const CfgDdimArgs& a, float* partial, hipStream_t st) {
+    if (!a.cw || a.K < 1 || a.K > CFG_KMAX) return 1;
+    const dim3 grid(CFG_NB, a.P);
+    if (a.sp_g || (a.guidance_scale > 0.f && a.guidance_rescale > 0.f)) {
+        if (a.start) hipLaunchKernelGGL((k_cfg_stats<true, true>), grid, dim3(256), 0, st, a, partial);
+        else hipLaunchKernelGGL((k_cfg_stats<false, true>), grid, dim3(256), 0, st, a, partial);
+    }
+    if (a.start) {
+        if (a.x0_hist) hipLaunchKernelGGL((k_cfg_apply<true, true, true>), grid, dim3(256), 0, st, a, partial);
+        else hipLaunchKernelGGL((k_cfg_apply<false, true, true>), grid, dim3(256), 0, st, a, partial);
+    } else if (a.x0_hist) hipLaunchKernelGGL((k_cfg_apply<true, false, true>), grid, dim3(256), 0, st, a, partial);
+    else hipLaunchKernelGGL((k_cfg_apply<false, false, true>), grid, dim3(256), 0, st, a, partial);
+    return 0;
 }
 
 void launch_add_noise(const AddNoiseArgs& a, hipStream_t st) {

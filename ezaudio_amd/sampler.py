@@ -48,6 +48,7 @@ def _collapse(value, n_prompts, name):
 
 TIMELINE_SEG = 128     # context rows of one prompt of a timeline: one key tile of the cross-attention kernel (csrc/attn.hip TL)
 TIMELINE_MAX = 16      # prompts of one timeline
+COMPOSE_MAX = 8        # conditions per sample of composed guidance (include/ezdit.h EZDIT_COMPOSE_MAX)
 
 
 def scene_weights(scene, frames, latent_sr, crossfade):
@@ -129,8 +130,8 @@ class LatentSampler:
 
     def prepare(self, text, text_mask, uncond_text, uncond_mask, init_noise, step_noises, guidance_scale,
                 guidance_rescale, ddim_steps, eta, gt=None, gt_mask=None, controlnet=None, condition=None,
-                conditioning_scale=1.0, lengths=None, init_latents=None, start_steps=None, latent_scale=1.0, latent_shift=0.0, context_weights=None, canvas=None,
-                canvas_loop=None, solver='ddim'):
+                conditioning_scale=1.0, lengths=None, init_latents=None, start_steps=None, latent_scale=1.0, latent_shift=0.0, context_weights=None, compose_text=None, compose_mask=None,
+                compose_weights=None, canvas=None, canvas_loop=None, solver='ddim'):
         """``lengths`` (list of P ints): init_noise / step_noises / gt / gt_mask are padded to L = max(lengths) frames and sample p is valid on
         [0, lengths[p]) -- its final latent is what a call with that sample alone at its own length gives, zero beyond (include/ezdit.h
         ezdit_set_lengths).  With a ControlNet the table goes to the attached pair (ezdit_sampler_set_pair_lengths) and ``condition`` is
@@ -168,8 +169,37 @@ class LatentSampler:
         ``context_weights`` [P, S, L] (prompt timeline, include/ezdit.h ezdit_set_context_weights): ``text`` is then [P, S, Lt, Cctx] and ``text_mask`` [P, S, Lt],
         S prompts per sample, and frame i of sample p weights prompt s by context_weights[p, s, i] in every block's cross-attention (scene_weights() makes such
         weights).  The 128-aligned context is built here; the unconditional rows keep their tokens in prompt 0 and weight it alone.  Not with a canvas, a loop or a
-        ControlNet."""
+        ControlNet.
+
+        ``compose_weights`` [P, K] with ``compose_text`` [P, K-1, Lt, Cctx] and ``compose_mask`` [P, K-1, Lt] (composed guidance, include/ezdit.h
+        ezdit_sampler_begin_composed): sample p carries K conditions -- ``text`` is condition 0, the primary one -- and is guided by
+        v = u + guidance_scale sum_k w[p, k] (c_k - u) against its one unconditional row; the guidance rescale takes the primary condition as its reference.
+        w[p, 0] > 0; the others are any finite value, negative ones steer away from their prompt, and a weight of exactly 0 drops its condition (its row is
+        computed and not read).  The batch is built here as [text | compose_text[:, 0] | ... | uncond_text]; set_compose_weights() replaces the values of a
+        prepared call without a re-capture.  It combines with lengths, per-sample settings, ``solver``, gt / gt_mask, init_latents and an attention window; not with
+        a ControlNet, a canvas, a loop or a timeline, and it needs guidance.  One condition with weight 1 is the plain call: nothing new is called, the same bits."""
         check_solver(solver, eta)
+        compose = None
+        if compose_weights is not None or compose_text is not None or compose_mask is not None:
+            if compose_weights is None:
+                raise ValueError('compose_text / compose_mask without compose_weights')
+            cw = torch.as_tensor(compose_weights, dtype=torch.float32).cpu()
+            n_cond = cw.shape[1] if cw.dim() == 2 else 0
+            if cw.dim() != 2 or cw.shape[0] != init_noise.shape[0] or not 1 <= n_cond <= COMPOSE_MAX:
+                raise ValueError(f'compose_weights {tuple(cw.shape)}: expected [P={init_noise.shape[0]}, K] with 1 <= K <= {COMPOSE_MAX}')
+            if not bool(torch.isfinite(cw).all()) or not bool((cw[:, 0] > 0).all()):
+                raise ValueError('compose_weights must be finite, and the primary condition (column 0) weighted above 0')
+            if n_cond > 1:
+                if (compose_text is None or compose_mask is None or text.dim() != 3 or compose_text.dim() != 4
+                        or tuple(compose_text.shape) != (text.shape[0], n_cond - 1) + tuple(text.shape[1:])
+                        or tuple(compose_mask.shape) != tuple(compose_text.shape[:3])):
+                    raise ValueError(f'compose_text / compose_mask with text {tuple(text.shape)} and K = {n_cond}: expected [P, K-1, Lt, Cctx] and [P, K-1, Lt]')
+            elif compose_text is not None and compose_text.shape[1] != 0:
+                raise ValueError('compose_weights [P, 1] takes no compose_text')
+            if not (n_cond == 1 and bool((cw == 1).all())):   # (one condition with weight 1: the plain call)
+                if controlnet is not None or canvas is not None or canvas_loop is not None or context_weights is not None:
+                    raise ValueError('composed guidance does not combine with a ControlNet, a canvas, a loop or a prompt timeline')
+                compose = cw.contiguous()
         if context_weights is not None:
             if canvas is not None or canvas_loop is not None or controlnet is not None:
                 raise ValueError('a prompt timeline does not combine with a canvas, a loop or a ControlNet')
@@ -243,7 +273,13 @@ class LatentSampler:
         ts = [int(t) for t in self.scheduler.timesteps]
         coefs = self.scheduler.ddim_coefficients(eta)
         use_cfg = bool(guidance_scale)
-        if use_cfg:
+        if compose is not None:   # [c_0 (P rows) | c_1 | ... | c_{K-1} | u]: row k P + p is condition k of sample p
+            if not use_cfg or float(guidance_scale) <= 0:
+                raise ValueError('composed guidance needs a guidance_scale above 0')
+            extra = [compose_text[:, k] for k in range(compose.shape[1] - 1)]
+            ctx = torch.cat([text] + extra + [uncond_text], dim=0)
+            msk = torch.cat([text_mask] + [compose_mask[:, k].to(text_mask.dtype) for k in range(compose.shape[1] - 1)] + [uncond_mask], dim=0)
+        elif use_cfg:
             ctx = torch.cat([text, uncond_text], dim=0)          # src/inference.py:76-77
             msk = torch.cat([text_mask, uncond_mask], dim=0)
         else:
@@ -269,6 +305,9 @@ class LatentSampler:
                 # (-3, EZDIT_E_STATE: the workspace was bound again since, which cleared the table and ended the call it belonged to)
                 self._table_call(u.lib.ezdit_sampler_set_canvas, None, 0, 0, 1, ok=(-3,))
                 u._canvas_on = False
+            if getattr(u, '_compose_on', False):   # ... and so does an earlier call's composition, which the attach and the context weights below refuse to meet
+                self._table_call(u.lib.ezdit_sampler_set_compose_weights, None, 0, 0, ok=(-3,))
+                u._compose_on = False
             u.bind(B, L, ctx.shape[1], ddim_steps)
             u.prepare_context(ctx, msk)
             u.prepare_timesteps(ts, per_row=False)
@@ -297,10 +336,19 @@ class LatentSampler:
                     wt = torch.cat([wt, one], dim=0)
                 u.set_context_weights(wt, st)
             arr = (_lib.EzditDdimCoef * ddim_steps)(*[_lib.EzditDdimCoef(*c) for c in coefs])
-            _lib.check(u.lib.ezdit_sampler_begin(u._h, _ptr(self.latents), P, _ptr(self.noise), arr, ddim_steps,
-                                                 float(guidance_scale or 0.0), float(guidance_rescale or 0.0),
-                                                 _ptr(self.gt), _ptr(self.gt_mask),
-                                                 C.c_void_p(self.stream.cuda_stream)))
+            if compose is not None:
+                n_cond = compose.shape[1]
+                _lib.check(u.lib.ezdit_sampler_begin_composed(u._h, _ptr(self.latents), P, _ptr(self.noise), arr, ddim_steps,
+                                                              float(guidance_scale), float(guidance_rescale or 0.0), _ptr(self.gt), _ptr(self.gt_mask),
+                                                              n_cond, (C.c_float * (P * n_cond))(*compose.flatten().tolist()),
+                                                              C.c_void_p(self.stream.cuda_stream)))
+            else:
+                _lib.check(u.lib.ezdit_sampler_begin(u._h, _ptr(self.latents), P, _ptr(self.noise), arr, ddim_steps,
+                                                     float(guidance_scale or 0.0), float(guidance_rescale or 0.0),
+                                                     _ptr(self.gt), _ptr(self.gt_mask),
+                                                     C.c_void_p(self.stream.cuda_stream)))
+        self.compose_K = None if compose is None else compose.shape[1]
+        u._compose_on = compose is not None
         self.n_steps = ddim_steps
         self.P = P
         self.x0_hist = None
@@ -395,6 +443,16 @@ class LatentSampler:
         for p in reversed(range(P)):
             out[0, :, offs[p]:offs[p] + L] = self.latents[p]
         return out
+
+    def set_compose_weights(self, weights):
+        """The weights [P, K] of the composed call prepare() began (``compose_weights``): same P and K, w[p, 0] > 0, finite.  The captured step reads them at
+        run time: new values need no re-capture.  Switching composition on or off, or another K, is another batch: prepare() again."""
+        if getattr(self, 'compose_K', None) is None:
+            raise ValueError('set_compose_weights: prepare(compose_weights=...) first')
+        w = torch.as_tensor(weights, dtype=torch.float32).cpu()
+        if tuple(w.shape) != (self.P, self.compose_K):
+            raise ValueError(f'compose weights {tuple(w.shape)}: the call was prepared with [P={self.P}, K={self.compose_K}]')
+        self._table_call(self.unet.lib.ezdit_sampler_set_compose_weights, (C.c_float * w.numel())(*w.flatten().tolist()), self.P, self.compose_K)
 
     def set_cn_scales(self, scales=None):
         """conditioning_scale per sample of the call prepare() began with a ControlNet: a list of P values, or None to go back to the call's scalar.
@@ -666,6 +724,37 @@ def _timeline_entries(text_raw, prompt_weights, frames):
     return entries, W
 
 
+def compose_entries(compose, n_prompts):
+    """``compose`` of inference() as (extras, W): extras[k][i] is the text of extra condition k of prompt i and W [n_prompts, K] the weights, column 0 the
+    primary prompt's 1.  One prompt takes a list of (text, weight) pairs; several take one such list (or None) per prompt.  Lists shorter than the longest
+    are padded with the prompt's own text at weight 0 (a dropped condition: its row is not read).  (None, None) when no prompt composes anything: the plain call."""
+    if n_prompts == 1 and compose and all(isinstance(e, (list, tuple)) and len(e) == 2 and isinstance(e[0], str) for e in compose):
+        compose = [compose]
+    if not isinstance(compose, (list, tuple)) or len(compose) != n_prompts:
+        raise ValueError(f'compose: a list of (text, weight) pairs for one prompt, or one such list (or None) per prompt; got {len(compose) if isinstance(compose, (list, tuple)) else compose!r} entries for {n_prompts} prompts')
+    lists = []
+    for i, c in enumerate(compose):
+        c = list(c or [])
+        for e in c:
+            if not (isinstance(e, (list, tuple)) and len(e) == 2 and isinstance(e[0], str)):
+                raise ValueError(f'compose of prompt {i}: expected (text, weight) pairs, got {e!r}')
+            w = float(e[1])
+            if w != w or w in (float('inf'), float('-inf')):
+                raise ValueError(f'compose of prompt {i}: weight {e[1]!r} is not finite')
+        lists.append(c)
+    n_extra = max(len(c) for c in lists)
+    if n_extra == 0:
+        return None, None
+    if n_extra + 1 > COMPOSE_MAX:
+        raise ValueError(f'{n_extra} composed prompts: at most {COMPOSE_MAX - 1} next to the primary one')
+    W = torch.zeros(n_prompts, n_extra + 1)
+    W[:, 0] = 1.0
+    for i, c in enumerate(lists):
+        for k, e in enumerate(c):
+            W[i, k + 1] = float(e[1])
+    return lists, W
+
+
 @torch.no_grad()
 def inference_controlnet(autoencoder, unet, controlnet, gt, gt_mask, condition, tokenizer, text_encoder, params,
                          noise_scheduler, text_raw, neg_text=None, audio_frames=500, guidance_scale=3,
@@ -683,9 +772,17 @@ def inference_controlnet(autoencoder, unet, controlnet, gt, gt_mask, condition, 
 def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, noise_scheduler, text_raw,
               neg_text=None, audio_frames=500, guidance_scale=3, guidance_rescale=0.0, ddim_steps=50, eta=1,
               random_seed=2024, device='cuda', use_graph=True, controlnet=None, condition=None, conditioning_scale=1.0,
-              first_index=None, init_latents=None, strength=None, attention_window=None, prompt_weights=None, canvas_loop=None, decode_context=None, canvas_offsets=None, canvas_ramp=None,
+              first_index=None, init_latents=None, strength=None, attention_window=None, prompt_weights=None, compose=None, canvas_loop=None, decode_context=None, canvas_offsets=None, canvas_ramp=None,
               solver='ddim'):
     """Same signature and semantics as the reference's ``inference`` (src/inference.py:26-107).
+
+    Extension (composed guidance): ``compose`` gives a prompt further prompts with weights: for one prompt a list of (text, weight) pairs, for several one such
+    list (or None) per prompt.  Every prompt is guided against the shared negative prompt with its own weight, v = u + guidance_scale ((c_0 - u) + sum_k w_k (c_k - u));
+    the primary prompt has weight 1 and is the reference of the guidance rescale.  A negative weight is a negative prompt that keeps the empty-prompt baseline (``neg_text``
+    replaces it).  Shorter lists are padded with the prompt's own text at weight 0; all prompts of the call are encoded in one text-encoder batch.  The batch grows to
+    (K + 1) rows per prompt.  It combines with ``audio_frames`` lists, per-prompt settings, ``solver``, gt / gt_mask, ``init_latents`` and ``attention_window``;
+    ValueError with a ControlNet, a canvas or loop, a timeline, without guidance, or for a call that would be sharded over ranks.  No entry for any prompt is the
+    plain call, bit for bit.  Audio quality on the real checkpoints is unmeasured.
 
     Extension (sliding-window self-attention): ``attention_window`` is a radius in latent frames: in every block's self-attention a frame attends to the frames
     within that many frames of it, so a row longer than the trained length stays inside the trained range of relative positions.  It is set on ``unet`` (and on
@@ -745,7 +842,7 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
             return inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, noise_scheduler, text_raw, neg_text, audio_frames, guidance_scale,
                              guidance_rescale, ddim_steps, eta, random_seed, device, use_graph, controlnet, condition, conditioning_scale, first_index=first_index,
                              init_latents=init_latents, strength=strength, canvas_loop=canvas_loop, decode_context=decode_context, canvas_offsets=canvas_offsets,
-                             canvas_ramp=canvas_ramp, solver=solver, prompt_weights=prompt_weights)
+                             canvas_ramp=canvas_ramp, solver=solver, prompt_weights=prompt_weights, compose=compose)
         finally:
             for m, prev in zip(models, previous):
                 m.set_attention_window(prev)
@@ -801,9 +898,20 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
             raise ValueError('a prompt timeline is not sharded over ranks: call it with one rank\'s prompts')
         timeline = _timeline_entries(text_raw, prompt_weights, frames if frames is not None else [int(audio_frames)] * len(text_raw))
         text_raw = [p for entry in timeline[0] for p in entry]      # every prompt of every entry, encoded in one batch below
+    composed = None
+    if compose is not None:
+        if controlnet is not None or canvas_offsets is not None or timeline is not None:
+            raise ValueError('composed guidance does not combine with a ControlNet, a canvas or loop, or a prompt timeline')
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and len(text_raw) > 1 and first_index is None:
+            raise ValueError('composed guidance is not sharded over ranks: call it with one rank\'s prompts')
+        lists, cw = compose_entries(compose, len(text_raw))
+        if lists is not None:
+            composed = (len(text_raw), cw)
+            # every prompt of the call in ONE text-encoder batch: the primaries, then extra condition k of every prompt (a missing one: the prompt's own text, weight 0)
+            text_raw = list(text_raw) + [lists[i][k][0] if k < len(lists[i]) else text_raw[i] for k in range(cw.shape[1] - 1) for i in range(len(text_raw))]
     if controlnet is not None:
         condition = pad_conditions(condition, frames if frames is not None else audio_frames, len(text_raw))
-    if canvas_offsets is None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and len(text_raw) > 1 and first_index is None:
+    if canvas_offsets is None and composed is None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and len(text_raw) > 1 and first_index is None:
         from .dist import sample_sharded
         n_all = len(text_raw)
         ratio_ = params['autoencoder']['sr'] // params['autoencoder']['latent_sr']
@@ -846,6 +954,11 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
                 t4[i, :len(entry)], m4[i, :len(entry)] = text[at:at + len(entry)], text_mask[at:at + len(entry)]
                 at += len(entry)
             text, text_mask = t4, m4
+        if composed is not None:      # [N, K-1, Lt, Cctx]: the batch was primaries, then condition 1 of every prompt, condition 2 of every prompt, ...
+            n_prompts, cw = composed
+            comp_text = text[n_prompts:].reshape((cw.shape[1] - 1, n_prompts) + tuple(text.shape[1:])).transpose(0, 1).contiguous()
+            comp_mask = text_mask[n_prompts:].reshape(cw.shape[1] - 1, n_prompts, text.shape[1]).transpose(0, 1).contiguous()
+            text, text_mask = text[:n_prompts], text_mask[:n_prompts]
         ub = tokenizer(neg_text * n_prompts if len(neg_text) == 1 else neg_text, max_length=max_len,
                        padding="max_length", truncation=True, return_tensors="pt")
         uncond_text, uncond_mask = ub.input_ids.to(device), ub.attention_mask.to(device).bool()
@@ -874,6 +987,8 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
         kw['solver'] = solver
     if timeline is not None:
         kw['context_weights'] = timeline[1]
+    if composed is not None:
+        kw.update(compose_text=comp_text.float(), compose_mask=comp_mask, compose_weights=composed[1])
     if canvas_loop is not None:
         kw['canvas_loop'] = (canvas_offsets, canvas_loop, canvas_ramp)
     elif long_form:

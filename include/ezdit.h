@@ -139,7 +139,10 @@ int    ezdit_bind_workspace(ezdit_handle* h, void* dev_ws, size_t bytes, int B, 
  *                                                   off after on, 0)
  *       canvas (.._set_canvas, .._set_canvas_loop:  off <-> on, another T or ramp,    ezdit_bind_workspace, ezdit_sampler_begin, either setter
  *         one table, a line or a ring)              line <-> ring                       with NULL
- * ezdit_bind_workspace ends the sampler call as well: ezdit_sampler_run and the call-scoped setters (the last four) return EZDIT_E_STATE
+ *       compose weights (.._begin_composed         off <-> on, another K: only a      ezdit_bind_workspace, ezdit_sampler_begin,
+ *         switches it on, .._set_compose_weights     begin does either                  ezdit_sampler_begin_composed (which sets its own)
+ *         replaces the values)
+ * ezdit_bind_workspace ends the sampler call as well: ezdit_sampler_run and the call-scoped setters (the last five) return EZDIT_E_STATE
  * until the next ezdit_sampler_begin, whatever shape was bound. */
 
 /* ---- step-invariant work, hoisted (reference recomputes it every step) ----------------------- */
@@ -315,6 +318,47 @@ int ezdit_sampler_set_multistep(ezdit_handle* h, const float* c_hist, int n_step
  * not applied).  dev_scratch >= P*256 floats.  Asynchronous, no handle needed. */
 int ezdit_cfg_multistep_step(const float* dev_pred, float* dev_latents, float* dev_x0_hist, const float* dev_params,
                              const int32_t* dev_lens, int L, int P, int n, float* dev_scratch, ezdit_stream stream);
+
+/* ---- composed guidance: K weighted prompts per sample in the fused step ---------------------------------------------------------- */
+/* Several conditions per sample, each guided with its own weight against ONE shared unconditional row (the AND of "Compositional Visual Generation with
+ * Composable Diffusion Models", Liu et al. 2022).  Sample p of P carries K conditions (1 <= K <= EZDIT_COMPOSE_MAX) with the weights w[p][0 .. K-1]:
+ *   batch rows   [c_0 (P rows) | c_1 (P rows) | ... | c_{K-1} (P rows) | u (P rows)], B = (K + 1) P: row k P + p is condition k of sample p, row K P + p its
+ *                unconditional row.  K = 1 is the layout of ezdit_sampler_begin.  Batch row b reads latent row b % P and length b % P, as always.
+ *   combination  in fp32, k ascending:  d = w_0 (c_0 - u);  d += w_k (c_k - u) for k = 1 .. K-1;  v = u + g_p d, g_p the sample's guidance_scale (the call's
+ *                scalar or its row of ezdit_sampler_set_sample_params).  Everything behind v is the step as it is without composition: rescale, x0 / eps,
+ *                the DDIM or 2M update, noise, history, padded frames, held samples.
+ *   rescale      the reference is the PRIMARY condition: ratio = std(c_0) / std(v), unbiased, over the sample's valid elements
+ *   weights      w[p][0] finite and > 0; the others any finite value.  A negative weight steers away from its prompt and keeps the empty-prompt baseline.
+ *                A weight of exactly 0: row k P + p is computed by the denoiser (the batch keeps its shape) but NOT read by the update -- how a sample
+ *                with fewer prompts than K sits in a batch.  A sample with g_p <= 0 reads c_0 alone.
+ *   identity     K = 1 with w = 1 gives the bits of the call without composition.
+ * ezdit_sampler_begin_composed takes the arguments of ezdit_sampler_begin plus K and the HOST array weights [P][K].  The weights are a run-time table of
+ * the step (contract above), call-scoped, in a workspace region of their own (B floats; ezdit_workspace_bytes grows by 256 .. 1024 bytes): one captured step
+ * serves every set of values, which ezdit_sampler_set_compose_weights replaces (same P and K, the same rules for the values; it cannot switch composition on
+ * or change K -- that is another batch layout, so another begin).  With NULL (or P = 0) it switches composition off: a call of K = 1 goes on as the plain call,
+ * one of K > 1 ENDS there (its batch has no plain reading: ezdit_sampler_run returns EZDIT_E_STATE until the next begin) -- what a caller does before it
+ * attaches a ControlNet or sets context weights on a handle whose last call was composed.  ezdit_sampler_begin itself is unchanged and begins a call
+ * without composition.
+ * Per-sample lengths, per-sample settings, the multistep solver, a start table, gt / gt_mask and an attention window work unchanged.
+ * EZDIT_E_INVALID: guidance_scale <= 0 (composition is guidance); K outside [1, EZDIT_COMPOSE_MAX]; B != (K + 1) P; a non-finite weight; w[p][0] <= 0;
+ * lengths that differ between the K + 1 rows of a sample; P or K of the setter that are not the call's.  EZDIT_E_UNSUPPORTED: an attached ControlNet,
+ * context weights that are on; ezdit_sampler_attach_controlnet, ezdit_set_context_weights and the canvas setters refuse likewise while composition is on.
+ * EZDIT_E_STATE: ezdit_sampler_set_compose_weights on a call that was not begun composed. */
+#define EZDIT_COMPOSE_MAX 8
+int ezdit_sampler_begin_composed(ezdit_handle* h, float* dev_latents, int P, const float* dev_noise,
+                                 const ezdit_ddim_coef* coefs, int n_steps,
+                                 float guidance_scale, float guidance_rescale,
+                                 const float* dev_gt, const uint8_t* dev_gt_mask, int K, const float* weights, ezdit_stream stream);
+int ezdit_sampler_set_compose_weights(ezdit_handle* h, const float* weights, int P, int K, ezdit_stream stream);
+
+/* The composed form of ezdit_cfg_ddim_step_per_sample / ezdit_cfg_multistep_step, for callers that keep their own loop: dev_pred fp32 [(K + 1) P][n] in
+ * the row order above, dev_weights fp32 [P][K] ON THE DEVICE (the caller guarantees the rules for the values; no value makes the kernels touch memory
+ * outside the (K + 1) P n elements), dev_params [P][8] = (guidance_scale, guidance_rescale, sa, sb, c_x0, c_dir, sigma, c_hist) as there.  dev_x0_hist NULL:
+ * the DDIM form (dev_noise [P][n] of this step, or NULL); given: the multistep form (dev_noise must be NULL).  dev_lens, L, dev_scratch (>= P*256 floats,
+ * always needed) as there.  Asynchronous, no handle needed.  EZDIT_E_INVALID: a NULL pointer among pred, latents, params, weights, scratch; K outside
+ * [1, EZDIT_COMPOSE_MAX]; P < 1, n < 2; L not dividing n with dev_lens; noise together with a history. */
+int ezdit_cfg_compose_step(const float* dev_pred, float* dev_latents, const float* dev_noise, float* dev_x0_hist, const float* dev_params,
+                           const float* dev_weights, int K, const int32_t* dev_lens, int L, int P, int n, float* dev_scratch, ezdit_stream stream);
 
 /* ---- audio-to-audio: start the sampler from a noised clip, per sample ------------------------------------------------------------ */
 /* Noise a clean VAE latent into the model's space at each sample's start step, in place of the init noise:
