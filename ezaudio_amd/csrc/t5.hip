@@ -267,14 +267,17 @@ size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // The four projections of a layer as (N, K).  What launch_gemm needs of a shape (csrc/gemm.hip: K a positive multiple of BK; common.h stage_offsets: the
 // furthest A and W element below 2^31) is decided HERE, by ezt5_bind_workspace, so that ezt5_encode never meets a shape refusal between two launches.
+int t5_check_gemm_shape(long M, long N, long K) {
+    if (K <= 0 || K % BK || N % 4 || M * K >= (1L << 31) || N * K >= (1L << 31) || M * N >= (1L << 31))
+        return ez_fail(EZDIT_E_UNSUPPORTED, "ezt5: the GEMM refuses M=%ld N=%ld K=%ld (K a multiple of %d, every operand below 2^31 elements)", M, N, K, BK);
+    return EZDIT_OK;
+}
+
 int t5_check_gemm_shapes(const ezt5_handle* h, long M) {
     const long D = h->cfg.d_model, I = h->inner, F = h->cfg.d_ff;
     const long nk[4][2] = {{3 * I, D}, {D, I}, {2 * F, D}, {D, F}};
-    for (const auto& s : nk) {
-        const long N = s[0], K = s[1];
-        if (K <= 0 || K % BK || N % 4 || M * K >= (1L << 31) || N * K >= (1L << 31) || M * N >= (1L << 31))
-            return ez_fail(EZDIT_E_UNSUPPORTED, "ezt5: the GEMM refuses M=%ld N=%ld K=%ld (K a multiple of %d, every operand below 2^31 elements)", M, N, K, BK);
-    }
+    for (const auto& s : nk)
+        if (int rc = t5_check_gemm_shape(M, s[0], s[1])) return rc;
     return EZDIT_OK;
 }
 
@@ -466,14 +469,66 @@ int ezt5_encode(ezt5_handle* h, const int32_t* dev_ids, const uint8_t* dev_mask,
     return launch_status("k_t5_embed_rms (final)");
 }
 
-int ezt5_test_attention(const void* dev_q, const void* dev_k, const void* dev_v, const float* dev_bias, const uint8_t* dev_mask, void* dev_out,
-                        int B, int H, int L, ezdit_stream stream) {
+// Everything that bounds an address is refused here, before the first HIP call (as ezdit_test_row and its siblings do): the kernel reads rows of ld elements in
+// groups of 8 (16-byte loads of bf16, two of fp32), stores 4 bf16 at a time into rows of ldo, and reads bias[h][bias_half - (L - 1) .. bias_half + L - 1].
+int ezt5_test_attention_ex(const void* dev_q, const void* dev_k, const void* dev_v, int f32_in, int ld, const float* dev_bias, int bias_ld, int bias_half,
+                           const uint8_t* dev_mask, void* dev_out, int ldo, int B, int H, int L, ezdit_stream stream) {
     if (!dev_q || !dev_k || !dev_v || !dev_bias || !dev_mask || !dev_out) return ez_fail(EZDIT_E_INVALID, "ezt5_test_attention: null argument");
     if (B <= 0 || H <= 0 || L <= 0 || B > 65535 || H > 65535) return ez_fail(EZDIT_E_INVALID, "ezt5_test_attention: B=%d, H=%d, L=%d out of range", B, H, L);
     if (L > T5_MAX_L) return ez_fail(EZDIT_E_UNSUPPORTED, "ezt5_test_attention: L=%d, the kernel covers up to %d tokens", L, T5_MAX_L);
+    if (ld < 64 * H || ld % 8) return ez_fail(EZDIT_E_INVALID, "ezt5_test_attention: ld=%d must be a multiple of 8 and at least 64 H = %d", ld, 64 * H);
+    if (ldo < 64 * H || ldo % 4) return ez_fail(EZDIT_E_INVALID, "ezt5_test_attention: ldo=%d must be a multiple of 4 and at least 64 H = %d", ldo, 64 * H);
+    if (bias_half < L - 1 || bias_ld < bias_half + L)
+        return ez_fail(EZDIT_E_INVALID, "ezt5_test_attention: bias_half=%d, bias_ld=%d do not hold the distances -(L - 1) .. L - 1 of L=%d", bias_half, bias_ld, L);
+    if ((uintptr_t)dev_q & 15 || (uintptr_t)dev_k & 15 || (uintptr_t)dev_v & 15 || (uintptr_t)dev_out & 7 || (uintptr_t)dev_bias & 3)
+        return ez_fail(EZDIT_E_INVALID, "ezt5_test_attention: operands must be 16-byte, the output 8-byte and the bias 4-byte aligned");
     (void)hipGetLastError();
-    launch_t5_attn<false>(dev_q, dev_k, dev_v, H * 64, dev_bias, 2 * L - 1, L - 1, dev_mask, (bf16_t*)dev_out, H * 64, B, H, L, (hipStream_t)stream);
+    if (f32_in) launch_t5_attn<true>(dev_q, dev_k, dev_v, ld, dev_bias, bias_ld, bias_half, dev_mask, (bf16_t*)dev_out, ldo, B, H, L, (hipStream_t)stream);
+    else launch_t5_attn<false>(dev_q, dev_k, dev_v, ld, dev_bias, bias_ld, bias_half, dev_mask, (bf16_t*)dev_out, ldo, B, H, L, (hipStream_t)stream);
     return launch_status("k_t5_attn");
+}
+
+int ezt5_test_attention(const void* dev_q, const void* dev_k, const void* dev_v, const float* dev_bias, const uint8_t* dev_mask, void* dev_out,
+                        int B, int H, int L, ezdit_stream stream) {
+    if (H <= 0 || H > 65535 || L <= 0) return ez_fail(EZDIT_E_INVALID, "ezt5_test_attention: B=%d, H=%d, L=%d out of range", B, H, L);
+    return ezt5_test_attention_ex(dev_q, dev_k, dev_v, 0, H * 64, dev_bias, 2 * L - 1, L - 1, dev_mask, dev_out, H * 64, B, H, L, stream);
+}
+
+int ezt5_test_embed_rms(const int32_t* dev_ids, const float* dev_emb, int vocab, const float* dev_x_in, float* dev_x_out, const float* dev_w, float eps,
+                        void* dev_u_bf16, float* dev_out_f32, int M, int D, ezdit_stream stream) {
+    if (!dev_w) return ez_fail(EZDIT_E_INVALID, "ezt5_test_embed_rms: null weight");
+    if ((dev_ids != nullptr) == (dev_x_in != nullptr)) return ez_fail(EZDIT_E_INVALID, "ezt5_test_embed_rms: exactly one of ids / x_in");
+    if ((dev_u_bf16 != nullptr) == (dev_out_f32 != nullptr)) return ez_fail(EZDIT_E_INVALID, "ezt5_test_embed_rms: exactly one of u_bf16 / out_f32");
+    if (dev_ids && (!dev_emb || !dev_x_out || vocab <= 0)) return ez_fail(EZDIT_E_INVALID, "ezt5_test_embed_rms: ids need emb, x_out and vocab=%d > 0", vocab);
+    if (M <= 0 || D <= 0 || D % 4) return ez_fail(EZDIT_E_INVALID, "ezt5_test_embed_rms: M=%d must be positive and D=%d a positive multiple of 4", M, D);
+    if ((uintptr_t)dev_emb & 15 || (uintptr_t)dev_x_in & 15 || (uintptr_t)dev_x_out & 15 || (uintptr_t)dev_w & 15 || (uintptr_t)dev_u_bf16 & 7 || (uintptr_t)dev_out_f32 & 15)
+        return ez_fail(EZDIT_E_INVALID, "ezt5_test_embed_rms: fp32 buffers must be 16-byte, the bf16 output 8-byte aligned");
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_t5_embed_rms, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, dev_ids, dev_emb, vocab, dev_x_in, dev_x_out, dev_w, eps,
+                       (bf16_t*)dev_u_bf16, dev_out_f32, M, D);
+    return launch_status("k_t5_embed_rms");
+}
+
+int ezt5_test_gated_gelu(const float* dev_h, void* dev_g, int M, int F, ezdit_stream stream) {
+    if (!dev_h || !dev_g) return ez_fail(EZDIT_E_INVALID, "ezt5_test_gated_gelu: null argument");
+    if (M <= 0 || F <= 0 || F % 4) return ez_fail(EZDIT_E_INVALID, "ezt5_test_gated_gelu: M=%d must be positive and F=%d a positive multiple of 4", M, F);
+    if ((uintptr_t)dev_h & 15 || (uintptr_t)dev_g & 7) return ez_fail(EZDIT_E_INVALID, "ezt5_test_gated_gelu: h must be 16-byte, g 8-byte aligned");
+    (void)hipGetLastError();
+    const long total = (long)M * (F / 4);
+    hipLaunchKernelGGL(k_t5_gated_gelu, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dev_h, (bf16_t*)dev_g, (long)M, F);
+    return launch_status("k_t5_gated_gelu");
+}
+
+int ezt5_test_gemm(const void* dev_A, int K, const void* dev_W, int N, const float* dev_resid, float* dev_out, int M, ezdit_stream stream) {
+    if (!dev_A || !dev_W || !dev_out) return ez_fail(EZDIT_E_INVALID, "ezt5_test_gemm: null argument");
+    if (M <= 0 || N <= 0) return ez_fail(EZDIT_E_INVALID, "ezt5_test_gemm: M=%d and N=%d must be positive", M, N);
+    if (int rc = t5_check_gemm_shape(M, N, K)) return rc;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) return ez_fail(EZDIT_E_UNSUPPORTED, "ezt5_test_gemm: device index %d, the GEMM covers devices 0 - 31", dev);
+    (void)hipGetLastError();
+    if (t5_gemm((const bf16_t*)dev_A, K, (const bf16_t*)dev_W, N, dev_resid, dev_out, M, (hipStream_t)stream))
+        return ez_fail(EZDIT_E_HIP, "ezt5_test_gemm: the GEMM M=%d N=%d K=%d was not launched", M, N, K);
+    return launch_status("k_gemm (t5 hook)");
 }
 
 int ezt5_test_rms(const float* dev_x, const float* dev_w, float eps, void* dev_out, int M, int D, ezdit_stream stream) {

@@ -739,6 +739,21 @@ int    ezt5_test_attention(const void* dev_q, const void* dev_k, const void* dev
                            int B, int H, int L, ezdit_stream stream);
 /* ... and k_t5_embed_rms on x fp32 [M][D] (D % 4 == 0), w fp32 [D] -> out bf16 [M][D] = bf16(x rsqrt(mean(x^2) + eps) w) */
 int    ezt5_test_rms(const float* dev_x, const float* dev_w, float eps, void* dev_out, int M, int D, ezdit_stream stream);
+/* The encoder's launchers with their full argument lists, one hook per launch of ezt5_encode (tests/test_t5_kernels_gpu.py chains them into a layer, bit for bit).
+ * Everything that bounds an address is refused (EZDIT_E_INVALID / EZDIT_E_UNSUPPORTED) before the first HIP call.
+ * k_t5_attn in either operand form: f32_in = 0 bf16 operands, 1 fp32 operands rounded in the loader (ezt5_encode: one interleaved buffer, k = q + inner, v = q + 2 inner,
+ * ld = 3 inner).  q, k, v rows [B L][ld] (ld >= 64 H, a multiple of 8), bias fp32 [H][bias_ld] with entry (key - query) + bias_half (bias_half >= L - 1,
+ * bias_ld >= bias_half + L), out bf16 rows [B L][ldo] (ldo >= 64 H, a multiple of 4; columns >= 64 H are not written). */
+int    ezt5_test_attention_ex(const void* dev_q, const void* dev_k, const void* dev_v, int f32_in, int ld, const float* dev_bias, int bias_ld, int bias_half,
+                              const uint8_t* dev_mask, void* dev_out, int ldo, int B, int H, int L, ezdit_stream stream);
+/* k_t5_embed_rms: exactly one of ids (int32 [M], clamped to [0, vocab); needs emb fp32 [vocab][D] and x_out fp32 [M][D], which receives the gathered rows) / x_in fp32 [M][D]
+ * (x_out is then not touched and may alias x_in), exactly one of u_bf16 [M][D] / out_f32 [M][D]; D a positive multiple of 4 */
+int    ezt5_test_embed_rms(const int32_t* dev_ids, const float* dev_emb, int vocab, const float* dev_x_in, float* dev_x_out, const float* dev_w, float eps,
+                           void* dev_u_bf16, float* dev_out_f32, int M, int D, ezdit_stream stream);
+/* k_t5_gated_gelu: h fp32 [M][2 F] -> g bf16 [M][F] = gelu_new(h[:, :F]) h[:, F:]; F a positive multiple of 4 */
+int    ezt5_test_gated_gelu(const float* dev_h, void* dev_g, int M, int F, ezdit_stream stream);
+/* the encoder's GEMM call: out fp32 [M][N] = A bf16 [M][K] . W bf16 [N][K]^T (+ resid fp32 [M][N], nullable), after the shape check ezt5_bind_workspace makes */
+int    ezt5_test_gemm(const void* dev_A, int K, const void* dev_W, int N, const float* dev_resid, float* dev_out, int M, ezdit_stream stream);
 
 #ifdef __cplusplus
 }

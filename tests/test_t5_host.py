@@ -158,7 +158,7 @@ def test_library_exports_the_t5_symbols_of_the_header(lib):
     src = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'ezdit.h')).read(), flags=re.S)
     declared = set(re.findall(r'\b(ezt5_[a-z_0-9]+)\s*\(', src))
     assert {'ezt5_create', 'ezt5_destroy', 'ezt5_blob_bytes', 'ezt5_bind_weights', 'ezt5_workspace_bytes', 'ezt5_bind_workspace', 'ezt5_encode',
-            'ezt5_test_attention'} <= declared
+            'ezt5_test_attention', 'ezt5_test_attention_ex', 'ezt5_test_embed_rms', 'ezt5_test_gated_gelu', 'ezt5_test_gemm'} <= declared
     out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
     exported = set(re.findall(r' T (ezt5_[a-z_0-9]+)', out))
     assert declared == exported == set(_lib.T5_PROTOTYPES)
