@@ -20,6 +20,10 @@ if os.environ.get('EZAUDIO_ABLATE'):   # timing-only variants of the ping-pong K
     FLAGS.append('-DEZ_ABLATE')
 if os.environ.get('EZAUDIO_DIAG'):      # diagnostic build: the `zfake` option (LayerNorm-algebra consumers on neutral tables); never in the shipped build
     FLAGS.append('-DEZ_DIAG')
+# per translation unit: the step kernels of these take their prologue arguments as leading scalar parameters, which gfx950 delivers in user SGPRs at wave
+# launch (csrc/gemm_ks.h); hipcc preloads only on request.  14 = what is left of the 16 user SGPRs behind the kernel-argument pointer
+PRELOAD = ['-mllvm', '-amdgpu-kernarg-preload-count=14']
+UNIT_FLAGS = {'gemm.hip': PRELOAD}
 
 
 def source_hash():
@@ -32,6 +36,8 @@ def source_hash():
         h.update(os.path.basename(f).encode())
         with open(f, 'rb') as fh:
             h.update(fh.read())
+    for src in sorted(UNIT_FLAGS):   # code-generation options of single translation units (FLAGS itself: the same for every tree, diagnostic builds aside)
+        h.update((src + ' ' + ' '.join(UNIT_FLAGS[src])).encode())
     return h.hexdigest()[:16]
 
 
@@ -62,7 +68,7 @@ def build(force=False, verbose=True):
 
     def compile_one(job):
         s, o = job
-        cmd = [hipcc] + FLAGS + ['-c', s, '-o', o]
+        cmd = [hipcc] + FLAGS + UNIT_FLAGS.get(os.path.basename(s), []) + ['-c', s, '-o', o]
         r = subprocess.run(cmd, capture_output=True, text=True)
         return job, r
 

@@ -27,6 +27,23 @@ int ez_fail(int code, const char* fmt, ...) {
     return code;
 }
 #define fail ez_fail
+// the reason a launcher gave for refusing a configuration (ez_refuse), until the caller that reports the refusal takes it
+static thread_local std::string g_refusal;
+int ez_refuse(const char* fmt, ...) {
+    char buf[384];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g_refusal = buf;
+    return 1;
+}
+static std::string take_refusal() {
+    std::string r;
+    if (!g_refusal.empty()) r = " (" + g_refusal + ")";
+    g_refusal.clear();
+    return r;
+}
 
 namespace {
 
@@ -549,18 +566,19 @@ struct Ctx {
     hipError_t err = hipSuccess;
     int rc = EZDIT_OK;
     const char* where = nullptr;
+    std::string why;   // the reason the refusing launcher gave (ez_refuse), for the message
     // cycle-stamp buffer for the launch about to be issued (nullptr unless the 'stamp_launch' option selects it)
     unsigned long long* stamps() const { return (g_gemm_ts && h->launches == h->opt_stamp_launch) ? g_gemm_ts : nullptr; }
     void launched(const char* what, int launch_rc = 0) {
         if (h->opt_trace_launches) fprintf(stderr, "launch %d %s\n", h->launches, what);
         h->launches++;
-        if (launch_rc != 0 && rc == EZDIT_OK) { rc = launch_rc; where = what; }
+        if (launch_rc != 0 && rc == EZDIT_OK) { rc = launch_rc; where = what; why = take_refusal(); }
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess && err == hipSuccess) { err = e; where = what; }
     }
     bool bad() const { return err != hipSuccess || rc != EZDIT_OK; }
     int result() const {
-        if (rc != EZDIT_OK) return fail(rc, "%s: configuration not supported by the HIP kernels", where ? where : "?");
+        if (rc != EZDIT_OK) return fail(rc, "%s: configuration not supported by the HIP kernels%s", where ? where : "?", why.c_str());
         if (err != hipSuccess) return fail(EZDIT_E_HIP, "launch of %s failed: %s", where ? where : "?", hipGetErrorString(err));
         return EZDIT_OK;
     }
@@ -727,7 +745,8 @@ void resolve_workspace(ezdit_handle* h) {
 template <typename Launch>
 int hook_launch(const char* kernel, const char* config, Launch launch) {
     (void)hipGetLastError();
-    if (launch()) return fail(EZDIT_E_UNSUPPORTED, "%s not supported", config);
+    g_refusal.clear();
+    if (launch()) return fail(EZDIT_E_UNSUPPORTED, "%s not supported%s", config, take_refusal().c_str());
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(EZDIT_E_HIP, "launch of %s failed: %s", kernel, hipGetErrorString(e));
     return EZDIT_OK;

@@ -48,11 +48,14 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 // test-hook stamp [6]: the 100 MHz device-wide clock at kernel start, tagged in its top 16 bits with the CU the workgroup runs on
 // (XCC_ID[3:0] << 8 | HW_ID[15:8] = SE / SH / CU): tools/microbench/gemm_bench.cpp rebuilds every CU's timeline from it (who shared a CU with whom, idle gaps between workgroups)
-__device__ __forceinline__ unsigned long long ez_stamp_start() {
+// (the step kernels read the clock at kernel start and tag + store it where they store stamp [1]: their stamp buffer's address arrives behind the first staging request,
+// and a store between that request and the loads behind it makes hipcc drain vmcnt there -- fused k_attn: + 1.3 us per launch)
+__device__ __forceinline__ unsigned long long ez_stamp_tag(unsigned long long realtime) {
     const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
     const unsigned long long id = ((unsigned long long)(xcc & 15u) << 8) | ((hw >> 8) & 255u);
-    return (__builtin_amdgcn_s_memrealtime() & 0xffffffffffffull) | (id << 48);
+    return (realtime & 0xffffffffffffull) | (id << 48);
 }
+__device__ __forceinline__ unsigned long long ez_stamp_start() { return ez_stamp_tag(__builtin_amdgcn_s_memrealtime()); }
 
 // Division of a small non-negative integer by a launch constant WITHOUT the ~35-instruction integer division (v_rcp_iflag + readfirstlane + two correction
 // steps, on the scalar unit of a prologue that has nothing else to do: the workgroup -> tile maps of the GEMM and attention kernels ran 4 - 8 of them in a
@@ -60,14 +63,16 @@ __device__ __forceinline__ unsigned long long ez_stamp_start() {
 inline unsigned ez_magic(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
 __device__ __forceinline__ int ez_div(int x, unsigned m) { return m ? (int)__umulhi((unsigned)x, m) : x; }
 
-// Kernel-argument batch of a GEMM prologue (k_gemm_pp, k_gemm_co, k_gemm_ks):  int lda = a.lda;  asm("" : "+s"(lda) : "s"(a.A), "s"(a.W), ...);  makes hipcc
+// Kernel-argument batch of a prologue (k_attn, k_gemm):  int lda = a.lda;  asm("" : "+s"(lda) : "s"(a.A), "s"(a.W), ...);  makes hipcc
 // request every listed argument BEFORE the first use of `lda` (a non-volatile asm that "modifies" it and reads the others).  Left alone, hipcc sinks each scalar load towards its first use and the prologue
-// walks a chain of serialised kernarg round trips in front of its first LDS-DMA.  NOT `asm volatile`: hipcc treats that as a possible store, and the device
+// walks a chain of serialised kernarg round trips in front of its first LDS-DMA.  (k_gemm_ks, k_gemm_pp and k_gemm_co get what their prologues read in SGPRs at wave launch -- their leading
+// parameters, preloaded -- and request the rest of the struct in one such batch BEHIND their first tile: gemm_ks.h, gemm_pp.h z_late_load.)  NOT `asm volatile`: hipcc treats that as a possible store, and the device
 // step counter's load behind it (GemmArgs.cur_step: global memory) turned from a scalar load into a VECTOR load with `s_waitcnt vmcnt(0)` right behind it
 // (ISA of the first round-6 build); an inline-asm s_load for the counter is no way out either -- the allocator copied its destination before the tied wait
 // (`s_mov_b32 s20, s53`: tests/test_host.py::test_step_counter_scalar_load_is_not_touched_before_its_wait was written for it and caught it).
 
 int ez_fail(int code, const char* fmt, ...);   // api.hip: record the message behind ezdit_last_error(), return code
+int ez_refuse(const char* fmt, ...);           // api.hip: a launcher says WHY it refuses a configuration (returns 1); the caller's "... not supported" message carries the reason
 
 // ------------------------------------------------------------------------------------------
 // host-side launchers (one per kernel family); all asynchronous on `st`

@@ -380,6 +380,26 @@ int pick_boxes(GemmArgs& a, int BM, int BN) {
     return 8 * a.bm * a.bn * a.bz;
 }
 
+// The leading (preloaded) parameters of k_gemm_pp / k_gemm_co that do not simply repeat the struct's values (gemm_pp.h tile_of_block_lead, tile_of_block_lead_partial): the packed boxes,
+// and for a split-K launch the split count in the top byte of K and two magic numbers in the slot of the step counter's address.  false = the launch does not fit the packing: refused
+struct PpLead { const int* step; int K; int box; };
+bool pp_lead(const GemmArgs& a, bool partial, long grid, PpLead& ld) {
+    if (!partial) {
+        if (a.splitk != 1 || a.pz != 1) return ez_refuse("split-K %d (K boxes %d) with an epilogue that writes no slabs", a.splitk, a.pz) == 0;
+        if (a.bm > PP_BOX_BM_MAX || a.bn > PP_BOX_BN_MAX) return ez_refuse("XCD boxes of %d x %d tiles do not fit the packed leading parameter (<= %d x %d)", a.bm, a.bn, PP_BOX_BM_MAX, PP_BOX_BN_MAX) == 0;
+        ld.step = a.cur_step; ld.K = a.K; ld.box = pp_pack_box(a.pm, a.pn, a.bm, a.bn);
+        return true;
+    }
+    if (a.bm > PP_PBOX_BM_MAX || a.bn > PP_PBOX_BN_MAX || a.bz > PP_PBOX_BZ_MAX || a.splitk < 1 || a.splitk > PP_PBOX_S_MAX || a.K > PP_PBOX_K_MAX || a.pm * a.pn * a.pz != 8 ||
+        grid / 8 >= (1 << 20))
+        return ez_refuse("split-K launch beyond the packed leading parameters: boxes %d x %d x %d tiles (<= %d x %d x %d), %d splits (<= %d), K = %d (<= %d), %ld workgroups (< 2^23)",
+                         a.bm, a.bn, a.bz, PP_PBOX_BM_MAX, PP_PBOX_BN_MAX, PP_PBOX_BZ_MAX, a.splitk, PP_PBOX_S_MAX, a.K, PP_PBOX_K_MAX, grid) == 0;
+    ld.step = reinterpret_cast<const int*>(static_cast<uintptr_t>((unsigned long long)a.mbn | ((unsigned long long)a.msplit << 32)));
+    ld.K = a.K | (a.splitk << 24);
+    ld.box = pp_pack_box_partial(a.pm, a.pn, a.bm, a.bn, a.bz, a.xcd_panel);
+    return true;
+}
+
 // ping-pong kernel (gemm_pp.h): 8 waves, two groups one barrier interval apart
 template <int BM, int BN, int WM, int WN, int NS, int EPI, int SCHED, int VAR = 0>
 int launch_pp(const GemmArgs& a0, hipStream_t st) {
@@ -399,7 +419,9 @@ int launch_pp(const GemmArgs& a0, hipStream_t st) {
         attr_set[dev].store(true, std::memory_order_release);
     }
     if (a.ts && (long)grid.x > a.ts_cap) a.ts = nullptr;   // the stamp buffer has no room for this grid
-    hipLaunchKernelGGL((k_gemm_pp<BM, BN, WM, WN, NS, EPI, SCHED, VAR>), grid, dim3(512), SMEM, st, a);
+    PpLead ld;
+    if (!pp_lead(a, EPI == EPI_PARTIAL, (long)grid.x, ld)) return 1;
+    hipLaunchKernelGGL((k_gemm_pp<BM, BN, WM, WN, NS, EPI, SCHED, VAR>), grid, dim3(512), SMEM, st, a.A, a.W, ld.step, a.lda, a.ldw, a.wrows, a.M, a.N, ld.K, ld.box, a.mbm, a);
     return 0;
 }
 
@@ -419,7 +441,9 @@ int launch_co(const GemmArgs& a0, hipStream_t st) {
         attr_set[dev].store(true, std::memory_order_release);
     }
     if (a.ts && (long)grid.x > a.ts_cap) a.ts = nullptr;   // the stamp buffer has no room for this grid
-    hipLaunchKernelGGL((k_gemm_co<BM, BN, EPI, VAR>), grid, dim3(256), SMEM, st, a);
+    PpLead ld;
+    if (!pp_lead(a, EPI == EPI_PARTIAL, (long)grid.x, ld)) return 1;
+    hipLaunchKernelGGL((k_gemm_co<BM, BN, EPI, VAR>), grid, dim3(256), SMEM, st, a.A, a.W, ld.step, a.lda, a.ldw, a.wrows, a.M, a.N, ld.K, ld.box, a.mbm, a);
     return 0;
 }
 
@@ -445,7 +469,9 @@ int launch_ks(const GemmArgs& a0, hipStream_t st) {
         attr_set[dev].store(true, std::memory_order_release);
     }
     if (a.ts && (long)grid.x > a.ts_cap) a.ts = nullptr;   // the stamp buffer has no room for this grid
-    hipLaunchKernelGGL((k_gemm_ks<FM, FN, EPI, GATE, RES, CK, X>), grid, dim3(512), SMEM, st, a);
+    if (a.pm > 255 || a.bn >= (1 << 23)) return ez_refuse("k_gemm_ks: XCD boxes pm = %d, bn = %d do not fit the packed leading parameter", a.pm, a.bn);   // (pm <= 8 by construction)
+    // the leading (preloaded) parameters repeat the struct's values: gemm_ks.h
+    hipLaunchKernelGGL((k_gemm_ks<FM, FN, EPI, GATE, RES, CK, X>), grid, dim3(512), SMEM, st, a.A, a.W, a.cur_step, a.lda, a.ldw, a.wrows, a.M, a.N, a.K, a.pm | (a.bn << 8), a);
     return 0;
 }
 // tile ids of the K-split kernel: 70 = 48 x 96 (21 x 12 = 252 workgroups at M = 1000, N = 1152), 72 = 32 x 96, 73 = 48 x 64 (the final Linear, N = 128), one 64-wide K chunk

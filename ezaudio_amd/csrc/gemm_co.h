@@ -28,7 +28,8 @@ constexpr int co_smem_bytes() {
 
 // VAR & 64: LayerNorm algebra in the epilogue (consumer side, GemmArgs.z*), as in k_gemm_pp
 template <int BM, int BN, int EPI, int VAR>
-__global__ __launch_bounds__(256, 2) void k_gemm_co(GemmArgs a) {
+__global__ __launch_bounds__(256, 2) void k_gemm_co(const bf16_t* kA, const bf16_t* kW, const int* kstep, int klda, int kldw, int kwrows, int kM, int kN, int kK, int kbox, unsigned kmbm,
+                                                    GemmArgs a) {   // (the leading parameters are preloaded into SGPRs: see k_gemm_pp)
     constexpr int NT = 256;
     constexpr int WM = 4, TM = BM / WM, TN = BN, FM = TM / 16, FN = TN / 16;
     static_assert(TM * WM == BM && TM % 16 == 0 && TN % 16 == 0, "tile geometry: four waves, each TM rows x the whole tile width");
@@ -40,28 +41,23 @@ __global__ __launch_bounds__(256, 2) void k_gemm_co(GemmArgs a) {
     static_assert(NP < 32, "vmcnt range");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
-    // (kernel arguments of the prologue in one batch, then the step counter as a plain scalar load: see k_gemm_pp)
-    int M_ = a.M;
-    asm("" : "+s"(M_) : "s"(a.A), "s"(a.W), "s"(a.lda), "s"(a.ldw), "s"(a.wrows), "s"(a.N), "s"(a.K), "s"(a.splitk), "s"(a.pm), "s"(a.pn), "s"(a.bm), "s"(a.bn), "s"(a.bz),
-        "s"(a.cur_step), "s"(a.ts), "s"(a.row_slot), "s"(a.mbm), "s"(a.mbn), "s"(a.msplit));
-    const int slot0 = a.cur_step ? *a.cur_step : 0;
-    // G' / C' table bases PINNED in SGPRs: the per-thread choice between them (z_late_load) must be a select on two scalars -- left to hipcc it became a vector load of the chosen
-    // pointer from the argument segment, and its `s_waitcnt vmcnt(0)` drained the first K tile's LDS-DMA in front of the G' / C' request (ISA of the first blind-load build of k_gemm_co)
-    const float *zG_ = a.zG, *zC_ = a.zC;
-    asm("" : "+s"(M_), "+s"(zG_), "+s"(zC_));
+    // (the step counter through the preloaded pointer, first thing, as a plain scalar load; down to the request of K tile 0 only the leading parameters are read: see k_gemm_pp)
+    int slot0 = 0;
+    if constexpr (EPI != EPI_PARTIAL) slot0 = kstep ? *kstep : 0;
+    const unsigned long long t_start = __builtin_readcyclecounter(), t_real = __builtin_amdgcn_s_memrealtime();   // test hook: stamps [0], [6] (kernel start), stored with stamp [1]; unconditional: see k_gemm_pp
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave;
 
-    const int tilesM = (M_ + BM - 1) / BM;
-    const int tilesN = (a.N + BN - 1) / BN;
-    int tm, tn, z;
-    if (!tile_of_block(a, tilesM, tilesN, tm, tn, z)) return;
+    const int tilesM = (kM + BM - 1) / BM;
+    const int tilesN = (kN + BN - 1) / BN;
+    const int nk = (EPI == EPI_PARTIAL ? kK & PP_PBOX_K_MAX : kK) / BK;
+    int tm, tn, z = 0, kb = 0, ke = nk;
+    if constexpr (EPI == EPI_PARTIAL) {   // split-K: gemm_pp.h tile_of_block_lead_partial
+        if (!tile_of_block_lead_partial(kbox, kmbm, (unsigned long long)reinterpret_cast<uintptr_t>(kstep), kK, tilesM, tilesN, tm, tn, z, kb, ke)) return;
+    } else if (!tile_of_block_lead(kbox, kmbm, tilesM, tilesN, tm, tn)) return;
     const int row0 = tm * BM, col0 = tn * BN;
-    const int nk = a.K / BK;
-    int kb, ke;
-    ksplit_range(a, nk, z, kb, ke);
     const int nt = ke - kb;
 
     constexpr bool ZM = (VAR & 64) != 0 && (EPI == EPI_GEGLU || EPI == EPI_QKV);
@@ -71,10 +67,23 @@ __global__ __launch_bounds__(256, 2) void k_gemm_co(GemmArgs a) {
     // the loop (gemm_pp.h z_lane_load / z_lane_finish): nothing of the algebra sits between the prologue and the loop's first barrier
     constexpr int NZT = ZM ? FM * Z_PT : 0;   // blind statistics loads per lane (into AGPRs), issued by z_late_load
     ZLaneRegs<FM> zlr;
-    const bool z_shared_slot = a.row_slot == nullptr;
+    bool z_shared_slot = true;   // (a.row_slot == nullptr: read from the struct where z_late_load begins, behind K tile 0; zx with it)
     constexpr int ZNV = 2 * (BN / 4);   // threads that fetch one float4 of G' | C' by LDS-DMA straight into zgc[tid] (gemm_pp.h wait_younger_x)
-    const bool zx = ZM && z_shared_slot && wave * 64 < ZNV;   // this wave issued that DMA: the counted wait in front of the loop leaves it (and the NZT statistics loads) in flight
+    bool zx = false;              // this wave issued that DMA: the counted wait in front of the loop leaves it (and the NZT statistics loads) in flight
+    unsigned long long* ts = nullptr;
     auto z_late_load = [&]() {
+        // the rest of the kernel arguments, from the struct in ONE batch (common.h "Kernel-argument batch") behind the requests of K tile 0.  G' / C' table bases PINNED in SGPRs
+        // (`late` is 0, unknown to hipcc: see k_gemm_pp): the per-thread choice between them must be a select on two scalars -- left to hipcc it became a vector load of the chosen pointer
+        // from the argument segment, and its `s_waitcnt vmcnt(0)` drained the first K tile's LDS-DMA in front of the G' / C' request (ISA of the first blind-load build of k_gemm_co)
+        long late = 0;
+        asm("; late arguments" : "+s"(late) : "s"(a.ts), "s"(a.row_slot), "s"(a.zstat_in), "s"(a.zs_stride), "s"(a.zparts), "s"(a.zt_slot_stride), "s"(a.zG), "s"(a.zC));
+        const float *zG_ = a.zG + late, *zC_ = a.zC + late;
+        {
+            unsigned long long* ts_ = a.ts ? a.ts + late : nullptr;
+            ts = (ts_ && wave == 0) ? ts_ + 8 * (long)blockIdx.x : nullptr;
+            z_shared_slot = a.row_slot == nullptr;
+            zx = ZM && z_shared_slot && wave * 64 < ZNV;
+        }
         if constexpr (ZM) {
             static_assert(2 * (BN / 4) <= NT, "one float4 of G' or C' per thread");
             if (z_shared_slot && tid < ZNV) {
@@ -87,8 +96,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm_co(GemmArgs a) {
             z_lane_load<FM>(a.zstat_in, a.zs_stride, a.zparts, row0 + wm * TM + (lane & 15), a.M - 1, lane >> 4, zlr);   // blind loads into AGPRs, every lane
         }
     };
-    unsigned long long* ts = (a.ts && wave == 0) ? a.ts + 8 * (long)blockIdx.x : nullptr;
-    if (ts && lane == 0) { ts[0] = __builtin_readcyclecounter(); ts[6] = ez_stamp_start(); }
     f32x4 acc[FM][FN];
 #pragma unroll
     for (int i = 0; i < FM; ++i)
@@ -103,17 +110,17 @@ __global__ __launch_bounds__(256, 2) void k_gemm_co(GemmArgs a) {
         const int row = q >> 3, c = q & 7;
         if (p < PA) {
             int grow = row0 + row;
-            grow = grow < a.M ? grow : a.M - 1;
-            poff[p] = (uint32_t)(grow * a.lda + ((c ^ ((row >> 1) & 7)) << 3)) * 2u;
+            grow = grow < kM ? grow : kM - 1;
+            poff[p] = (uint32_t)(grow * klda + ((c ^ ((row >> 1) & 7)) << 3)) * 2u;
         } else {
             const int r2 = row - BM;
             int gr = col0 + r2;
-            gr = gr < a.wrows ? gr : a.wrows - 1;   // (the ragged last piece re-fetches a clamped row into the stage's padding: every wave issues NP loads per tile)
-            poff[p] = (uint32_t)(gr * a.ldw + ((c ^ ((r2 >> 1) & 7)) << 3)) * 2u;
+            gr = gr < kwrows ? gr : kwrows - 1;   // (the ragged last piece re-fetches a clamped row into the stage's padding: every wave issues NP loads per tile)
+            poff[p] = (uint32_t)(gr * kldw + ((c ^ ((r2 >> 1) & 7)) << 3)) * 2u;
         }
     }
-    const char* gA = reinterpret_cast<const char*>(a.A) + (long)kb * (BK * 2);
-    const char* gW = reinterpret_cast<const char*>(a.W) + (long)kb * (BK * 2);
+    const char* gA = reinterpret_cast<const char*>(kA) + (long)kb * (BK * 2);
+    const char* gW = reinterpret_cast<const char*>(kW) + (long)kb * (BK * 2);
     auto issue = [&](int t) {
         char* dst = smem + (t & 1) * STAGE + wave * 1024;
         const long koff = (long)t * (BK * 2);
@@ -152,7 +159,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_co(GemmArgs a) {
     if (nt > 1) issue(1);
     if (nt > 1) { if (zx) wait_vmcnt<NP + NZT + 1>(); else wait_vmcnt<NP + NZT>(); } else wait_vmcnt<0>();   // (the statistics loads and, zx, the G' | C' DMA -- issued between tile 0 and tile 1 -- stay in flight)
     barrier();
-    if (ts && lane == 0) ts[1] = __builtin_readcyclecounter();
+    if (ts && lane == 0) { const unsigned long long t1 = __builtin_readcyclecounter(); ts[0] = t_start; ts[6] = ez_stamp_tag(t_real); ts[1] = t1; }
     // one K tile.  MODE 2: steady state (tile t + 2 exists and is issued here); 1: the last but one tile; 0: the last tile.  Compile-time, so that the
     // steady-state loop is straight-line code: with the `t + 2 < nt` tests inside ONE loop hipcc shuffled all 72 accumulators through VGPRs and spare
     // AGPRs on every trip (phi copies of the inline-asm MFMA operands across the branches: 140 v_accvgpr moves per K tile in the first build)

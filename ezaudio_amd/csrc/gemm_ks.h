@@ -78,15 +78,15 @@ __device__ __forceinline__ int ks_slot_of(int q, int j) {
 // linearised M-major and dealt in a.pm equal contiguous runs to the a.pm XCDs of the group (XCD = blockIdx % 8): every XCD sees a.bn weight
 // panels and 1 / a.pm of the rows like the box map (tile_of_block), but no XCD gets more than ceil(tiles of a group / a.pm) workgroups --
 // 21 x 12 tiles on 2 x 4 boxes are 33 / 30 tiles per XCD, i.e. a SECOND ROUND on the 32 CUs of four XCDs; the runs are 32 / 31
-__device__ __forceinline__ bool ks_tile_of_block(const GemmArgs& a, int tilesM, int tilesN, int& tm, int& tn) {
+__device__ __forceinline__ bool ks_tile_of_block(int pm, int bn, int tilesM, int tilesN, int& tm, int& tn) {
     const int xcd = blockIdx.x & 7, l = blockIdx.x >> 3;
-    const int lpm = __builtin_ctz(a.pm);           // a.pm is 1, 2, 4 or 8 (pick_boxes)
-    const int xm = xcd & (a.pm - 1), gn = xcd >> lpm;
-    const int n0 = gn * a.bn;
+    const int lpm = __builtin_ctz(pm);             // pm is 1, 2, 4 or 8 (pick_boxes)
+    const int xm = xcd & (pm - 1), gn = xcd >> lpm;
+    const int n0 = gn * bn;
     int gw = tilesN - n0;                          // N tiles of this group
-    gw = gw < a.bn ? gw : a.bn;
+    gw = gw < bn ? gw : bn;
     if (gw <= 0) return false;
-    const int T = tilesM * gw, run = (T + a.pm - 1) >> lpm;
+    const int T = tilesM * gw, run = (T + pm - 1) >> lpm;
     const int t = xm * run + l;
     if (l >= run || t >= T) return false;
     tm = (int)(((float)t + 0.5f) * __builtin_amdgcn_rcpf((float)gw));   // t / gw for the small integers of a tile grid, without the 40-instruction integer division
@@ -101,8 +101,13 @@ __device__ __forceinline__ bool ks_tile_of_block(const GemmArgs& a, int tilesM, 
 // KS_COPY2 / KS_ZIN (round 6): the out-blocks' LN_2D([x | skip]) -> skip_linear (blocks.py:124-128) by the LayerNorm algebra.  The statistics of the concatenation are the sums of
 // the halves' statistics: the in-block that produced `skip` stored them (and bf16(skip * g[D:]) into the right half of the out-block's operand, COPY2), the MLP-out projection in front
 // of the out-block stores bf16(x * g[:D]) + its statistics, and skip_linear (ZIN) finishes the LayerNorm in its epilogue: no split-K slabs, no row kernel
+// Leading parameters (13 dwords: the translation unit is built with -amdgpu-kernarg-preload-count, ezaudio_amd/build.py): gfx950 hands them to every wave in user SGPRs at launch,
+// so nothing between wave start and the first LDS-DMA waits for a (cold: read once per step) kernel-argument load.  They are what that stretch reads -- the operands, their
+// strides and clamps, the tile grid and its XCD boxes (kbox = pm | bn << 8) -- plus the step counter's address; the launcher passes the same values as in `a`, whose layout is
+// untouched (r06ah) and whose other fields are requested behind the first chunk.  A by-value struct is never preloaded.
 template <int FM, int FN, int EPI, bool GATE, bool RES, int CK, int X = KS_PLAIN>
-__global__ __launch_bounds__(512) void k_gemm_ks(GemmArgs a) {
+__global__ __launch_bounds__(512) void k_gemm_ks(const bf16_t* kA, const bf16_t* kW, const int* kstep, int klda, int kldw, int kwrows, int kM, int kN, int kK,
+                                                 int kbox, GemmArgs a) {
     constexpr bool DUAL = X == KS_DUAL;
     static_assert(EPI == EPI_F32 || EPI == EPI_RESID, "epilogues");
     static_assert(!DUAL || (EPI == EPI_RESID && GATE && RES), "DUAL: the gated residual projection only");
@@ -130,37 +135,35 @@ __global__ __launch_bounds__(512) void k_gemm_ks(GemmArgs a) {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    // the kernel arguments the prologue needs in ONE batch (common.h "Kernel-argument batch"), then the device step counter (selects the modulation slot of
-    // gate / gain) as a plain scalar load: used right in front of the operand requests, behind the first chunk's LDS-DMA.  (Round 5 issued it by inline asm
-    // under `if (a.cur_step)`: ADVICE r05 -- a phi with 0 may become a copy of a register that has not been written yet.)
-    int M_ = a.M;
-    asm("" : "+s"(M_) : "s"(a.A), "s"(a.W), "s"(a.lda), "s"(a.ldw), "s"(a.wrows), "s"(a.N), "s"(a.K), "s"(a.pm), "s"(a.bn), "s"(a.cur_step), "s"(a.ts), "s"(a.ts_cap),
-        "s"(a.row_slot), "s"(a.bias), "s"(a.resid), "s"(a.ldr), "s"(a.gate), "s"(a.zg));
+    // the device step counter (selects the modulation slot of gate / gain) through the PRELOADED pointer, first thing: a plain scalar load, used right in front of the
+    // operand requests, behind the first chunk's LDS-DMA.  (Round 5 issued it by inline asm under `if (a.cur_step)`: ADVICE r05 -- a phi with 0 may become a copy of a
+    // register that has not been written yet.)  Down to the first chunk's requests only the leading parameters are read: no wait for a kernel-argument load in front of them
     int slot0 = 0;
-    if constexpr (EPI == EPI_RESID) slot0 = a.cur_step ? *a.cur_step : 0;
-    const int tilesM = (M_ + BM - 1) / BM;
-    const int tilesN = (a.N + BN - 1) / BN;
+    if constexpr (EPI == EPI_RESID) slot0 = kstep ? *kstep : 0;
+    // test hook: stamps [0] and [6] (shader clock and 100 MHz clock at kernel start); the stamp buffer's address is in the struct: the values are stored with stamp [1]
+    // (UNCONDITIONAL, two scalar instructions per wave whose results nothing waits for before the first tile is out: under `if (ts)` they would need the struct, i.e. sit behind the
+    // first tile, and stamp [0] would no longer be the kernel's start.  They are inside every step time DESIGN.md quotes for this form.)
+    const unsigned long long t_start = __builtin_readcyclecounter(), t_real = __builtin_amdgcn_s_memrealtime();
+    const int tilesM = (kM + BM - 1) / BM;
+    const int tilesN = (kN + BN - 1) / BN;
     int tm, tn;
-    if (!ks_tile_of_block(a, tilesM, tilesN, tm, tn)) return;
+    if (!ks_tile_of_block(kbox & 255, kbox >> 8, tilesM, tilesN, tm, tn)) return;
     const int row0 = tm * BM, col0 = tn * BN;
-    const int nk = a.K / CK;
-    unsigned long long* ts = (a.ts && wave == 0) ? a.ts + 8 * (long)blockIdx.x : nullptr;
-    unsigned long long t_start = 0, t_sum = 0;   // test hook: [5] packs two epilogue marks relative to [0]: low 32 bits = partial sums complete, high 32 = stores issued
-    if (ts && lane == 0) { t_start = __builtin_readcyclecounter(); ts[0] = t_start; ts[6] = ez_stamp_start(); }
+    const int nk = kK / CK;
 
     // epilogue thread layout: (row er, lane-in-row ej) of the first 8 BM threads
     const int er = tid >> 3, ej = tid & 7;
     const bool epi_thread = tid < 8 * BM;
     int erow = row0 + er;
-    const bool row_ok = epi_thread && erow < a.M;
-    erow = erow < a.M ? erow : a.M - 1;
-    const int ncl = a.N - 4;                       // N is a multiple of 4 for every caller
+    const bool row_ok = epi_thread && erow < kM;
+    erow = erow < kM ? erow : kM - 1;
+    const int ncl = kN - 4;                        // N is a multiple of 4 for every caller
 
     // ---- loop-invariant addressing: byte offset of this lane's 16 bytes of piece p (K offset excluded)
     // The pieces of this wave's FIRST chunk go out as soon as their offsets are known, not behind all NPC offset computations: the time to the
     // first byte is what the whole (latency-bound) kernel is shifted by
-    const char* gA = reinterpret_cast<const char*>(a.A);
-    const char* gW = reinterpret_cast<const char*>(a.W);
+    const char* gA = reinterpret_cast<const char*>(kA);
+    const char* gW = reinterpret_cast<const char*>(kW);
     char* slot = smem + wave * SLOT;               // wave-uniform
     const int nmine = wave < nk ? (nk - wave + 7) / 8 : 0;   // chunks of this wave: wave, wave + 8, ...; chunk number i lives in slot i % NSL
     uint32_t poff[NPC];
@@ -172,18 +175,23 @@ __global__ __launch_bounds__(512) void k_gemm_ks(GemmArgs a) {
         const int gc = CK == 64 ? (c ^ ((r2 >> 1) & 7)) : (c ^ ((r2 >> 2) & 3));
         if (p < PA) {
             int grow = row0 + row;
-            grow = grow < a.M ? grow : a.M - 1;
-            poff[p] = (uint32_t)(grow * a.lda + (gc << 3)) * 2u;
+            grow = grow < kM ? grow : kM - 1;
+            poff[p] = (uint32_t)(grow * klda + (gc << 3)) * 2u;
         } else {
             int gr = col0 + r2;
-            gr = gr < a.wrows ? gr : a.wrows - 1;
-            poff[p] = (uint32_t)(gr * a.ldw + (gc << 3)) * 2u;
+            gr = gr < kwrows ? gr : kwrows - 1;
+            poff[p] = (uint32_t)(gr * kldw + (gc << 3)) * 2u;
         }
         if (nmine > 0)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((p < PA ? gA : gW) + (long)wave * (CK * 2) + poff[p]),
                                              (__attribute__((address_space(3))) void*)(slot + p * 1024), 16, 0, 0);
     }
-    auto issue = [&](int c, char* dst) {           // chunk c (K columns [c CK, (c + 1) CK)) -> LDS at dst
+    // the rest of the kernel arguments, from the struct in ONE batch (common.h "Kernel-argument batch") BEHIND the first chunk's requests: their round trip runs under the chunk's
+    unsigned long long* ts_ = a.ts;
+    asm("" : "+s"(ts_) : "s"(a.ts_cap), "s"(a.row_slot), "s"(a.bias), "s"(a.resid), "s"(a.ldr), "s"(a.gate), "s"(a.zg));
+    unsigned long long* ts = (ts_ && wave == 0) ? ts_ + 8 * (long)blockIdx.x : nullptr;
+    unsigned long long t_sum = 0;   // test hook: [5] packs two epilogue marks relative to [0]: low 32 bits = partial sums complete, high 32 = stores issued
+    auto issue =[&](int c, char* dst) {           // chunk c (K columns [c CK, (c + 1) CK)) -> LDS at dst
         const long koff = (long)c * (CK * 2);
 #pragma unroll
         for (int p = 0; p < NPC; ++p) {
@@ -264,7 +272,7 @@ __global__ __launch_bounds__(512) void k_gemm_ks(GemmArgs a) {
         }
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (ts && lane == 0) ts[1] = __builtin_readcyclecounter();
+    if (ts && lane == 0) { const unsigned long long t1 = __builtin_readcyclecounter(); ts[0] = t_start; ts[6] = ez_stamp_tag(t_real); ts[1] = t1; }
     for (int i = 0; i < nmine; ++i) {
         // own LDS-DMA of chunk i landed (nothing else orders a ds_read behind it): wait until only the loads issued AFTER it are outstanding
         // -- the operand loads (behind the NSL prologue chunks) and, with two slots, the next chunk.  No other wave touches this slot: no barrier
@@ -380,7 +388,7 @@ __global__ __launch_bounds__(512) void k_gemm_ks(GemmArgs a) {
             const int col = col0 + 4 * ks_slot_of<SL>(q, ej);
             const f32x4 bb = a.bias ? op.b[q] : f32x4{0.f, 0.f, 0.f, 0.f};   // (a select: the dummy load of a null bias may hold NaN bit patterns)
             const float4 o = make_float4(v[q].x + bb[0], v[q].y + bb[1], v[q].z + bb[2], v[q].w + bb[3]);
-            if (row_ok && col < a.N) {
+            if (row_ok && col < kN) {
                 float* dst = out + (long)erow * a.ldo + col;
                 if (a.wt) st16_wt(dst, o); else *reinterpret_cast<float4*>(dst) = o;
             }
@@ -401,7 +409,7 @@ __global__ __launch_bounds__(512) void k_gemm_ks(GemmArgs a) {
 #pragma unroll
         for (int q = 0; q < SL; ++q) {
             const int col = col0 + 4 * ks_slot_of<SL>(q, ej);
-            const bool ok = col < a.N;
+            const bool ok = col < kN;
             if constexpr (X == KS_ZIN) {   // finish the LayerNorm of the operand: r (acc - mu G') (+ C' = the `bias` operand, below)
                 v[q].x = zr * fmaf(-zmu, op.g[q][0], v[q].x); v[q].y = zr * fmaf(-zmu, op.g[q][1], v[q].y);
                 v[q].z = zr * fmaf(-zmu, op.g[q][2], v[q].z); v[q].w = zr * fmaf(-zmu, op.g[q][3], v[q].w);
@@ -436,9 +444,9 @@ __global__ __launch_bounds__(512) void k_gemm_ks(GemmArgs a) {
         }
         bf16_t* zrow = a.zu + (long)erow * a.ld_zu;
         auto store8 = [&](int col, uint2 lo, uint2 hi, bf16_t* rowp) {   // columns [col, col + 8) of this row
-            if (!row_ok || col >= a.N) return;
+            if (!row_ok || col >= kN) return;
             bf16_t* dst = rowp + col;
-            if (col + 8 <= a.N) {
+            if (col + 8 <= kN) {
                 const float4 f = make_float4(__uint_as_float(lo.x), __uint_as_float(lo.y), __uint_as_float(hi.x), __uint_as_float(hi.y));
                 if (a.wt) st16_wt(dst, f); else *reinterpret_cast<float4*>(dst) = f;
             } else {   // ragged tail: N is a multiple of 4

@@ -119,6 +119,55 @@ __device__ __forceinline__ bool tile_of_block(const GemmArgs& a, int tilesM, int
     z = xz * a.bz + lz;
     return tm < tilesM && tn < tilesN && z < a.splitk;
 }
+// The same map from the LEADING kernel parameters of k_gemm_pp / k_gemm_co (preloaded into SGPRs: see k_gemm_pp), for the launches without split-K and without panel placement
+// (every epilogue but EPI_PARTIAL): box = lpm | lpn << 2 | bm << 4 | bn << 20 (pm = 1 << lpm, pn = 1 << lpn: pm pn = 8, one K box), mbm = ez_magic(bm).  z is 0, so of the
+// second division (l / bm) / bn only "the quotient is 0" is left: the same tm, tn and the same verdict as tile_of_block
+constexpr int PP_BOX_BM_MAX = 0xffff, PP_BOX_BN_MAX = 0x7ff;
+inline int pp_pack_box(int pm, int pn, int bm, int bn) { return __builtin_ctz(pm) | (__builtin_ctz(pn) << 2) | (bm << 4) | (bn << 20); }
+__device__ __forceinline__ bool tile_of_block_lead(int box, unsigned mbm, int tilesM, int tilesN, int& tm, int& tn) {
+    const int xcd = blockIdx.x & 7;
+    const int l = blockIdx.x >> 3;
+    const int lpm = box & 3, lpn = (box >> 2) & 3, bm = (box >> 4) & PP_BOX_BM_MAX, bn = (box >> 20) & PP_BOX_BN_MAX;
+    const int xm = xcd & ((1 << lpm) - 1), xn = (xcd >> lpm) & ((1 << lpn) - 1);
+    const int t1 = ez_div(l, mbm), lm = l - t1 * bm;
+    tm = xm * bm + lm;
+    tn = xn * bn + t1;
+    return tm < tilesM && tn < tilesN && t1 < bn;
+}
+// ... and for a split-K launch (EPI_PARTIAL), which needs the K boxes, the split count and three magic numbers: the boxes pack tighter (box = lpm | lpn << 2 | bm << 4 | bn << 16 |
+// bz << 24 | panel << 31; pz = 8 / (pm pn)), the split count rides in the top byte of the K parameter, ez_magic(bn) | ez_magic(splitk) << 32 in the slot of the step counter's address
+// (slabs take no modulation slot), and the panel form divides by N tiles x splits with the reciprocal of k_gemm_ks's map (exact while the dividend is below 2^20: the relative
+// error of v_rcp_f32 and the product, 1.8e-7, times the dividend stays under the 0.5 that (x + 0.5) / d keeps from the next integer).  Same tm, tn, z, kb, ke as tile_of_block /
+// panel_of_block / ksplit_range
+constexpr int PP_PBOX_BM_MAX = 0xfff, PP_PBOX_BN_MAX = 0xff, PP_PBOX_BZ_MAX = 0x7f, PP_PBOX_S_MAX = 0x7f, PP_PBOX_K_MAX = 0xffffff;
+inline int pp_pack_box_partial(int pm, int pn, int bm, int bn, int bz, int panel) {
+    return (int)((unsigned)__builtin_ctz(pm) | ((unsigned)__builtin_ctz(pn) << 2) | ((unsigned)bm << 4) | ((unsigned)bn << 16) | ((unsigned)bz << 24) | ((unsigned)(panel != 0) << 31));
+}
+__device__ __forceinline__ bool tile_of_block_lead_partial(int box_, unsigned mbm, unsigned long long m2, int kpacked, int tilesM, int tilesN, int& tm, int& tn, int& z, int& kb, int& ke) {
+    const unsigned box = (unsigned)box_, mbn = (unsigned)m2, msplit = (unsigned)(m2 >> 32);
+    const int S = (kpacked >> 24) & PP_PBOX_S_MAX, nk = (kpacked & PP_PBOX_K_MAX) / BK;
+    const int xcd = blockIdx.x & 7, l = blockIdx.x >> 3;
+    if (box >> 31) {   // panel placement: M tile tm -> XCD tm % 8
+        const int G = tilesN * S;
+        const int lg = (int)(((float)l + 0.5f) * __builtin_amdgcn_rcpf((float)G)), r = l - lg * G;
+        tm = xcd + 8 * lg;
+        tn = ez_div(r, msplit);
+        z = r - tn * S;
+        if (tm >= tilesM) return false;
+    } else {
+        const int lpm = box & 3, lpn = (box >> 2) & 3, bm = (box >> 4) & PP_PBOX_BM_MAX, bn = (box >> 16) & PP_PBOX_BN_MAX, bz = (box >> 24) & PP_PBOX_BZ_MAX;
+        const int xm = xcd & ((1 << lpm) - 1), xn = (xcd >> lpm) & ((1 << lpn) - 1), xz = xcd >> (lpm + lpn);
+        const int t1 = ez_div(l, mbm), lm = l - t1 * bm;
+        const int lz = ez_div(t1, mbn), ln = t1 - lz * bn;
+        tm = xm * bm + lm;
+        tn = xn * bn + ln;
+        z = xz * bz + lz;
+        if (!(tm < tilesM && tn < tilesN && z < S)) return false;
+    }
+    if (S == 1) { kb = 0; ke = nk; }
+    else { kb = ez_div(nk * z, msplit); ke = ez_div(nk * (z + 1), msplit); }
+    return true;
+}
 // panel placement of a split-K GEMM: ALL workgroups of an M tile (N tiles x K splits) are dealt to ONE XCD (M tile tm -> XCD tm % 8)
 __device__ __forceinline__ void panel_of_block(const GemmArgs& a, int tilesN, int& tm, int& tn, int& z) {
     const int G = tilesN * a.splitk, l = blockIdx.x >> 3;
@@ -868,8 +917,14 @@ constexpr int pp_smem_bytes() {
     return NS * ((BM + BN + 31) / 32) * 4096 + BM * 8 + (EPI == EPI_RESID ? 4 : 2) * BN * 4 + (EPI == EPI_QKV ? 8 * 256 + 1024 : 0);   // EPI_QKV: + the RoPE warm-up sink + the LayerNorm-affine table (qkv_aff_*)
 }
 
+// Leading parameters (14 dwords; the translation unit is built with -amdgpu-kernarg-preload-count, ezaudio_amd/build.py): gfx950 hands them to every wave in user SGPRs at launch, so
+// nothing between wave start and the request of K tile 0 waits for a (cold: read once per step) kernel-argument load.  They are what that stretch reads: the operands with their strides
+// and clamps, the tile grid, the XCD boxes packed with ONE magic number (kbox, kmbm: tile_of_block_lead) and the step counter's address.  The launcher passes the same values as
+// in `a`, whose layout is untouched (r06ah).  Left to the struct, requested behind K tile 0 (z_late_load): everything the epilogue and the loop's waits read.  A split-K launch
+// (EPI_PARTIAL) packs its K boxes, split count and further magic numbers into the same 14 dwords (tile_of_block_lead_partial).  A by-value struct is never preloaded.
 template <int BM, int BN, int WM, int WN, int NS, int EPI, int SCHED, int VAR>
-__global__ __launch_bounds__(512) void k_gemm_pp(GemmArgs a) {
+__global__ __launch_bounds__(512) void k_gemm_pp(const bf16_t* kA, const bf16_t* kW, const int* kstep, int klda, int kldw, int kwrows, int kM, int kN, int kK, int kbox, unsigned kmbm,
+                                                 GemmArgs a) {
     static_assert(SCHED == 1 || SCHED == 2, "schedule");
     static_assert(WM * WN == (SCHED == 1 ? 8 : 4), "SCHED 1: 8 waves tile the block; SCHED 2: each group of 4 tiles it");
     constexpr int NT = 512, NTG = 256;
@@ -885,21 +940,17 @@ __global__ __launch_bounds__(512) void k_gemm_pp(GemmArgs a) {
     constexpr int P0 = SCHED == 1 ? (NP + 1) / 2 : NP;   // group 0's pieces of a tile: [0, P0); group 1: [P0, NP) (SCHED 2: the issuing group takes all)
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
-    // the kernel arguments the prologue needs, requested in ONE batch in front of the tile map (common.h "Kernel-argument batch"), then the device step
-    // counter as a plain (scalar) load: nothing in front of the first LDS-DMA waits on the scalar-memory counter again, so its round trip runs under the
-    // tile map, the address arithmetic and the first K tile
-    int M_ = a.M;
-    asm("" : "+s"(M_) : "s"(a.A), "s"(a.W), "s"(a.lda), "s"(a.ldw), "s"(a.wrows), "s"(a.N), "s"(a.K), "s"(a.splitk), "s"(a.pm), "s"(a.pn), "s"(a.bm), "s"(a.bn), "s"(a.bz),
-        "s"(a.cur_step), "s"(a.ts), "s"(a.xcd_panel), "s"(a.row_slot), "s"(a.mbm), "s"(a.mbn), "s"(a.msplit), "s"(a.mG));
-    const int slot0 = a.cur_step ? *a.cur_step : 0;   // device step counter: needed from z_late_load on
+    // the device step counter through the PRELOADED pointer, first thing, as a plain (scalar) load: needed from z_late_load on, so its round trip runs under the tile map, the
+    // address arithmetic and the first K tile.  Down to the request of K tile 0 only the leading parameters are read
+    int slot0 = 0;
+    if constexpr (EPI != EPI_PARTIAL) slot0 = kstep ? *kstep : 0;   // (split-K slabs take no modulation slot: the parameter carries two magic numbers there)
+    // test hook: stamps [0] and [6] (shader clock and 100 MHz clock at kernel start); the stamp buffer's address is in the struct: the values are stored with stamp [1]
+    // (UNCONDITIONAL, two scalar instructions per wave whose results nothing waits for before the first tile is out: under `if (ts)` they would need the struct, i.e. sit behind the
+    // first tile, and stamp [0] would no longer be the kernel's start.  They are inside every step time DESIGN.md quotes for this form.)
+    const unsigned long long t_start = __builtin_readcyclecounter(), t_real = __builtin_amdgcn_s_memrealtime();
     // G' / C' table bases PINNED in SGPRs: the per-thread choice between them (z_late_load) must be a select on two scalars -- left to hipcc it became a vector load of the chosen
-    // pointer from the argument segment, and its `s_waitcnt vmcnt(0)` drained the first K tile's LDS-DMA in front of the G' / C' request (ISA of the first blind-load build of k_gemm_co)
-    const float *zG_ = a.zG, *zC_ = a.zC;
-    asm("" : "+s"(M_), "+s"(zG_), "+s"(zC_));
-    const float *rb_ = a.bias, *rg_ = a.gate, *rz_ = a.zg, *rz2_ = a.zg2;   // the same for the producer's per-column vectors (EPI_RESID)
-    if constexpr (EPI == EPI_RESID) asm("" : "+s"(M_), "+s"(rb_), "+s"(rg_), "+s"(rz_), "+s"(rz2_));
-    const float *rc_ = a.hn.rope_cos, *rs_ = a.hn.rope_sin;                 // ... and for the RoPE tables the fused-QKV warm-up chooses between per thread
-    if constexpr (EPI == EPI_QKV) asm("" : "+s"(M_), "+s"(rc_), "+s"(rs_));
+    // pointer from the argument segment, and its `s_waitcnt vmcnt(0)` drained the first K tile's LDS-DMA in front of the G' / C' request (ISA of the first blind-load build of k_gemm_co).
+    // The same for the producer's per-column vectors (EPI_RESID) and for the RoPE tables the fused-QKV warm-up chooses between per thread.  (Locals of z_late_load, their only user.)
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -908,18 +959,15 @@ __global__ __launch_bounds__(512) void k_gemm_pp(GemmArgs a) {
     const int wt = SCHED == 1 ? wave : wg;     // position among the waves that tile the block
     const int wm = wt / WN, wn = wt % WN;
 
-    const int tilesM = (M_ + BM - 1) / BM;
-    const int tilesN = (a.N + BN - 1) / BN;
-    int tm, tn, z;
-    if (EPI == EPI_PARTIAL && a.xcd_panel) {
-        // panel placement: the tile's slabs and the row kernel that reduces them (row panel p on XCD p % 8) stay inside one XCD's L2
-        panel_of_block(a, tilesN, tm, tn, z);
-        if (tm >= tilesM) return;
-    } else if (!tile_of_block(a, tilesM, tilesN, tm, tn, z)) return;
+    const int tilesM = (kM + BM - 1) / BM;
+    const int tilesN = (kN + BN - 1) / BN;
+    const int nk = (EPI == EPI_PARTIAL ? kK & PP_PBOX_K_MAX : kK) / BK;
+    int tm, tn, z = 0, kb = 0, ke = nk;
+    if constexpr (EPI == EPI_PARTIAL) {
+        // (panel placement: the tile's slabs and the row kernel that reduces them -- row panel p on XCD p % 8 -- stay inside one XCD's L2)
+        if (!tile_of_block_lead_partial(kbox, kmbm, (unsigned long long)reinterpret_cast<uintptr_t>(kstep), kK, tilesM, tilesN, tm, tn, z, kb, ke)) return;
+    } else if (!tile_of_block_lead(kbox, kmbm, tilesM, tilesN, tm, tn)) return;
     const int row0 = tm * BM, col0 = tn * BN;
-    const int nk = a.K / BK;
-    int kb, ke;
-    ksplit_range(a, nk, z, kb, ke);
     const int nt = ke - kb;
 
     // VAR & 64 ("ZM"): EPI_GEGLU / EPI_QKV finish a LayerNorm in their epilogue (GemmArgs.z*, consumer side)
@@ -933,15 +981,17 @@ __global__ __launch_bounds__(512) void k_gemm_pp(GemmArgs a) {
     constexpr int FMR = SCHED == 1 ? FM : FM / 2;                        // 16-row fragments a lane finishes in the epilogue (SCHED 2: after the k-split exchange)
     constexpr int NZT = ZMC ? FMR * Z_PT : 0;                            // blind statistics loads per lane (into AGPRs), issued by z_late_load
     ZLaneRegs<FMR> zlr;
-    const bool z_shared_slot = a.row_slot == nullptr;
+    bool z_shared_slot = true;   // (a.row_slot == nullptr; this, z_warm and zx read the struct: set where z_late_load begins, behind K tile 0)
     // threads that fetch one float4 of the epilogue's per-column vectors (LDS-DMA in z_late_load), and whether THIS wave is one of theirs: its counted wait in front of the
     // K loop then leaves that one DMA in flight (nt >= 2: the wait for K tile 1, which is younger, covers it)
     constexpr int ZNV = EPI == EPI_RESID ? ((VAR & (256 | 512)) ? 4 : 3) * (BN / 4) : 2 * (BN / 4);
     // zx = LDS-DMA instructions THIS wave issues in z_late_load on top of the NZT statistics loads every wave issues there (0 .. 2, wave-uniform): the per-column vectors'
     // (the first waves only) and, fused QKV, the RoPE-table warm-up (every wave of a q / k tile).  The counted wait in front of the K loop leaves all of them in flight;
     // they are older than every K tile but the first, so the wait for K tile 1 (nt >= 2) covers them
-    const bool z_warm = EPI == EPI_QKV && rc_ && col0 < 2 * a.hn.H * a.hn.dh;
-    const int zx = nt >= 2 ? ((((ZMC && z_shared_slot) || EPI == EPI_RESID) && wave * 64 < ZNV) ? 1 : 0) + (z_warm ? 1 : 0) : -1;   // (-1: a single K tile -- wait for everything)
+    bool z_warm = false;
+    int zslot = slot0;   // slot0 as z_late_load uses it
+    int zx = -1;   // (-1: a single K tile -- wait for everything)
+    unsigned long long* ts = nullptr;
     // G' / C' live in the table of the CURRENT modulation slot: their address needs the device step counter (slot0, a scalar load issued at
     // the top of the kernel).  Requested right AFTER the prologue's LDS-DMA went out, so that the counter's round trip does not sit in front
     // of the first tile (it did: +1 us per consumer launch)
@@ -949,7 +999,26 @@ __global__ __launch_bounds__(512) void k_gemm_pp(GemmArgs a) {
     constexpr bool RCOPY2 = EPI == EPI_RESID && (VAR & 512) != 0, RZIN = EPI == EPI_RESID && (VAR & 1024) != 0;   // pp_store_resid: second operand / LayerNorm-finishing skip_linear
     static_assert(!RDUAL || (RGATE && RRES), "DUAL: the gated residual projection only");
     static_assert(!(RDUAL && RCOPY2) && !(RZIN && (RGATE || RRES || RDUAL || RCOPY2)), "forms of the residual epilogue");
-    auto z_late_load = [&]() {
+    auto z_late_load = [&](auto SITE_) {
+        // the rest of the kernel arguments, from the struct in ONE batch (common.h "Kernel-argument batch") BEHIND the requests of this wave's first K tile: their round trip runs under the tile's.
+        // (SITE: the call sites' statements must not be identical, or hipcc merges them into the block in front of the groups' branch -- in front of every tile -- and waits there.
+        // `late` is 0, unknown to hipcc: added to a pointer it PINS the result in SGPRs (see the function's head) and makes this block the place of the arguments' first use -- as tied asm operands the
+        // loaded pointers were copied, behind a wait, right where hipcc had hoisted their loads to: in front of the groups' branch)
+        long late = 0;
+        asm("; late arguments, site %1" : "+s"(late) : "n"(decltype(SITE_)::value), "s"(a.ts), "s"(a.row_slot), "s"(a.zstat_in), "s"(a.zs_stride), "s"(a.zparts), "s"(a.zt_slot_stride),
+            "s"(a.gate_slot_stride), "s"(a.zg_slot_stride), "s"(a.zG), "s"(a.zC));
+        const float *zG_ = a.zG + late, *zC_ = a.zC + late;
+        const float *rb_ = a.bias + late, *rg_ = a.gate + late, *rz_ = a.zg + late, *rz2_ = a.zg2 + late;
+        const float *rc_ = a.hn.rope_cos, *rs_ = a.hn.rope_sin;
+        if (rc_) { rc_ += late; rs_ += late; }   // (nullable, and tested below)
+        {
+            unsigned long long* ts_ = a.ts ? a.ts + late : nullptr;
+            ts = (ts_ && wave == 0) ? ts_ + 8 * (long)blockIdx.x : nullptr;
+            asm("" : "+s"(zslot));   // (the counter's first use, sign extension included, is HERE: hipcc had put `s_waitcnt lgkmcnt(0); s_ashr_i32` right behind the load)
+            z_shared_slot = a.row_slot == nullptr;
+            z_warm = EPI == EPI_QKV && rc_ && col0 < 2 * a.hn.H * a.hn.dh;
+            zx = nt >= 2 ? ((((ZMC && z_shared_slot) || EPI == EPI_RESID) && wave * 64 < ZNV) ? 1 : 0) + (z_warm ? 1 : 0) : -1;
+        }
         if constexpr (EPI == EPI_QKV) {
             // q / k tiles: the RoPE rows of the tile's 128 tokens (2 x 18 KB of the cos / sin tables) are read in the epilogue, by every workgroup
             // at the same time, and no longer in the L2 by then (the kernels in between stream through it): each thread pulls one end of one row
@@ -972,8 +1041,8 @@ __global__ __launch_bounds__(512) void k_gemm_pp(GemmArgs a) {
                 const int which = tid / (BN / 4), t4 = tid - which * (BN / 4);
                 int cp = col0 + 4 * t4;
                 cp = cp < a.N - 4 ? cp : a.N - 4;
-                const float* src = which == 0 ? rb_ : which == 1 ? (RGATE ? rg_ + (long)slot0 * a.gate_slot_stride : RZIN ? zG_ : rb_) : which == 2 ? rz_ + (long)slot0 * a.zg_slot_stride
-                                   : ((RDUAL || RCOPY2) ? rz2_ + (long)slot0 * a.zg2_slot_stride : rb_);
+                const float* src = which == 0 ? rb_ : which == 1 ? (RGATE ? rg_ + (long)zslot * a.gate_slot_stride : RZIN ? zG_ : rb_) : which == 2 ? rz_ + (long)zslot * a.zg_slot_stride
+                                   : ((RDUAL || RCOPY2) ? rz2_ + (long)zslot * a.zg2_slot_stride : rb_);
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + cp),
                                                  (__attribute__((address_space(3))) void*)(reinterpret_cast<char*>(zgc) + wave * 1024), 16, 0, 0);
             }
@@ -984,7 +1053,7 @@ __global__ __launch_bounds__(512) void k_gemm_pp(GemmArgs a) {
                 const int which = tid >= BN / 4, t4 = tid - which * (BN / 4);
                 int cp = col0 + 4 * t4;
                 cp = cp < a.N - 4 ? cp : a.N - 4;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((which ? zC_ : zG_) + (long)slot0 * a.zt_slot_stride + cp),
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((which ? zC_ : zG_) + (long)zslot * a.zt_slot_stride + cp),
                                                  (__attribute__((address_space(3))) void*)(reinterpret_cast<char*>(zgc) + wave * 1024), 16, 0, 0);
             }
             // the partial statistics of the rows this lane finishes in the epilogue: blind loads into AGPRs (every lane, no branch), in flight through the first K tile
@@ -992,8 +1061,6 @@ __global__ __launch_bounds__(512) void k_gemm_pp(GemmArgs a) {
             z_lane_load<FMR>(a.zstat_in, a.zs_stride, a.zparts, frow, a.M - 1, lane >> 4, zlr);
         }
     };
-    unsigned long long* ts = (a.ts && wave == 0) ? a.ts + 8 * (long)blockIdx.x : nullptr;
-    if (ts && lane == 0) { ts[0] = __builtin_readcyclecounter(); ts[6] = ez_stamp_start(); }   // [6], [7]: the 100 MHz device-wide clock (cycle counters are not comparable between workgroups)
     f32x4 acc[FM][FN];
 #pragma unroll
     for (int i = 0; i < FM; ++i)
@@ -1011,17 +1078,17 @@ __global__ __launch_bounds__(512) void k_gemm_pp(GemmArgs a) {
         const int row = q >> 3, c = q & 7;
         if (p < PA) {
             int grow = row0 + row;
-            grow = grow < a.M ? grow : a.M - 1;
-            poff[i] = (uint32_t)(grow * a.lda + ((c ^ ((row >> 1) & 7)) << 3)) * 2u;
+            grow = grow < kM ? grow : kM - 1;
+            poff[i] = (uint32_t)(grow * klda + ((c ^ ((row >> 1) & 7)) << 3)) * 2u;
         } else {
             const int r2 = row - BM;
             int gr = col0 + r2;
-            gr = gr < a.wrows ? gr : a.wrows - 1;
-            poff[i] = (uint32_t)(gr * a.ldw + ((c ^ ((r2 >> 1) & 7)) << 3)) * 2u;
+            gr = gr < kwrows ? gr : kwrows - 1;
+            poff[i] = (uint32_t)(gr * kldw + ((c ^ ((r2 >> 1) & 7)) << 3)) * 2u;
         }
     }
-    const char* gA = reinterpret_cast<const char*>(a.A) + (long)kb * (BK * 2);
-    const char* gW = reinterpret_cast<const char*>(a.W) + (long)kb * (BK * 2);
+    const char* gA = reinterpret_cast<const char*>(kA) + (long)kb * (BK * 2);
+    const char* gW = reinterpret_cast<const char*>(kW) + (long)kb * (BK * 2);
 
     // issue this wave's LDS-DMA instructions of K tile t: pieces [PB, PE) of the tile (compile-time range)
     auto issue = [&](int t, auto PB_, auto PE_) {
@@ -1129,7 +1196,7 @@ __global__ __launch_bounds__(512) void k_gemm_pp(GemmArgs a) {
 #pragma unroll
             for (int t = 0; t < PD; ++t) {
                 if (t < nt) issue(t, IB{}, IE{});
-                if (t == 0) z_late_load();   // right behind tile 0 (one LDS-DMA, left in flight by the wait below: zx)
+                if (t == 0) z_late_load(G_);   // right behind tile 0 (one LDS-DMA, left in flight by the wait below: zx)
             }
             if (zx < 0) wait_vmcnt<0>(); else wait_younger_x<PG, PD - 1, NZT>((nt < PD ? nt : PD) - 1, zx);
             barrier();
@@ -1155,7 +1222,7 @@ __global__ __launch_bounds__(512) void k_gemm_pp(GemmArgs a) {
                     if (rf || t + 1 < nt) barrier();
                 }
             };
-            if (ts && lane == 0) ts[1] = __builtin_readcyclecounter();
+            if (ts && lane == 0) { const unsigned long long t1 = __builtin_readcyclecounter(); ts[0] = t_start; ts[6] = ez_stamp_tag(t_real); ts[1] = t1; }   // [6], [7]: the 100 MHz device-wide clock (cycle counters are not comparable between workgroups)
             int t = 0;
             for (; t + PD < nt; ++t) step(t, std::true_type{});
             for (; t < nt; ++t) step(t, std::false_type{});
@@ -1168,6 +1235,7 @@ __global__ __launch_bounds__(512) void k_gemm_pp(GemmArgs a) {
         using IB = std::integral_constant<int, 0>;
         using IE = std::integral_constant<int, NP>;
         static_assert(NP * ((PD - 1) / 2 + 1) < 64, "vmcnt range");
+        static_assert(PD >= 2, "the group that does not own tile 0 runs z_late_load behind ITS first tile, K tile 1: the prologue must reach u == 1");
         // own tiles that are younger than tile u and already issued at the end of interval u - 1: u + 2, u + 4, ... <= min(u - 1 + PD, nt - 1)
         auto own_younger = [&](int u) {
             const int last = u - 1 + PD < nt - 1 ? u - 1 + PD : nt - 1;
@@ -1175,13 +1243,13 @@ __global__ __launch_bounds__(512) void k_gemm_pp(GemmArgs a) {
         };
         auto run = [&](auto G_) {
             constexpr int G = decltype(G_)::value;
-            // z_late_load (the per-column vectors' LDS-DMA; fused QKV: the RoPE-table warm-up) goes out right behind tile 0 in the group that owns it, in front of its first
-            // tile in the other group; nothing in front of the loop waits for it in the other group
-            if constexpr ((PD & 1) != G) z_late_load();
+            // z_late_load (the rest of the kernel arguments; the per-column vectors' LDS-DMA; fused QKV: the RoPE-table warm-up) goes out right behind tile 0 in the group that owns it,
+            // right behind ITS first tile, K tile 1, in the other group (whether or not that tile exists); nothing in front of the loop waits for it in the other group
 #pragma unroll
             for (int u = 0; u < PD; ++u) {
                 if (((u + PD) & 1) == G && u < nt) issue(u, IB{}, IE{});
-                if (u == 0 && (PD & 1) == G) z_late_load();
+                if (u == 0 && (PD & 1) == G) z_late_load(G_);
+                if (u == 1 && (PD & 1) != G) z_late_load(G_);   // (the other group: behind ITS first tile, K tile 1 -- the requests of either are older than the group's second tile, whose wait covers them)
             }
             {
                 const int last = PD - 1 < nt - 1 ? PD - 1 : nt - 1;
@@ -1218,7 +1286,7 @@ __global__ __launch_bounds__(512) void k_gemm_pp(GemmArgs a) {
                     barrier();
                 }
             };
-            if (ts && lane == 0) ts[1] = __builtin_readcyclecounter();
+            if (ts && lane == 0) { const unsigned long long t1 = __builtin_readcyclecounter(); ts[0] = t_start; ts[6] = ez_stamp_tag(t_real); ts[1] = t1; }   // [6], [7]: the 100 MHz device-wide clock (cycle counters are not comparable between workgroups)
             int t = G;
             for (; t + 1 + PD < nt; t += 2) step(t, std::true_type{});
             for (; t < nt; t += 2) step(t, std::false_type{});
@@ -1340,14 +1408,14 @@ __global__ __launch_bounds__(512) void k_gemm_pp(GemmArgs a) {
             static_assert(BN == 144 || BN == 128, "EPI_QKV tiles hold two whole heads (head_dim 72 / 64)");
             static_assert(BM * (BN + 4) * 4 + BM * BN * 2 <= NS * STAGE, "epilogue tile + staging must fit the ring");
             static_assert(BM * (BN + 8) * 2 <= NS * STAGE, "bf16 staging tile must fit the ring");
-            if (a.hn.perm) pp_store_qkv_reg<BM, BN, BN / 2, HF, FN, TM / 2, TN, NT, ZM>(a, half, smem, row0, col0, ewm, lane, tid, zmr, zgc, reinterpret_cast<float*>(smem + NS * STAGE + BM * 8 + 2 * BN * 4 + 8 * 256), slot0, qop, ts);
-            else pp_store_qkv<BM, BN, BN / 2, HF, FN, TM / 2, TN, NT, ZM>(a, half, smem, row0, col0, ewm, wn, lane, tid, zmr, zgc, slot0);
+            if (a.hn.perm) pp_store_qkv_reg<BM, BN, BN / 2, HF, FN, TM / 2, TN, NT, ZM>(a, half, smem, row0, col0, ewm, lane, tid, zmr, zgc, reinterpret_cast<float*>(smem + NS * STAGE + BM * 8 + 2 * BN * 4 + 8 * 256), zslot, qop, ts);
+            else pp_store_qkv<BM, BN, BN / 2, HF, FN, TM / 2, TN, NT, ZM>(a, half, smem, row0, col0, ewm, wn, lane, tid, zmr, zgc, zslot);
         }
         if constexpr (EPI == EPI_GEGLU || EPI == EPI_PARTIAL) {
             constexpr bool lds_ok = BM * ((EPI == EPI_GEGLU ? BN / 2 : BN) + 8) * 2 <= NS * STAGE;
             if constexpr (lds_ok) {
                 if (EPI == EPI_GEGLU || a.part_bf16) {
-                    pp_store_lds<BM, BN, HF, FN, TM / 2, TN, NT, EPI, ZM>(a, half, smem, row0, col0, ewm, wn, lane, tid, z, zmr, zgc, slot0, ts);
+                    pp_store_lds<BM, BN, HF, FN, TM / 2, TN, NT, EPI, ZM>(a, half, smem, row0, col0, ewm, wn, lane, tid, z, zmr, zgc, zslot, ts);
                     if (ts && lane == 0) { ts[3] = __builtin_readcyclecounter(); ts[7] = __builtin_amdgcn_s_memrealtime(); }
                     return;
                 }
@@ -1364,13 +1432,13 @@ __global__ __launch_bounds__(512) void k_gemm_pp(GemmArgs a) {
             static_assert(BM * (BN + 8) * 2 <= NS * STAGE, "bf16 staging tile must fit the ring");
             QkvOperands<BN / 2, FM> qop;
             qkv_request<BN / 2, FM>(a, col0, row0 + wm * TM + (lane & 15), lane, tid, qop);
-            pp_store_qkv_reg<BM, BN, BN / 2, FM, FN, TM, TN, NT, ZM>(a, acc, smem, row0, col0, wm, lane, tid, zmr, zgc, reinterpret_cast<float*>(smem + NS * STAGE + BM * 8 + 2 * BN * 4 + 8 * 256), slot0, qop, ts);
+            pp_store_qkv_reg<BM, BN, BN / 2, FM, FN, TM, TN, NT, ZM>(a, acc, smem, row0, col0, wm, lane, tid, zmr, zgc, reinterpret_cast<float*>(smem + NS * STAGE + BM * 8 + 2 * BN * 4 + 8 * 256), zslot, qop, ts);
         }
         if constexpr (EPI == EPI_GEGLU || EPI == EPI_PARTIAL) {
             constexpr bool lds_ok = BM * ((EPI == EPI_GEGLU ? BN / 2 : BN) + 8) * 2 <= NS * STAGE;
             if constexpr (lds_ok) {
                 if (EPI == EPI_GEGLU || a.part_bf16) {
-                    pp_store_lds<BM, BN, FM, FN, TM, TN, NT, EPI, ZM>(a, acc, smem, row0, col0, wm, wn, lane, tid, z, zmr, zgc, slot0, ts);
+                    pp_store_lds<BM, BN, FM, FN, TM, TN, NT, EPI, ZM>(a, acc, smem, row0, col0, wm, wn, lane, tid, z, zmr, zgc, zslot, ts);
                     if (ts && lane == 0) { ts[3] = __builtin_readcyclecounter(); ts[7] = __builtin_amdgcn_s_memrealtime(); }
                     return;
                 }

@@ -9,6 +9,8 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from ezaudio_amd.build import UNIT_FLAGS  # noqa: E402  (the unit's own code-generation options: kernel-argument preload)
 
 
 def main():
@@ -16,7 +18,7 @@ def main():
     flt = sys.argv[2] if len(sys.argv) > 2 else ''
     with tempfile.TemporaryDirectory() as d:
         r = subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-c', src, '-o', os.path.join(d, 'x.o'),
-                            '-Rpass-analysis=kernel-resource-usage'] + sys.argv[3:], capture_output=True, text=True)
+                            '-Rpass-analysis=kernel-resource-usage'] + UNIT_FLAGS.get(sys.argv[1], []) + sys.argv[3:], capture_output=True, text=True)
     blocks = re.split(r'remark: Function Name: ', r.stderr)[1:]
     for b in blocks:
         name = b.split()[0]
