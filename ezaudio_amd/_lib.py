@@ -154,6 +154,14 @@ PROTOTYPES = {
                                                       C.c_int, C.c_int, C.c_int, C.c_int,
                                                       C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                                       C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
+    'ezdit_set_context_token_weights': (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
+    'ezdit_test_attention_keyweights': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
+    'ezdit_test_cross_attention_keyweights': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                        C.c_int, C.c_int, C.c_int, C.c_int,
+                                                        C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
+                                                        C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
 }
 
 

@@ -97,8 +97,10 @@ class EzAudio:
         return radius
 
     def generate_audio(self, text, length=10, guidance_scale=5, guidance_rescale=0.75, ddim_steps=100, eta=1,
-                       random_seed=None, randomize_seed=False, attention_window=None, compose=None, solver='ddim'):
-        """api/ezaudio.py:101-130.  `text` may also be a list of prompts (batched extension): the result is then
+                       random_seed=None, randomize_seed=False, attention_window=None, compose=None, emphasis=False, solver='ddim'):
+        """`emphasis=True` reads '(words:1.6)' markup in the prompts (sampler.parse_emphasis: per-token weights in cross-attention; the default leaves every prompt
+        verbatim; audio quality on the real checkpoints is unmeasured) -- here and on editing_audio, audio_to_audio, generate_long_audio and generate_loop.
+        api/ezaudio.py:101-130.  `text` may also be a list of prompts (batched extension): the result is then
         an array [N, T].  With a list of prompts `length` may be a list too, one duration in seconds per prompt (mixed-length
         batch, one call): the result is then (sr, [one 1-D array per prompt]), each trimmed to its own duration.
         `guidance_scale`, `guidance_rescale`, `eta` and `random_seed` may be lists as well, one entry per prompt of the list `text`: every
@@ -145,7 +147,7 @@ class EzAudio:
             random_seed = random.randint(0, MAX_SEED) if isinstance(text, str) else [random.randint(0, MAX_SEED) for _ in text]
         pred = inference(self.autoencoder, self.unet, gt, gt_mask, self.tokenizer, self.text_encoder, self.params,
                          self.noise_scheduler, text, neg_text, length, guidance_scale, guidance_rescale, ddim_steps,
-                         eta, random_seed, self.device, solver=solver, attention_window=radius, **({} if compose is None else dict(compose=compose)))
+                         eta, random_seed, self.device, solver=solver, attention_window=radius, **({} if compose is None else dict(compose=compose)), **({} if not emphasis else dict(emphasis=True)))
         pred = pred.cpu().numpy()
         if per_prompt:
             ratio = self.params['autoencoder']['sr'] // latent_sr
@@ -180,7 +182,7 @@ class EzAudio:
         return self.params['autoencoder']['sr'], pred.cpu().numpy().squeeze(0).squeeze(0)
 
     def generate_long_audio(self, text, length, window=10, overlap=2.5, guidance_scale=5, guidance_rescale=0.75, ddim_steps=100, eta=1,
-                            random_seed=None, randomize_seed=False, solver='ddim'):
+                            random_seed=None, randomize_seed=False, solver='ddim', emphasis=False):
         """A clip of `length` seconds, longer than the `window` seconds the model was trained on: the latent canvas is covered by overlapping windows of
         `window` seconds that share at least `overlap` seconds with their neighbours (sampler.canvas_windows chooses the fewest such windows, spread evenly),
         all windows are denoised together as the prompts of ONE batched sampler call, the shared frames are cross-faded inside every step, and the canvas is
@@ -211,11 +213,11 @@ class EzAudio:
         if randomize_seed:
             random_seed = random.randint(0, MAX_SEED)
         pred = inference(self.autoencoder, self.unet, None, None, self.tokenizer, self.text_encoder, self.params, self.noise_scheduler, prompts, None,
-                         frames, guidance_scale, guidance_rescale, ddim_steps, eta, random_seed, self.device, canvas_offsets=offsets, solver=solver)
+                         frames, guidance_scale, guidance_rescale, ddim_steps, eta, random_seed, self.device, canvas_offsets=offsets, solver=solver, **({} if not emphasis else dict(emphasis=True)))
         return self.params['autoencoder']['sr'], pred.cpu().numpy().squeeze(0).squeeze(0)
 
     def generate_loop(self, text, length, window=10, overlap=2.5, guidance_scale=5, guidance_rescale=0.75, ddim_steps=100, eta=1,
-                      random_seed=None, randomize_seed=False, solver='ddim', decode_context=None):
+                      random_seed=None, randomize_seed=False, solver='ddim', decode_context=None, emphasis=False):
         """A clip of `length` seconds that runs from its end into its own beginning: ``np.tile(waveform, k)`` is the loop.  The latent canvas is a RING covered
         by windows of `window` seconds, each sharing at least `overlap` seconds with the next one around the ring, the last with the first
         (sampler.loop_windows chooses the fewest such windows, at least two, spread evenly); all windows are denoised together as the prompts of ONE batched
@@ -249,7 +251,7 @@ class EzAudio:
             random_seed = random.randint(0, MAX_SEED)
         pred = inference(self.autoencoder, self.unet, None, None, self.tokenizer, self.text_encoder, self.params, self.noise_scheduler, prompts, None,
                          frames, guidance_scale, guidance_rescale, ddim_steps, eta, random_seed, self.device, canvas_offsets=offsets, canvas_loop=ring,
-                         decode_context=decode_context, solver=solver)
+                         decode_context=decode_context, solver=solver, **({} if not emphasis else dict(emphasis=True)))
         return self.params['autoencoder']['sr'], pred.cpu().numpy().squeeze(0).squeeze(0)
 
     def _load_edit_clip(self, gt_file):
@@ -286,7 +288,7 @@ class EzAudio:
                     chunk_length=end_idx - start_idx)
 
     def editing_audio(self, text, boundary, gt_file, mask_start, mask_length, guidance_scale=3.5, guidance_rescale=0,
-                      ddim_steps=100, eta=1, random_seed=None, randomize_seed=False, attention_window=None, solver='ddim'):
+                      ddim_steps=100, eta=1, random_seed=None, randomize_seed=False, attention_window=None, emphasis=False, solver='ddim'):
         """api/ezaudio.py:132-207 (crop / pad / mask bookkeeping on the host, sampling on the GPU).  `solver` and `attention_window` (seconds; quality on the real
         checkpoints unmeasured) as in generate_audio.  `gt_file` is a path or a
         1-D numpy waveform at the model's sample rate.
@@ -302,7 +304,7 @@ class EzAudio:
         radius = self._window_radius(attention_window)
         if not isinstance(text, str):
             return self._editing_audio_batch(list(text), boundary, gt_file, mask_start, mask_length, guidance_scale, guidance_rescale, ddim_steps, eta,
-                                             random_seed, randomize_seed, solver, radius)
+                                             random_seed, randomize_seed, solver, radius, emphasis)
         for name, v in (('gt_file', gt_file), ('boundary', boundary), ('mask_start', mask_start), ('mask_length', mask_length),
                         ('guidance_scale', guidance_scale), ('guidance_rescale', guidance_rescale), ('eta', eta), ('random_seed', random_seed)):
             if isinstance(v, (list, tuple)):
@@ -326,7 +328,7 @@ class EzAudio:
             random_seed = random.randint(0, MAX_SEED)
         pred = inference(self.autoencoder, self.unet, gt_latent, gt_mask, self.tokenizer, self.text_encoder,
                          self.params, self.noise_scheduler, text, neg_text, L, guidance_scale, guidance_rescale,
-                         ddim_steps, eta, random_seed, self.device, solver=solver, attention_window=radius)
+                         ddim_steps, eta, random_seed, self.device, solver=solver, attention_window=radius, **({} if not emphasis else dict(emphasis=True)))
         pred = pred.cpu().numpy().squeeze(0).squeeze(0)
         pred = pred[:round(req['chunk_length'] * sr)]
         output_audio = req['output_audio']
@@ -334,7 +336,7 @@ class EzAudio:
         return sr, output_audio
 
     def _editing_audio_batch(self, text, boundary, gt_file, mask_start, mask_length, guidance_scale, guidance_rescale, ddim_steps, eta, random_seed,
-                             randomize_seed, solver, radius=None):
+                             randomize_seed, solver, radius=None, emphasis=False):
         """editing_audio for a list of prompts: N crops in one ragged encode, one sampler call at per-request latent lengths, one ragged decode."""
         n = len(text)
         if isinstance(ddim_steps, (list, tuple)):
@@ -373,7 +375,7 @@ class EzAudio:
             random_seed = [random.randint(0, MAX_SEED) for _ in text]
         pred = inference(self.autoencoder, self.unet, gt_latent, gt_mask, self.tokenizer, self.text_encoder,
                          self.params, self.noise_scheduler, text, None, frames, guidance_scale, guidance_rescale,
-                         ddim_steps, eta, random_seed, self.device, solver=solver, attention_window=radius)
+                         ddim_steps, eta, random_seed, self.device, solver=solver, attention_window=radius, **({} if not emphasis else dict(emphasis=True)))
         pred = pred.cpu().numpy()
         outs = []
         for i, r in enumerate(reqs):
@@ -383,7 +385,7 @@ class EzAudio:
         return sr, outs
 
     def audio_to_audio(self, text, audio, strength=0.5, guidance_scale=5, guidance_rescale=0.75, ddim_steps=100, eta=1, random_seed=None,
-                       randomize_seed=False, attention_window=None, solver='ddim'):
+                       randomize_seed=False, attention_window=None, solver='ddim', emphasis=False):
         """Re-render a recording under a prompt, staying as close to it as `strength` says (not in the reference: the standard "start the sampler from the
         noised clip" of image-to-image, SDEdit).  `audio` is a path or a 1-D numpy waveform at the model's sample rate, peak-normalised and encoded whole;
         `strength` in (0, 1] is the share of the `ddim_steps` that are run (scheduler.start_step): 1 starts from pure noise, the plain generate_audio of the
@@ -438,7 +440,7 @@ class EzAudio:
             L = latent.shape[-1]
             pred = inference(self.autoencoder, self.unet, None, None, self.tokenizer, self.text_encoder, self.params, self.noise_scheduler, text, None, L,
                              guidance_scale, guidance_rescale, ddim_steps, eta, random_seed, self.device, solver=solver, init_latents=latent,
-                             strength=strength, attention_window=radius)
+                             strength=strength, attention_window=radius, **({} if not emphasis else dict(emphasis=True)))
             return sr, pred.cpu().numpy().squeeze(0).squeeze(0)
         text = list(text)
         if '' in text:
@@ -454,7 +456,7 @@ class EzAudio:
         frames = [int(v) for v in self.autoencoder.latent_lengths(samples)]
         pred = inference(self.autoencoder, self.unet, None, None, self.tokenizer, self.text_encoder, self.params, self.noise_scheduler, text, None, frames,
                          guidance_scale, guidance_rescale, ddim_steps, eta, random_seed, self.device, solver=solver, init_latents=latent,
-                         strength=per(strength), attention_window=radius)
+                         strength=per(strength), attention_window=radius, **({} if not emphasis else dict(emphasis=True)))
         pred = pred.cpu().numpy()
         up = pred.shape[-1] // max(frames)                                     # samples per latent frame, as decoded
         return sr, [pred[i, 0, :f * up] for i, f in enumerate(frames)]

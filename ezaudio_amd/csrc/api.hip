@@ -140,6 +140,9 @@ struct ezdit_handle {
     Table<float> tl;
     int2* tlsup = nullptr;
     int tl_S = 0;
+    // prompt emphasis (ezdit_set_context_token_weights): [B][Lcp] score biases log2(w_j / max w) of the context keys (k_attn KW, AttnArgs.kbias), zero at masked and padding
+    // keys.  On only while some bias is non-zero: a uniform row is the plain kernel.  Read by the cross-attention launch only
+    Table<float> tw;
     // ---- call-scoped: they belong to one sampler call and are cleared by reset_call_state ----
     // per-sample sampler settings (ezdit_sampler_set_sample_params), read by k_cfg_stats / k_cfg_apply: the mirror is [P][2] (guidance_scale, guidance_rescale),
     // which goes to `dev`, then [n_steps][P][8] DDIM coefficients, which go to p.spc.  Room for sp_cap(B) samples: the B / 2 of a CFG batch
@@ -550,6 +553,7 @@ size_t carve(const ezdit_handle* h, int B, int L, int Lc, int n_slots, std::map<
         add("tlb", (size_t)B * (Lcp / 128) * L * 4);     // prompt timeline (ezdit_set_context_weights): one score bias per (batch element, prompt, frame) and the prompts' frame
         add("tlsup", (size_t)B * (Lcp / 128) * 8);       // supports, behind `canvas` for the same reason: B L 4 bytes at one prompt
         add("cw", (size_t)B * sizeof(float));            // weights of composed guidance [P][K], P K < B = (K + 1) P; at the very end for the same reason
+        add("kbias", (size_t)B * Lcp * 4);               // prompt emphasis (ezdit_set_context_token_weights): one score bias per context key, behind `cw` for the same reason
     }
     return off;
 }
@@ -736,6 +740,7 @@ void resolve_workspace(ezdit_handle* h) {
     h->start.dev = h->buf<int>("start"); h->canvas.dev = h->buf<int>("canvas");
     h->tl.dev = h->buf<float>("tlb"); h->tlsup = h->buf<int2>("tlsup");
     h->cw.dev = h->buf<float>("cw");
+    h->tw.dev = h->buf<float>("kbias");
     p.zstat = h->buf<float2>("zstat"); p.zt_qkv = h->buf<float>("zt_qkv"); p.zt_geglu = h->buf<float>("zt_geglu"); p.zt_q2 = h->buf<float>("zt_q2");
     p.zstat_skip = h->buf<float2>("zstat_skip"); p.zt_skip = h->buf<float>("zt_skip"); p.ucat_z = h->buf<bf16_t>("ucat_z");
     if (h->is_cn) { p.cembed = h->buf<float>("cembed"); p.cnres = h->buf<float>("cnres"); p.skipbf = h->buf<bf16_t>("skipbf"); }
@@ -852,6 +857,35 @@ int timeline_table(const float* w, int B, int S, int L, const int* lens, const u
     return EZDIT_OK;
 }
 
+// Prompt emphasis of B batch elements (include/ezdit.h, ezdit_set_context_token_weights): natural weights w [B][Lk] -> the table the KW form of k_attn reads, [B][Lkp]
+// biases fp32(log2(w_j / max over the valid keys)), computed in fp64: every bias is <= 0, the heaviest valid key has exactly 0, and masked and padding keys hold 0.
+// mask (nullable = every key valid, [B][Lk]): w is not read at a masked key.  *any: some bias is non-zero (a table of zeros is the plain kernel)
+int keyweight_table(const float* w, int B, int Lk, int Lkp, const uint8_t* mask, std::vector<float>* out, bool* any) {
+    out->assign((size_t)B * Lkp, 0.f);
+    *any = false;
+    for (int b = 0; b < B; ++b) {
+        double mx = 0.0, mn = 0.0;
+        bool seen = false;
+        for (int j = 0; j < Lk; ++j) {
+            if (mask && !mask[(size_t)b * Lk + j]) continue;
+            const float x = w[(size_t)b * Lk + j];
+            if (!std::isfinite(x) || !(x > 0.f)) return fail(EZDIT_E_INVALID, "weights[%d][%d] = %g: the weight of a valid key is finite and above 0 (the mask drops a token)", b, j, (double)x);
+            mx = seen ? (x > mx ? x : mx) : x;
+            mn = seen ? (x < mn ? x : mn) : x;
+            seen = true;
+        }
+        if (!seen) continue;   // (a row without a valid key has no weights to check; its biases stay 0)
+        if (mx > mn * 1048576.0) return fail(EZDIT_E_INVALID, "weights of batch element %d span %g .. %g: more than 2^20 apart", b, mn, mx);
+        for (int j = 0; j < Lk; ++j) {
+            if (mask && !mask[(size_t)b * Lk + j]) continue;
+            const float bias = (float)std::log2((double)w[(size_t)b * Lk + j] / mx);
+            (*out)[(size_t)b * Lkp + j] = bias;
+            *any = *any || bias != 0.f;
+        }
+    }
+    return EZDIT_OK;
+}
+
 // A ControlNet handle carries a length table only as half of an attached pair (ezdit_sampler_set_pair_lengths): when the pair ends -- detach, or the
 // backbone is destroyed -- the table goes, and with it the condition embed that was computed from it.  The backbone keeps its own table.
 void clear_cn_lengths(ezdit_handle* cn) {
@@ -886,6 +920,7 @@ void reset_bind_state(ezdit_handle* h) {
     h->lens.set(h, false); h->lens.host.clear();
     h->cns.set(h, false);
     h->tl.set(h, false); h->tl.host.clear(); h->tl_S = 0;
+    h->tw.set(h, false); h->tw.host.clear();
     h->coef.host.clear();
     h->latents = nullptr; h->noise = nullptr; h->s_gt = nullptr; h->s_gt_mask = nullptr;
     h->P = 0; h->n_steps = 0;
@@ -1036,6 +1071,7 @@ int ezdit_prepare_context(ezdit_handle* h, const float* ctx, const uint8_t* mask
     else HIPCHK(hipMemsetAsync(km, 1, Mc, c.st));
     // (the context weights were checked against the old mask: a new context starts without them.  Behind the first copy: a call refused above changes nothing)
     h->tl.set(h, false); h->tl.host.clear(); h->tl_S = 0;
+    h->tw.set(h, false); h->tw.host.clear();   // (the token weights likewise)
     // single-key batch elements (opt_xkey1): their cross-attention output is a constant.  The mask is read back once per call (B Lc bytes)
     std::vector<int> key1(h->B, -1);   // the valid key of a single-key batch element, -1 otherwise
     const bool old_x1 = h->xkey1; const int old_b0 = h->act_b0, old_b1 = h->act_b1;
@@ -1260,6 +1296,7 @@ int ezdit_set_context_weights(ezdit_handle* h, const float* weights, int S, ezdi
     if (h->cn) return fail(EZDIT_E_UNSUPPORTED, "context weights with a ControlNet attached");
     if (h->canvas.on) return fail(EZDIT_E_UNSUPPORTED, "context weights while the canvas is on (ezdit_sampler_set_canvas): a window has one prompt");
     if (h->cw.on) return fail(EZDIT_E_UNSUPPORTED, "context weights while composed guidance is on (ezdit_sampler_begin_composed)");
+    if (h->tw.on) return fail(EZDIT_E_UNSUPPORTED, "context weights while the token weights are on (ezdit_set_context_token_weights)");
     if (S < 1 || S > TL_MAXS) return fail(EZDIT_E_INVALID, "S = %d outside [1, %d]", S, TL_MAXS);
     if (h->Lc != 128 * S) return fail(EZDIT_E_INVALID, "S = %d prompts need a context of %d tokens (128 each), the workspace is bound to Lc = %d", S, 128 * S, h->Lc);
     if (!h->ctx_ready) return fail(EZDIT_E_STATE, "ezdit_prepare_context first: the weights are checked against its key mask");
@@ -1271,6 +1308,36 @@ int ezdit_set_context_weights(ezdit_handle* h, const float* weights, int S, ezdi
     if (int rc = upload_table(h->tl, std::move(v), st, (size_t)h->B * S * h->L, reinterpret_cast<float*>(h->tlsup))) return rc;
     h->tl.set(h, true);
     h->tl_S = S;
+    return EZDIT_OK;
+}
+
+// Prompt emphasis: one weight per context token of every batch row.  The table is checked against the key mask of the latest ezdit_prepare_context, then read by the
+// cross-attention launch of every block (k_attn KW).  A table of zeros (every row uniform) is OFF: the plain instantiations run
+int ezdit_set_context_token_weights(ezdit_handle* h, const float* weights, int n, ezdit_stream stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (h && weights && h->is_cn) return fail(EZDIT_E_UNSUPPORTED, "token weights on a ControlNet handle (its blocks have cross-attention of their own)");
+    if (int rc = setter_checks(h, "ezdit_set_context_token_weights", Needs::Bound, st)) return rc;
+    if (!weights) {
+        h->tw.set(h, false); h->tw.host.clear();
+        return EZDIT_OK;
+    }
+    if (h->cn) return fail(EZDIT_E_UNSUPPORTED, "token weights with a ControlNet attached (its blocks have cross-attention of their own)");
+    if (h->tl.on) return fail(EZDIT_E_UNSUPPORTED, "token weights while the context weights are on (ezdit_set_context_weights)");
+    if (n != h->B) return fail(EZDIT_E_INVALID, "n = %d rows of weights, the workspace is bound to B = %d", n, h->B);
+    if (!h->ctx_ready) return fail(EZDIT_E_STATE, "ezdit_prepare_context first: the weights are checked against its key mask");
+    std::vector<uint8_t> km((size_t)h->Mc);
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(km.data(), h->p.kmask, km.size(), hipMemcpyDeviceToHost));
+    std::vector<float> v;
+    bool any = false;
+    if (int rc = keyweight_table(weights, h->B, h->Lc, h->Lcp, km.data(), &v, &any)) return rc;
+    if (!any) {   // every row uniform: the plain kernel, bit for bit the call that never set the table
+        h->tw.set(h, false); h->tw.host.clear();
+        return EZDIT_OK;
+    }
+    // (a shape whose cross-attention does not run an 8-wave form is refused by launch_attention itself: the forward or the step reports its return code as EZDIT_E_UNSUPPORTED)
+    if (int rc = upload_table(h->tw, std::move(v), st)) return rc;
+    h->tw.set(h, true);
     return EZDIT_OK;
 }
 
@@ -1546,10 +1613,12 @@ static int forward_impl(ezdit_handle* h, const float* x, int in_ch, int x_rows, 
             at.v = p.vc + (size_t)b * h->B * h->H * h->Lcp * h->DV;
             at.kmask = p.kmask; at.klen = nullptr; at.band = 0;   // (the key lengths and the band are self-attention's: context keys have their own mask and no time axis)
             at.tlb = h->tl.read(); at.tlsup = h->tl.on ? h->tlsup : nullptr;   // ... unless the prompt timeline gives them one (ezdit_set_context_weights): the TL form, the same single launch
+            at.kbias = h->tw.read();   // prompt emphasis (ezdit_set_context_token_weights): the KW form, the same single launch; [B][Lcp], advanced by b0 like the mask
             at.Lk = h->Lc; at.Lkp = h->Lcp;
             STOPCHK();
             at.ts = c.stamps(); at.ts_cap = g_gemm_ts_cap;
-            c.launched("k_attn (cross)", launch_attention(at, st));
+            const int arc = launch_attention(at, st);
+            c.launched("k_attn (cross)", arc && at.kbias ? EZDIT_E_UNSUPPORTED : arc);   // (a shape without an 8-wave form while the token weights are on: ezdit_set_context_token_weights)
             STOPCHK();
             Edge e;
             e.name = "k_gemm (un-split residual: cross-out)"; e.algebra = zf;
@@ -1696,6 +1765,7 @@ int ezdit_sampler_attach_controlnet(ezdit_handle* h, ezdit_handle* cn, float con
     if (cn && h->canvas.on) return fail(EZDIT_E_UNSUPPORTED, "a ControlNet while the canvas is on (ezdit_sampler_set_canvas)");
     if (cn && h->tl.on) return fail(EZDIT_E_UNSUPPORTED, "a ControlNet while the context weights are on (ezdit_set_context_weights)");
     if (cn && h->cw.on) return fail(EZDIT_E_UNSUPPORTED, "a ControlNet while composed guidance is on (ezdit_sampler_begin_composed)");
+    if (cn && h->tw.on) return fail(EZDIT_E_UNSUPPORTED, "a ControlNet while the token weights are on (ezdit_set_context_token_weights)");
     if (cn && cn->attn_window != h->attn_window)
         return fail(EZDIT_E_INVALID, "attention windows differ: backbone %d, ControlNet %d frames (ezdit_set_attention_window on both)", h->attn_window, cn->attn_window);
     if (h->cn && h->cn != cn) {
@@ -2404,6 +2474,71 @@ int ezdit_test_cross_attention_timeline(const void* xu, int ldu, const void* xw,
     a.qn_w = qn_w; a.qn_b = qn_b; a.nkh = 4; a.xk2 = xk2; a.qtile = qtile; a.xcd_map = xcd_map;
     a.zstat_in = (const float2*)zstat_in; a.zs_stride = zs_stride; a.zparts = zparts; a.zD = zD; a.zw = zw; a.zG = zG; a.zC = zC; a.zeps = zeps;
     return timeline_hook(a, weights, S, (hipStream_t)stream);
+}
+
+// the emphasis form, stand-alone: what both hooks share.  The key mask is read back (a test hook may wait), the table is built and checked as the setter does it, lives
+// in device memory of the hook's own for the launch of the batch elements [b0, b0 + B), and goes when the launch is done.  keep_on = 0: a table of zeros launches the
+// plain instantiation, as the setter would; 1: the KW instantiation whatever the table holds
+static int keyweight_hook(AttnArgs& a, const float* weights, int keep_on, hipStream_t st) {
+    if (!weights) return fail(EZDIT_E_INVALID, "null weights");
+    if (a.B <= 0 || a.b0 < 0 || a.Lq <= 0 || a.Lk <= 0 || a.Lkp < a.Lk) return fail(EZDIT_E_INVALID, "bad shape B=%d b0=%d Lq=%d Lk=%d Lkp=%d", a.B, a.b0, a.Lq, a.Lk, a.Lkp);
+    std::vector<uint8_t> km;
+    HIPCHK(hipStreamSynchronize(st));
+    if (a.kmask) {
+        km.resize((size_t)a.B * a.Lk);
+        HIPCHK(hipMemcpy(km.data(), a.kmask + (size_t)a.b0 * a.Lk, km.size(), hipMemcpyDeviceToHost));
+    }
+    std::vector<float> v;
+    bool any = false;
+    if (int rc = keyweight_table(weights, a.B, a.Lk, a.Lkp, a.kmask ? km.data() : nullptr, &v, &any)) return rc;
+    if (!any && !keep_on) return hook_launch("k_attn", "attention configuration", [&] { return launch_attention(a, st); });
+    const size_t nb = (size_t)a.B * a.Lkp, skip_b = (size_t)a.b0 * a.Lkp;
+    float* dev = nullptr;   // [b0 + B][Lkp]: launch_attention advances it by b0 batch elements
+    HIPCHK(hipMalloc(&dev, (skip_b + nb) * sizeof(float)));
+    const hipError_t e = hipMemcpy(dev + skip_b, v.data(), nb * sizeof(float), hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? EZDIT_OK : fail(EZDIT_E_HIP, "upload of the key-bias table failed: %s", hipGetErrorString(e));
+    if (!rc) {
+        a.kbias = dev;
+        rc = hook_launch("k_attn (emphasis)", "attention configuration", [&] { return launch_attention(a, st); });
+    }
+    const hipError_t es = hipStreamSynchronize(st);
+    (void)hipFree(dev);
+    if (!rc && es != hipSuccess) rc = fail(EZDIT_E_HIP, "k_attn (emphasis) failed: %s", hipGetErrorString(es));
+    return rc;
+}
+
+// the emphasis form of the plain 8-wave kernel (the q2_pp / q_raw paths of cross-attention): the arguments of ezdit_test_attention_timeline with natural weights [B][Lk] (HOST)
+int ezdit_test_attention_keyweights(ezdit_handle* h, const void* q, const void* k, const void* v, const uint8_t* kmask, void* out, int B,
+                                    int Lq, int Lk, int Lqp, int Lkp, const float* weights, int keep_on, ezdit_stream stream) {
+    if (int rc = attn_hook_refusals(h, q, k, v, kmask, out, B, Lq, Lk, Lqp, Lkp, (hipStream_t)stream)) return rc;
+    AttnArgs a;
+    memset(&a, 0, sizeof a);
+    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.kmask = kmask;
+    a.nkh = 4; a.xcd_map = h->opt_attn_xcd;
+    a.out = (bf16_t*)out; a.ldo = h->ldD;
+    a.B = B; a.H = h->H; a.Lq = Lq; a.Lk = Lk; a.Lqp = Lqp; a.Lkp = Lkp; a.dh = h->dh;
+    return keyweight_hook(a, weights, keep_on, (hipStream_t)stream);
+}
+
+// ... and of the fused-projection forms with the LayerNorm algebra: the arguments of ezdit_test_cross_attention, then weights [B][Lk] (HOST) of the launched batch elements
+int ezdit_test_cross_attention_keyweights(const void* xu, int ldu, const void* xw, int ldw, int xw_rows, int xK, const float* qn_w, const float* qn_b,
+                                          const void* k, const void* v, const uint8_t* kmask, void* out, int ldo, int B, int b0, int H, int dh, int Lq, int Lk, int Lqp, int Lkp,
+                                          const void* zstat_in, long zs_stride, int zparts, int zD, int zw, const float* zG, const float* zC, float zeps,
+                                          int xk2, int qtile, int xcd_map, const float* weights, int keep_on, ezdit_stream stream) {
+    if (!xu || !xw || xK <= 0 || xK % 64) return fail(EZDIT_E_INVALID, "the fused projection needs xu, xw and xK a multiple of 64");
+    if (!k || !v || !out || !zstat_in) return fail(EZDIT_E_INVALID, "null k, v, out or statistics");
+    if (qtile != 32 && qtile != 64) return fail(EZDIT_E_INVALID, "qtile = %d: 32 or 64", qtile);
+    if (qtile == 32 && (!xcd_map || (xK / 64) % 2)) return fail(EZDIT_E_INVALID, "qtile = 32 needs the XCD map and an even number of K tiles");
+    if (H <= 0 || (dh != 64 && dh != 72) || Lkp % 128 || Lqp < Lq) return fail(EZDIT_E_INVALID, "bad shape H=%d dh=%d Lq=%d Lqp=%d Lkp=%d", H, dh, Lq, Lqp, Lkp);
+    AttnArgs a;
+    memset(&a, 0, sizeof a);
+    a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.kmask = kmask;
+    a.out = (bf16_t*)out; a.ldo = ldo;
+    a.B = B; a.b0 = b0; a.H = H; a.Lq = Lq; a.Lk = Lk; a.Lqp = Lqp; a.Lkp = Lkp; a.dh = dh;
+    a.xu = (const bf16_t*)xu; a.ldu = ldu; a.xw = (const bf16_t*)xw; a.ldw = ldw; a.xw_rows = xw_rows; a.xK = xK;
+    a.qn_w = qn_w; a.qn_b = qn_b; a.nkh = 4; a.xk2 = xk2; a.qtile = qtile; a.xcd_map = xcd_map;
+    a.zstat_in = (const float2*)zstat_in; a.zs_stride = zs_stride; a.zparts = zparts; a.zD = zD; a.zw = zw; a.zG = zG; a.zC = zC; a.zeps = zeps;
+    return keyweight_hook(a, weights, keep_on, (hipStream_t)stream);
 }
 
 int ezdit_test_final_conv(const float* y, int ldy, const float* w, const float* b, float* out, int B, int C, int L, const int32_t* dev_lens,

@@ -64,8 +64,13 @@ struct HeadGeom<72> { static constexpr int DQK = 80, DV = 96; };
 // its registers nor its code.  Plain self-attention only (no query prologue, no key mask, Lq == Lk); what changes is marked "band:" below
 // TL: prompt timeline of cross-attention (AttnArgs.tlb / tlsup): key tile t IS prompt t (128 keys), and query i sees it under the additive score bias
 // tlb[b][t][i] = log2(w / max_s w) -- or not at all (weight 0).  A template switch like ZQ and BAND; the 8-wave form only (128-key tiles); what changes is marked "timeline:" below
-template <int DH, int NKH, bool ZQ = false, int QT = 64, bool BAND = false, bool TL = false>
+// KW: prompt emphasis of cross-attention (AttnArgs.kbias): key j carries the additive score bias kbias[b][j] = log2(w_j / max w) <= 0, the case between the validity bit per
+// key (kmask) and the timeline's bias per (query, tile).  A template switch like the others; the 8-wave forms only, not with BAND or TL; what changes is marked "emphasis:" below.
+// The 128 biases of a key tile are staged beside its K / V in the LDS double buffer (512 B per stage, requested with LOAD_TILE(t + 1)), so nothing waits on them in front of
+// the MFMAs; a lane reads its 16 as four float4 (keys key0 + 4 hi + 8 g + {0..3} are the values r = 4 g + {0..3} of the C layout)
+template <int DH, int NKH, bool ZQ = false, int QT = 64, bool BAND = false, bool TL = false, bool KW = false>
 __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
+    static_assert(!KW || (NKH == 4 && !BAND && !TL), "emphasis: the 8-wave cross-attention forms, without the timeline");
     static_assert(!TL || (NKH == 4 && !BAND), "the timeline: one prompt per 128-key tile, cross-attention only");
     static_assert(QT == 64 || (QT == 32 && NKH == 4), "32-query tiles: the 8-wave fused-projection form only");
     static_assert(!BAND || (!ZQ && QT == 64), "the band exists in the plain self-attention form only");
@@ -97,7 +102,8 @@ __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
     constexpr int PRED = 4 * 64 * DS * 4, PQS = QT * DQK * 2;               // partial tiles: [4][64][DS] or [8][32][DS] fp32
     constexpr int SMEM = NKH == 4 ? (2 * BUF > PRED + PQS ? (2 * BUF > PRING ? 2 * BUF : PRING) : (PRED + PQS > PRING ? PRED + PQS : PRING)) : 2 * BUF;
     constexpr int ZX = ZQ ? QT * 8 + 2 * DQK * 4 : 0;   // fused projection with the LayerNorm algebra: (mu, r) of the 64 query rows + G' | C' of the head
-    __shared__ __attribute__((aligned(16))) char smem[SMEM + ZX];
+    constexpr int KWB = KW ? 2 * TK * 4 : 0;            // emphasis: the key biases of the two staged tiles, behind everything else (never aliased)
+    __shared__ __attribute__((aligned(16))) char smem[SMEM + ZX + KWB];
 
     // kernel arguments in ONE batch (common.h "Kernel-argument batch": left alone, hipcc requests them in four dependent groups in front of the first load)
     int Lq_ = a.Lq;
@@ -452,6 +458,10 @@ __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
     // staging registers: NAMED scalars, not an array (hipcc demotes a register array that is live across the tile loop
     // to scratch); every thread issues all its loads unconditionally (chunk index clamped), only LDS writes are predicated
     uint4 k0 = {}, k1 = {}, k2 = {}, v0 = {}, v1 = {}, v2 = {};
+    // emphasis: the tile's 128 biases as 32 float4; every thread requests chunk tid & 31 (aligned and in bounds: the table is [B][Lkp], Lkp % 128 == 0), the first 32 park it
+    [[maybe_unused]] float4 kwreg = make_float4(0.f, 0.f, 0.f, 0.f);
+    [[maybe_unused]] const float* kwrow = nullptr;
+    if constexpr (KW) kwrow = a.kbias + (long)b * a.Lkp + 4 * (tid & 31);
     // per-thread byte offsets of the staged chunks, computed ONCE; the tile base pointers below are wave-uniform, so the loads take the
     // SGPR-base + 32-bit VGPR-offset form and the loop spends no VALU work on 64-bit addresses
     uint32_t koff[3], voff[3];
@@ -490,6 +500,7 @@ __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
         v0 = vchunk(0, key0_);                         \
         v1 = vchunk(1, key0_);                         \
         if constexpr (VPT > 2) v2 = vchunk(2, key0_);  \
+        if constexpr (KW) kwreg = *reinterpret_cast<const float4*>(kwrow + key0_);   \
     } while (0)
 #define WRITE_TILE(buf)                                \
     do {                                               \
@@ -501,6 +512,7 @@ __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
         vstore(0, vb_, v0);                            \
         vstore(1, vb_, v1);                            \
         if constexpr (VPT > 2) vstore(2, vb_, v2);     \
+        if constexpr (KW) { if (tid < TK / 4) *reinterpret_cast<float4*>(smem + SMEM + ZX + (buf) * (TK * 4) + 16 * tid) = kwreg; }   \
     } while (0)
 
     f32x16 o[NDT];
@@ -615,17 +627,34 @@ __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
                 else asm("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0\n\ts_nop 7\n\ts_nop 7\n\ts_nop 3" : "+v"(s) : "v"(kf), "v"(qf[ks]));
             }
             // lane holds S^T[key0 + (r&3) + 8*(r>>2) + 4*hi][q0 + r32]
+            // emphasis: kwb[4 g + e] = bias of key key0 + 4 hi + 8 g + e, the key of s[4 g + e]
+            [[maybe_unused]] float kwb[16];
+            if constexpr (KW) {
+                const float4* bl = reinterpret_cast<const float4*>(smem + SMEM + ZX + ((t - t_lo) & 1) * (TK * 4)) + kh * 8 + hi;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const float4 b4 = bl[2 * g];
+                    kwb[4 * g] = b4.x; kwb[4 * g + 1] = b4.y; kwb[4 * g + 2] = b4.z; kwb[4 * g + 3] = b4.w;
+                }
+            }
             float tmax = -1e30f;
             if (full) {
+                if constexpr (KW) {
+                    // emphasis: the maximum is over the biased scores.  At bias 0, fma(s, c, 0) = c s rounded once, and max(c s) == c max(s): the plain path's bits
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, __builtin_fmaf(s[r], c, kwb[r]));
+                } else {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, s[r]);
                 tmax *= c;   // c > 0: max(c s) == c max(s), rounding included
                 if constexpr (TL) tmax += tbias;   // timeline: the bias is per (query, tile): one add behind the maximum (a bias of 0 changes no bit)
+                }
             } else {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const bool v = (tmask >> ((r & 3) + 8 * (r >> 2))) & 1u;
                     if constexpr (TL) s[r] = v ? s[r] * c + tbias : -1e30f;
+                    else if constexpr (KW) s[r] = v ? __builtin_fmaf(s[r], c, kwb[r]) : -1e30f;   // emphasis: one FMA for the multiply (bias 0: the same bits); a masked key's bias is never used
                     else s[r] = v ? s[r] * c : -1e30f;
                     tmax = fmaxf(tmax, s[r]);
                 }
@@ -653,6 +682,10 @@ __global__ __launch_bounds__(128 * NKH) void k_attn(AttnArgs a) {
 #pragma unroll
                 for (int r = 0; r < 16; r += 2) {
                     f32x2 x = {s[r], s[r + 1]};
+                    if constexpr (KW) {   // emphasis: exp2(fma(s, c, bias - m)): at bias 0 this is the plain fma(s, c, -m)
+                        const f32x2 bm2 = {kwb[r] - m, kwb[r + 1] - m};
+                        x = __builtin_elementwise_fma(x, c2, bm2);
+                    } else
                     x = __builtin_elementwise_fma(x, c2, nm2);
                     p[r] = __builtin_amdgcn_exp2f(x[0]);
                     p[r + 1] = __builtin_amdgcn_exp2f(x[1]);
@@ -781,6 +814,7 @@ int launch_attention(const AttnArgs& a0, hipStream_t st) {
         if (a.zstat_in) a.zstat_in += b0 * a.Lq;
         if (a.klen) a.klen += b0;
         if (a.tlb) { a.tlb += b0 * (a.Lkp / 128) * a.Lq; a.tlsup += b0 * (a.Lkp / 128); }
+        if (a.kbias) a.kbias += b0 * a.Lkp;
         a.b0 = 0;
     }
     const long nwg64 = (long)((a.Lq + 63) / 64) * a.H * a.B;
@@ -795,6 +829,8 @@ int launch_attention(const AttnArgs& a0, hipStream_t st) {
     if ((a.tlb != nullptr) != (a.tlsup != nullptr)) return 1;
     if (a.tlb && (a.klen || a.band > 0 || a.Lk != a.Lkp || a.Lkp % 128 || a.Lkp / 128 > TL_MAXS)) return 1;
     if (a.tlb) nkh = 4;
+    // emphasis: a bias per key, cross-attention in an 8-wave form; not together with the timeline
+    if (a.kbias && (a.Lkp % 128 || nkh != 4 || a.band > 0 || a.klen || (a.Lq == a.Lk && !a.kmask && !a.xu && !a.q_raw) || a.tlb)) return 1;   // (self-attention: equal lengths, no key mask, no query prologue; a context as long as the row is cross-attention still)
     if (a.band > a.Lk) a.band = a.Lk;   // (the same mask: keeps the kernel's tile-range arithmetic far from overflow)
     const bool zq = a.xu && a.zstat_in;
     if (zq && !(a.zG && a.zC && a.zparts > 0 && a.zparts <= Z_MAXP && a.zs_stride > 0 && a.zw > 0)) return 1;
@@ -818,6 +854,19 @@ int launch_attention(const AttnArgs& a0, hipStream_t st) {
         } else {
             if (a.dh == 64) hipLaunchKernelGGL((k_attn<64, 4, false, 64, false, true>), grid, dim3(512), 0, st, a);
             else hipLaunchKernelGGL((k_attn<72, 4, false, 64, false, true>), grid, dim3(512), 0, st, a);
+        }
+        return 0;
+    }
+    if (a.kbias) {
+        if (q32) {
+            if (a.dh == 64) hipLaunchKernelGGL((k_attn<64, 4, true, 32, false, false, true>), grid, dim3(512), 0, st, a);
+            else hipLaunchKernelGGL((k_attn<72, 4, true, 32, false, false, true>), grid, dim3(512), 0, st, a);
+        } else if (zq) {
+            if (a.dh == 64) hipLaunchKernelGGL((k_attn<64, 4, true, 64, false, false, true>), grid, dim3(512), 0, st, a);
+            else hipLaunchKernelGGL((k_attn<72, 4, true, 64, false, false, true>), grid, dim3(512), 0, st, a);
+        } else {
+            if (a.dh == 64) hipLaunchKernelGGL((k_attn<64, 4, false, 64, false, false, true>), grid, dim3(512), 0, st, a);
+            else hipLaunchKernelGGL((k_attn<72, 4, false, 64, false, false, true>), grid, dim3(512), 0, st, a);
         }
         return 0;
     }

@@ -318,6 +318,10 @@ struct AttnArgs {
     // tlsup [B][S] = (first, last + 1) frame with a weight > 0 ((0, 0): none): a workgroup walks only the prompts whose support meets its queries.  Another instantiation
     // of k_attn (TL), the 8-wave form.  Read at run time: one captured graph serves every set of weights.  Behind band, for the same reason
     const float* tlb; const int2* tlsup;
+    // prompt emphasis of cross-attention (null = off): kbias [B][Lkp] fp32, the score bias log2(w_j / max_j w_j) <= 0 of key j in log2 units, 0 at masked and padding keys
+    // (kmask alone decides validity: a masked key takes P = 0 through the select, its bias is never used).  Another instantiation of k_attn (KW), the 8-wave forms
+    // (Lkp % 128 == 0); not with klen, band or the timeline.  Read at run time: one captured graph serves every set of weights.  Behind tlsup, for the same reason
+    const float* kbias;
 };
 constexpr float TL_OFF = -1e30f;   // stored bias of a zero weight (never added to a score: the validity select takes it)
 constexpr int TL_MAXS = 16;        // prompts of a timeline

@@ -143,6 +143,23 @@ class MaskDiT:
         arr = C.cast(C.c_void_p(w.data_ptr()), C.POINTER(C.c_float))   # (the call reads the host tensor and waits: `w` outlives it)
         _lib.check(self.lib.ezdit_set_context_weights(self._h, arr, int(w.shape[1]), st))
 
+    def set_context_token_weights(self, weights, stream=None):
+        """Prompt emphasis (ezdit_set_context_token_weights): ``weights`` [B, Lc] > 0, the weight of context token j of batch row b in every block's
+        cross-attention (a weight n acts like the token repeated n times); values at masked tokens are not read.  None switches it off, and so does a table whose
+        rows are uniform.  After prepare_context, whose mask it is checked against."""
+        st = _stream() if stream is None else stream
+        if weights is None:
+            _lib.check(self.lib.ezdit_set_context_token_weights(self._h, None, 0, st))
+            return
+        w = torch.as_tensor(weights, dtype=torch.float32).cpu().contiguous()
+        if w.dim() != 2:
+            raise ValueError(f'context token weights must be [B, Lc], got {tuple(w.shape)}')
+        B, L, Lc, _ = self._ws_key or (0, 0, 0, 0)
+        if w.shape[0] != B or w.shape[1] != Lc:
+            raise ValueError(f'context token weights {tuple(w.shape)} for a binding of B = {B} rows and Lc = {Lc} tokens')
+        arr = C.cast(C.c_void_p(w.data_ptr()), C.POINTER(C.c_float))   # (the call reads the host tensor and waits: `w` outlives it)
+        _lib.check(self.lib.ezdit_set_context_token_weights(self._h, arr, int(w.shape[0]), st))
+
     def set_attention_window(self, frames):
         """Sliding-window self-attention (ezdit_set_attention_window): every frame attends to the frames within ``frames`` of it, on either side.  None or 0
         switches it off.  Stays with the model until it is changed; a window that covers the bound row runs the plain kernels, bit for bit."""
@@ -163,7 +180,7 @@ class MaskDiT:
         return t if shape is None else t[:int(np.prod(shape))].reshape(shape)
 
     # -- forward ------------------------------------------------------------------------------------
-    def _run(self, x, timesteps, context, context_mask, gt, gt_mask, controlnet_skips, in_ch, x_lens=None, context_weights=None):
+    def _run(self, x, timesteps, context, context_mask, gt, gt_mask, controlnet_skips, in_ch, x_lens=None, context_weights=None, context_token_weights=None):
         B, _, L = x.shape
         Lc = context.shape[1]
         if context.shape[0] != B:
@@ -179,6 +196,8 @@ class MaskDiT:
         self.set_lengths(x_lens)
         if context_weights is not None:   # (prepare_context above switched an earlier call's table off)
             self.set_context_weights(context_weights)
+        if context_token_weights is not None:
+            self.set_context_token_weights(context_token_weights)
         x = x.to(self.device, torch.float32).contiguous()
         gt_d = None if gt is None else gt.to(self.device, torch.float32).contiguous()
         gm_d = None if gt_mask is None else gt_mask.to(self.device).expand(B, self.C, L).to(torch.uint8).contiguous()
@@ -194,13 +213,16 @@ class MaskDiT:
         return out
 
     def forward(self, x, timesteps, context, x_mask=None, context_mask=None, cls_token=None, gt=None,
-                mae_mask_infer=None, forward_model=True, x_lens=None, context_weights=None):
+                mae_mask_infer=None, forward_model=True, x_lens=None, context_weights=None, context_token_weights=None):
         """``x_lens`` (list / int tensor [B]): x, gt and mae_mask_infer are padded to L = max(x_lens) frames, row b is valid on [0, x_lens[b]); its
         valid output frames are what a call with that row alone computes, output frames beyond are exactly 0, and whatever the padded
         region of the inputs holds is ignored (include/ezdit.h ezdit_set_lengths).
 
         ``context_weights`` [B, S, L] (prompt timeline, include/ezdit.h ezdit_set_context_weights): ``context`` is [B, 128 S, Cctx], S prompts of 128 rows
-        each (sampler.timeline_context builds it), and frame i of row b weights prompt s by context_weights[b, s, i] in every block's cross-attention."""
+        each (sampler.timeline_context builds it), and frame i of row b weights prompt s by context_weights[b, s, i] in every block's cross-attention.
+
+        ``context_token_weights`` [B, Lc] (prompt emphasis, include/ezdit.h ezdit_set_context_token_weights): token j of row b weighs context_token_weights[b, j] > 0
+        in every block's cross-attention; values at masked tokens are not read.  Not together with ``context_weights``."""
         if x_mask is not None:
             raise NotImplementedError(_X_MASK_MSG)
         if cls_token is not None:
@@ -212,7 +234,8 @@ class MaskDiT:
             me = self._mask_embed.view(1, -1, 1).to(x.device).expand_as(x)
             g = me if gt is None else torch.where(mae_mask_infer.expand_as(gt), me, gt)
             return torch.cat([x, g, mae_mask[:, 0:1, :]], dim=1), mae_mask
-        pred = self._run(x, timesteps, context, context_mask, gt, mae_mask_infer, None, in_ch=self.C, x_lens=x_lens, context_weights=context_weights)
+        pred = self._run(x, timesteps, context, context_mask, gt, mae_mask_infer, None, in_ch=self.C, x_lens=x_lens, context_weights=context_weights,
+                         context_token_weights=context_token_weights)
         return pred, mae_mask
 
     __call__ = forward

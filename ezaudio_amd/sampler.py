@@ -131,7 +131,7 @@ class LatentSampler:
     def prepare(self, text, text_mask, uncond_text, uncond_mask, init_noise, step_noises, guidance_scale,
                 guidance_rescale, ddim_steps, eta, gt=None, gt_mask=None, controlnet=None, condition=None,
                 conditioning_scale=1.0, lengths=None, init_latents=None, start_steps=None, latent_scale=1.0, latent_shift=0.0, context_weights=None, compose_text=None, compose_mask=None,
-                compose_weights=None, canvas=None, canvas_loop=None, solver='ddim'):
+                compose_weights=None, token_weights=None, uncond_token_weights=None, compose_token_weights=None, canvas=None, canvas_loop=None, solver='ddim'):
         """``lengths`` (list of P ints): init_noise / step_noises / gt / gt_mask are padded to L = max(lengths) frames and sample p is valid on
         [0, lengths[p]) -- its final latent is what a call with that sample alone at its own length gives, zero beyond (include/ezdit.h
         ezdit_set_lengths).  With a ControlNet the table goes to the attached pair (ezdit_sampler_set_pair_lengths) and ``condition`` is
@@ -177,8 +177,19 @@ class LatentSampler:
         w[p, 0] > 0; the others are any finite value, negative ones steer away from their prompt, and a weight of exactly 0 drops its condition (its row is
         computed and not read).  The batch is built here as [text | compose_text[:, 0] | ... | uncond_text]; set_compose_weights() replaces the values of a
         prepared call without a re-capture.  It combines with lengths, per-sample settings, ``solver``, gt / gt_mask, init_latents and an attention window; not with
-        a ControlNet, a canvas, a loop or a timeline, and it needs guidance.  One condition with weight 1 is the plain call: nothing new is called, the same bits."""
+        a ControlNet, a canvas, a loop or a timeline, and it needs guidance.  One condition with weight 1 is the plain call: nothing new is called, the same bits.
+
+        ``token_weights`` [P, Lt] (prompt emphasis, include/ezdit.h ezdit_set_context_token_weights): token j of sample p's prompt weighs token_weights[p, j] > 0 in every
+        block's cross-attention, as if it stood there that many times (parse_emphasis() / emphasis_weights() make such weights from '(words:1.6)' markup).
+        ``uncond_token_weights`` [P, Lt] does the same for the unconditional rows (default: 1) and ``compose_token_weights`` [P, K-1, Lt] for the extra conditions of
+        ``compose_text``.  The [B, Lc] table is built here in the layout of the batch; values at masked tokens are not read.  It combines with composed guidance, a canvas
+        or loop, lengths, init_latents and ``solver``; not with a ControlNet or a timeline.  Weights that are equal within every row call nothing new: the same bits."""
         check_solver(solver, eta)
+        if token_weights is not None or uncond_token_weights is not None or compose_token_weights is not None:
+            if controlnet is not None or context_weights is not None:
+                raise ValueError('token weights do not combine with a ControlNet or a prompt timeline')
+            if text.dim() != 3:
+                raise ValueError(f'token weights with text {tuple(text.shape)}: expected [P, Lt, Cctx]')
         compose = None
         if compose_weights is not None or compose_text is not None or compose_mask is not None:
             if compose_weights is None:
@@ -285,6 +296,28 @@ class LatentSampler:
         else:
             ctx, msk = text, text_mask
         B = ctx.shape[0]
+        tok_w = None
+        if token_weights is not None or uncond_token_weights is not None or compose_token_weights is not None:
+            # one row of weights per batch row, in the order the context was built in above; a part that was not given weighs 1
+            def _part(wt, shape, name):
+                if wt is None:
+                    return torch.ones(shape, dtype=torch.float32)
+                wt = torch.as_tensor(wt, dtype=torch.float32).cpu()
+                if tuple(wt.shape) != tuple(shape):
+                    raise ValueError(f'{name} {tuple(wt.shape)}: expected {tuple(shape)}')
+                return wt
+            Pt, Lt = text.shape[0], text.shape[1]
+            parts = [_part(token_weights, (Pt, Lt), 'token_weights')]
+            if compose is not None:
+                cwt = _part(compose_token_weights, (Pt, compose.shape[1] - 1, Lt), 'compose_token_weights')
+                parts += [cwt[:, k] for k in range(compose.shape[1] - 1)]
+            elif compose_token_weights is not None:
+                raise ValueError('compose_token_weights without composed guidance')
+            if compose is not None or use_cfg:
+                parts.append(_part(uncond_token_weights, (uncond_text.shape[0], Lt), 'uncond_token_weights'))
+            elif uncond_token_weights is not None:
+                raise ValueError('uncond_token_weights without guidance: there is no unconditional row')
+            tok_w = torch.cat(parts, dim=0).contiguous()
         self.latents = init_noise.to(dev, torch.float32).contiguous().clone()
         self.noise = None if (eta <= 0 or step_noises is None) else step_noises.to(dev, torch.float32).contiguous()
         if eta > 0 and self.noise is None:
@@ -335,6 +368,8 @@ class LatentSampler:
                     one[:, 0] = 1.0
                     wt = torch.cat([wt, one], dim=0)
                 u.set_context_weights(wt, st)
+            if tok_w is not None:   # behind the context, whose mask the table is checked against (prepare_context switched an earlier call's off)
+                u.set_context_token_weights(tok_w, st)
             arr = (_lib.EzditDdimCoef * ddim_steps)(*[_lib.EzditDdimCoef(*c) for c in coefs])
             if compose is not None:
                 n_cond = compose.shape[1]
@@ -755,6 +790,91 @@ def compose_entries(compose, n_prompts):
     return lists, W
 
 
+EMPHASIS_MIN, EMPHASIS_MAX = 2.0 ** -10, 2.0 ** 10      # a span's weight, products of nested groups included
+
+
+def parse_emphasis(text):
+    """Prompt emphasis markup -> (clean_text, spans).  A group is ``(words:1.6)``: a parenthesis group that ends in ``:number``.  Groups nest and their weights
+    multiply; ``\\(`` and ``\\)`` are literal parentheses; parentheses without ``:number`` are ordinary text and stay; ``(words:0)`` removes the words from the text.
+    spans is a list of (start, end, weight) over characters of clean_text, one per group that is left, inner groups carrying the product.  ValueError: a group that
+    is not closed (an opening parenthesis that a later ``:number)`` would have to close), or a weight outside [2^-10, 2^10] (0 aside).  ``:number)`` is markup wherever
+    it stands: ordinary text that holds it outside a group, such as 'at 3:30)', raises as unbalanced -- write the parenthesis as ``\\)``."""
+    import re
+    num = re.compile(r':\s*([0-9]*\.?[0-9]+(?:[eE][-+]?[0-9]+)?)\s*\)')
+    out = []           # characters of the clean text
+    stack = []         # open parentheses: index into `out` of the '(' that was emitted
+    spans = []         # (start, end, weight, depth-independent): closed groups, in clean-text coordinates
+    i, n = 0, len(text)
+    squeeze = False
+    while i < n:
+        ch = text[i]
+        if ch == '\\' and i + 1 < n and text[i + 1] in '()':
+            out.append(text[i + 1]); i += 2
+            continue
+        if ch == '(':
+            stack.append(len(out)); out.append('('); i += 1
+            continue
+        m = num.match(text, i) if ch == ':' else None
+        if m is not None and stack:
+            w = float(m.group(1))
+            start = stack.pop()
+            del out[start]      # the group's parentheses are markup
+            spans = [(a - (a > start), b - (b > start), ww) for a, b, ww in spans]
+            end = len(out)
+            if w == 0.0:       # the group leaves the text, and the spans inside it with it
+                del out[start:end]
+                spans = [(a, b, ww) for a, b, ww in spans if not (a >= start and b <= end and a < end)]
+                squeeze = True      # (the space behind the group goes when one stands in front of it, or nothing does)
+            else:
+                spans = [(a, b, ww * w) if (a >= start and b <= end) else (a, b, ww) for a, b, ww in spans]
+                spans.append((start, end, w))
+            i = m.end()
+            continue
+        if m is not None and not stack:
+            raise ValueError(f'unbalanced emphasis markup in {text!r}: ":{m.group(1)})" closes no group')
+        if ch == ')':
+            if stack:
+                stack.pop()      # a plain parenthesis pair: ordinary text
+            out.append(')'); i += 1
+            continue
+        if ch == ' ' and squeeze and (not out or out[-1] == ' '):
+            i += 1
+            continue
+        squeeze = False
+        out.append(ch); i += 1
+    clean = ''.join(out).rstrip()      # (an opening parenthesis that no ':number)' closes is ordinary text)
+    res = []
+    for a, b, w in spans:
+        # nested groups: the inner span carries the product already; an outer span covers the whole group, so per-token weights take the innermost span's weight
+        if not (EMPHASIS_MIN <= w <= EMPHASIS_MAX):
+            raise ValueError(f'emphasis weight {w:g} in {text!r} outside [2^-10, 2^10]')
+        b = min(b, len(clean))
+        if b > a:
+            res.append((a, b, w))
+    return clean, sorted(res, key=lambda t: (t[0], -t[1]))
+
+
+def emphasis_weights(tokenizer, clean_text, spans, max_length):
+    """Per-token weights [Lt] (a list of max_length floats) of ``clean_text`` under ``spans`` of parse_emphasis().  The tokenizer need not give offsets: a span boundary at
+    character p maps to token index len(tokenizer(clean_text[:p], add_special_tokens=False).input_ids), and those ids must be a prefix of the ids of the whole text
+    (spans cover whole words), otherwise ValueError naming the span.  A token takes the weight of the innermost span that holds it; tokens outside every span, EOS
+    and the padding weigh 1.  Truncation at max_length truncates the weights."""
+    ids = list(tokenizer(clean_text, add_special_tokens=False).input_ids)
+    w = [1.0] * len(ids)
+
+    def at(p, span):
+        pre = list(tokenizer(clean_text[:p], add_special_tokens=False).input_ids)
+        if pre != ids[:len(pre)]:
+            raise ValueError(f'emphasis span {clean_text[span[0]:span[1]]!r} (characters {span[0]}:{span[1]}) does not fall on token boundaries of {clean_text!r}: spans cover whole words')
+        return len(pre)
+    for sp in sorted(spans, key=lambda t: t[1] - t[0], reverse=True):      # outer spans first: inner ones overwrite with their product
+        a, b = at(sp[0], sp), at(sp[1], sp)
+        for j in range(a, b):
+            w[j] = float(sp[2])
+    w = (w + [1.0])[:max_length]      # EOS
+    return w + [1.0] * (max_length - len(w))
+
+
 @torch.no_grad()
 def inference_controlnet(autoencoder, unet, controlnet, gt, gt_mask, condition, tokenizer, text_encoder, params,
                          noise_scheduler, text_raw, neg_text=None, audio_frames=500, guidance_scale=3,
@@ -772,9 +892,15 @@ def inference_controlnet(autoencoder, unet, controlnet, gt, gt_mask, condition, 
 def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, noise_scheduler, text_raw,
               neg_text=None, audio_frames=500, guidance_scale=3, guidance_rescale=0.0, ddim_steps=50, eta=1,
               random_seed=2024, device='cuda', use_graph=True, controlnet=None, condition=None, conditioning_scale=1.0,
-              first_index=None, init_latents=None, strength=None, attention_window=None, prompt_weights=None, compose=None, canvas_loop=None, decode_context=None, canvas_offsets=None, canvas_ramp=None,
+              first_index=None, init_latents=None, strength=None, attention_window=None, prompt_weights=None, compose=None, emphasis=False, token_weights=None, canvas_loop=None, decode_context=None, canvas_offsets=None, canvas_ramp=None,
               solver='ddim'):
     """Same signature and semantics as the reference's ``inference`` (src/inference.py:26-107).
+
+    Extension (prompt emphasis): ``emphasis=True`` parses '(words:1.6)' markup (parse_emphasis) in every prompt of the call -- ``text_raw``, the extra prompts of
+    ``compose`` and ``neg_text`` -- the text encoder sees the clean text, and token j of a prompt weighs its group's weight in every block's cross-attention
+    (include/ezdit.h ezdit_set_context_token_weights); the table is passed on only if some weight is not 1.  ``token_weights`` [N, max_length] gives the primary
+    prompts' weights directly.  ValueError with a prompt timeline or a ControlNet.  On a call sharded over ranks each rank parses its own prompts.  The default
+    leaves every prompt verbatim.  Audio quality on the real checkpoints is unmeasured.
 
     Extension (composed guidance): ``compose`` gives a prompt further prompts with weights: for one prompt a list of (text, weight) pairs, for several one such
     list (or None) per prompt.  Every prompt is guided against the shared negative prompt with its own weight, v = u + guidance_scale ((c_0 - u) + sum_k w_k (c_k - u));
@@ -842,7 +968,7 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
             return inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, noise_scheduler, text_raw, neg_text, audio_frames, guidance_scale,
                              guidance_rescale, ddim_steps, eta, random_seed, device, use_graph, controlnet, condition, conditioning_scale, first_index=first_index,
                              init_latents=init_latents, strength=strength, canvas_loop=canvas_loop, decode_context=decode_context, canvas_offsets=canvas_offsets,
-                             canvas_ramp=canvas_ramp, solver=solver, prompt_weights=prompt_weights, compose=compose)
+                             canvas_ramp=canvas_ramp, solver=solver, prompt_weights=prompt_weights, compose=compose, emphasis=emphasis, token_weights=token_weights)
         finally:
             for m, prev in zip(models, previous):
                 m.set_attention_window(prev)
@@ -930,7 +1056,8 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
             wav = inference(autoencoder, unet, cut(gt), cut(gt_mask), tokenizer, text_encoder, params, noise_scheduler,
                             list(text_raw[s:e]), neg_all[s:e], audio_frames if frames is None else frames[s:e], pp(guidance_scale), pp(guidance_rescale),
                             ddim_steps, pp(eta), pp(random_seed), device, use_graph, controlnet, cut(condition, 2), pp(conditioning_scale), first_index=s,
-                            solver=solver, init_latents=cut(init_latents), strength=pp(strength))
+                            solver=solver, init_latents=cut(init_latents), strength=pp(strength), emphasis=emphasis,
+                            token_weights=None if token_weights is None else torch.as_tensor(token_weights)[s:e])
             if frames is None:
                 return wav
             out = torch.zeros(wav.shape[0], wav.shape[1], t_all, dtype=wav.dtype, device=wav.device)
@@ -939,8 +1066,27 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
         return sample_sharded(local, n_all)
     first_index = first_index or 0
     n_prompts = len(text_raw)
+    if (emphasis or token_weights is not None) and (timeline is not None or controlnet is not None):
+        raise ValueError('prompt emphasis does not combine with a prompt timeline or a ControlNet')
+    if emphasis and token_weights is not None:
+        raise ValueError('emphasis=True and token_weights: give one')
+    emph = None
     if tokenizer is not None:
         max_len = params['text_encoder']['max_length']
+        if emphasis:      # every prompt of the call: the primaries and the extra conditions (text_raw holds both by now), and the negative prompts
+            parsed = [parse_emphasis(t) for t in text_raw]
+            text_raw = [c for c, _ in parsed]
+            w_text = torch.tensor([emphasis_weights(tokenizer, c, sp, max_len) for c, sp in parsed], dtype=torch.float32)
+            neg_parsed = [parse_emphasis(t) for t in neg_text]
+            neg_text = [c for c, _ in neg_parsed]
+            w_neg = torch.tensor([emphasis_weights(tokenizer, c, sp, max_len) for c, sp in neg_parsed], dtype=torch.float32)
+            emph = (w_text, w_neg)
+        elif token_weights is not None:
+            w_text = torch.as_tensor(token_weights, dtype=torch.float32).cpu()
+            n_primary = composed[0] if composed is not None else n_prompts
+            if tuple(w_text.shape) != (n_primary, max_len):
+                raise ValueError(f'token_weights {tuple(w_text.shape)}: expected [{n_primary}, {max_len}]')
+            emph = (torch.cat([w_text, torch.ones(n_prompts - n_primary, max_len)]), torch.ones(len(neg_text), max_len))
         tb = tokenizer(text_raw, max_length=max_len, padding="max_length", truncation=True, return_tensors="pt")
         text, text_mask = tb.input_ids.to(device), tb.attention_mask.to(device).bool()
         text = text_encoder(input_ids=text, attention_mask=text_mask).last_hidden_state
@@ -987,6 +1133,14 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
         kw['solver'] = solver
     if timeline is not None:
         kw['context_weights'] = timeline[1]
+    if emph is not None and (bool((emph[0] != 1).any()) or bool((emph[1] != 1).any())):      # (all weights 1: the plain call, no table)
+        w_text, w_neg = emph
+        n_primary = composed[0] if composed is not None else n_prompts
+        kw['token_weights'] = w_text[:n_primary]
+        if composed is not None:
+            kw['compose_token_weights'] = w_text[n_primary:].reshape(composed[1].shape[1] - 1, n_primary, -1).transpose(0, 1).contiguous()
+        if bool((w_neg != 1).any()):
+            kw['uncond_token_weights'] = w_neg.expand(n_primary, -1) if w_neg.shape[0] == 1 else w_neg
     if composed is not None:
         kw.update(compose_text=comp_text.float(), compose_mask=comp_mask, compose_weights=composed[1])
     if canvas_loop is not None:

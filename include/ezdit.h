@@ -132,6 +132,8 @@ int    ezdit_bind_workspace(ezdit_handle* h, void* dev_ws, size_t bytes, int B, 
  *       ControlNet scales (.._set_cn_scales)      off <-> on                          ezdit_bind_workspace, ezdit_sampler_attach_controlnet,
  *                                                                                       ezdit_destroy of the ControlNet
  *       context weights (ezdit_set_context_weights) off <-> on                        ezdit_bind_workspace, ezdit_prepare_context
+ *       token weights                             off <-> on (a table of equal        ezdit_bind_workspace, ezdit_prepare_context
+ *         (ezdit_set_context_token_weights)         weights per row is off)
  *       sample settings (.._set_sample_params)    off <-> on                          ezdit_bind_workspace, ezdit_sampler_begin
  *       multistep (.._set_multistep)              off <-> on, another history buffer  ezdit_bind_workspace, ezdit_sampler_begin
  *       start (.._set_start)                      off <-> on (also moves the step     ezdit_bind_workspace, ezdit_sampler_begin
@@ -676,6 +678,37 @@ int ezdit_test_cross_attention_timeline(const void* dev_xu, int ldu, const void*
                                         const void* dev_k, const void* dev_v, const uint8_t* dev_kmask, void* dev_out, int ldo, int B, int b0, int H, int dh, int Lq, int Lk,
                                         int Lqp, int Lkp, const void* dev_zstat_in, long zs_stride, int zparts, int zD, int zw, const float* dev_zG, const float* dev_zC,
                                         float zeps, int xk2, int qtile, int xcd_map, const float* weights, int S, ezdit_stream stream);
+
+/* ---- Prompt emphasis: per-token weights as a key bias in cross-attention ------------------------------------------------------------------------------------
+ * Every context token j of batch row b carries a weight w_bj > 0 (HOST, [B][Lc], natural weights; n = B rows) and, with V_b the valid keys of the row's mask,
+ *     out_i = sum_{j in V_b} w_bj exp(q_i k_j / sqrt(dh)) v_j  /  sum_{j in V_b} w_bj exp(q_i k_j / sqrt(dh))
+ * -- attention with the bias ln w_bj on the scores of key j, the same in every block and head.  An integer weight n is exactly that token's context row repeated n
+ * times.  V is untouched, and so are K / V of ezdit_prepare_context: the table costs nothing per call.  Only the ratios within a row matter: the table stores
+ * fp32(log2(w_bj / max_{j in V_b} w_bj)) (computed in fp64; [B][Lcp], 0 at masked and padding keys).  The mask alone decides validity: the values of `weights` at masked keys
+ * are not read, and dropping a token is the mask's business (a weight of 0 is refused).  Applied inside the cross-attention launch of every block (csrc/attn.hip KW):
+ * the launch count of a step does not change.  A single-key row (the unconditional row of classifier-free guidance) stays exact: softmax over one key is 1 whatever its weight.
+ * A run-time table of the step (contract above), bind-scoped; it serves ezdit_forward and the sampler step alike, with composed guidance, the canvas and the ring, length
+ * tables, the start table and the multistep solver.  Call it after ezdit_prepare_context (the weights are checked against its key mask; a new ezdit_prepare_context switches
+ * the table off).  A table in which every row's valid weights are equal ("all weights 1" included) is OFF: the step runs the plain kernels, bit for bit the call that
+ * never set it.  weights == NULL switches it off.
+ * EZDIT_E_INVALID: n != B; a valid key's weight that is not finite or <= 0; a row whose largest and smallest valid weights differ by more than 2^20.
+ * EZDIT_E_UNSUPPORTED: a ControlNet handle or a backbone with a ControlNet attached (its blocks have cross-attention of their own; ezdit_sampler_attach_controlnet refuses
+ * likewise while the table is on); the prompt timeline being on (ezdit_set_context_weights refuses likewise while this table is on); a bound shape whose cross-attention
+ * does not run an 8-wave form of the kernel (Lc padded to a multiple of 128 and at most 512 workgroups of 64 queries): that one is reported by ezdit_forward /
+ * ezdit_sampler_run, from the launcher's own check, while the table is on.  EZDIT_E_STATE: no prepared context.
+ * Audio quality on the released checkpoints is unmeasured: how strongly a weight of 1.6 is heard.
+ * ABI: additive (version unchanged): one setter and the two hooks below; AttnArgs is internal. */
+int ezdit_set_context_token_weights(ezdit_handle* h, const float* weights, int n, ezdit_stream stream);
+/* unit-test hooks of the emphasis form: the arguments of their ..._timeline twins with natural weights (HOST, [B][Lk], for the launched batch elements) instead of the
+ * timeline's, checked as the setter checks them against the launched rows of dev_kmask, and keep_on: 0 = a table of zeros launches the plain instantiation (as the
+ * setter would), 1 = the KW instantiation whatever the table holds -- that launch must equal the hook without weights bit for bit.  Lkp % 128 == 0 (EZDIT_E_UNSUPPORTED
+ * otherwise); they wait for the launch. */
+int ezdit_test_attention_keyweights(ezdit_handle* h, const void* dev_q, const void* dev_k, const void* dev_v, const uint8_t* dev_kmask, void* dev_out, int B,
+                                    int Lq, int Lk, int Lqp, int Lkp, const float* weights, int keep_on, ezdit_stream stream);
+int ezdit_test_cross_attention_keyweights(const void* dev_xu, int ldu, const void* dev_xw, int ldw, int xw_rows, int xK, const float* dev_qn_w, const float* dev_qn_b,
+                                          const void* dev_k, const void* dev_v, const uint8_t* dev_kmask, void* dev_out, int ldo, int B, int b0, int H, int dh, int Lq, int Lk,
+                                          int Lqp, int Lkp, const void* dev_zstat_in, long zs_stride, int zparts, int zD, int zw, const float* dev_zG, const float* dev_zC,
+                                          float zeps, int xk2, int qtile, int xcd_map, const float* weights, int keep_on, ezdit_stream stream);
 
 /* ---- T5 text encoder (csrc/t5.hip): stands in for transformers' T5EncoderModel in the `text_encoder` slot (api/ezaudio.py:80-82, src/inference.py:42-50) --------
  * Encoder stacks of the flan-t5 / T5 v1.1 family only: gated gelu_new feed-forward, head dim 64, no biases, T5LayerNorm (RMS), the bidirectional
