@@ -13,7 +13,7 @@ import torch
 
 from .config import configs, controlnet_configs, load_yaml_with_includes
 from .denoiser import MaskDiT
-from .sampler import canvas_windows, check_solver, inference, inference_controlnet, loop_windows
+from .sampler import apg_entries, canvas_windows, check_apg, check_solver, inference, inference_controlnet, loop_windows
 from .scheduler import DDIMScheduler
 
 MAX_SEED = np.iinfo(np.int32).max
@@ -96,8 +96,21 @@ class EzAudio:
             raise ValueError(f'attention_window of {attention_window} s is less than one latent frame on either side')
         return radius
 
+    @staticmethod
+    def _apg_kw(apg, text, guidance_scale, guidance_rescale):
+        """`apg` of a request as the keyword inference() takes, refused here -- before anything is encoded -- where the request cannot have it."""
+        if apg is None or apg is False:
+            return {}
+        texts = [text] if isinstance(text, str) else list(text)
+        n = len(texts)
+        if isinstance(apg, (list, tuple)) and (isinstance(text, str) or len(apg) != n):
+            raise ValueError('a list of apg entries needs a list of prompts of the same size: True, a dict, or None, per prompt')
+        per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n   # noqa: E731
+        check_apg(apg_entries(apg, n), [None if t == '' else g for t, g in zip(texts, per(guidance_scale))], per(guidance_rescale))
+        return dict(apg=apg)
+
     def generate_audio(self, text, length=10, guidance_scale=5, guidance_rescale=0.75, ddim_steps=100, eta=1,
-                       random_seed=None, randomize_seed=False, attention_window=None, compose=None, emphasis=False, solver='ddim'):
+                       random_seed=None, randomize_seed=False, attention_window=None, compose=None, emphasis=False, apg=None, solver='ddim'):
         """`emphasis=True` reads '(words:1.6)' markup in the prompts (sampler.parse_emphasis: per-token weights in cross-attention; the default leaves every prompt
         verbatim; audio quality on the real checkpoints is unmeasured) -- here and on editing_audio, audio_to_audio, generate_long_audio and generate_loop.
         api/ezaudio.py:101-130.  `text` may also be a list of prompts (batched extension): the result is then
@@ -116,8 +129,16 @@ class EzAudio:
         must be there, and less of that one": compose=[('distant thunder', 0.8), ('wind', -0.5)].  `text` has weight 1 and is the reference of the guidance
         rescale; a negative weight steers away from its prompt.  With a list of prompts, one such list (or None) per prompt.  The batch grows to K + 1 rows per
         prompt.  ValueError for a prompt list of another size, a non-finite weight, more than 7 extra prompts, or a call without guidance (text '').  No extra
-        prompt is the plain call, bit for bit.  Audio quality on the real checkpoints -- which weights sound like "both" or "less of" -- is unmeasured."""
+        prompt is the plain call, bit for bit.  Audio quality on the real checkpoints -- which weights sound like "both" or "less of" -- is unmeasured.
+        `apg` (adaptive projected guidance, Sadat et al.; also on editing_audio and audio_to_audio): guidance that does not over-drive the latent at the scales
+        that make a prompt stick.  apg=True, or apg=dict(eta=0.0, norm_threshold=0.0, momentum=-0.5) with any of the three keys; with a list of prompts also one
+        entry (or None) per prompt.  The guidance direction loses its component parallel to the prediction (`eta`: the share that stays), carries `momentum`
+        across steps and is capped at `norm_threshold` (0: no cap).  True means eta 0, momentum -0.5 and NO cap: which cap suits the EzAudio latent is
+        unmeasured, so none is invented.  The guidance rescale is not applied to it: pass guidance_rescale=0 with apg (the default 0.75 raises), or a list with 0
+        for the prompts that take it.  ValueError also with `compose`, for text '' (no guidance), an unknown key, a non-finite value or a negative cap.
+        Which settings sound best on the real checkpoints is unmeasured."""
         neg_text = None
+        apg_kw = self._apg_kw(apg, text, guidance_scale, guidance_rescale)
         if compose is not None and not isinstance(text, str) and len(compose) != len(text):
             raise ValueError('compose for a list of prompts is a list of the same size: one list of (text, weight) pairs, or None, per prompt')
         check_solver(solver, eta)
@@ -147,7 +168,7 @@ class EzAudio:
             random_seed = random.randint(0, MAX_SEED) if isinstance(text, str) else [random.randint(0, MAX_SEED) for _ in text]
         pred = inference(self.autoencoder, self.unet, gt, gt_mask, self.tokenizer, self.text_encoder, self.params,
                          self.noise_scheduler, text, neg_text, length, guidance_scale, guidance_rescale, ddim_steps,
-                         eta, random_seed, self.device, solver=solver, attention_window=radius, **({} if compose is None else dict(compose=compose)), **({} if not emphasis else dict(emphasis=True)))
+                         eta, random_seed, self.device, solver=solver, attention_window=radius, **({} if compose is None else dict(compose=compose)), **({} if not emphasis else dict(emphasis=True)), **apg_kw)
         pred = pred.cpu().numpy()
         if per_prompt:
             ratio = self.params['autoencoder']['sr'] // latent_sr
@@ -288,8 +309,8 @@ class EzAudio:
                     chunk_length=end_idx - start_idx)
 
     def editing_audio(self, text, boundary, gt_file, mask_start, mask_length, guidance_scale=3.5, guidance_rescale=0,
-                      ddim_steps=100, eta=1, random_seed=None, randomize_seed=False, attention_window=None, emphasis=False, solver='ddim'):
-        """api/ezaudio.py:132-207 (crop / pad / mask bookkeeping on the host, sampling on the GPU).  `solver` and `attention_window` (seconds; quality on the real
+                      ddim_steps=100, eta=1, random_seed=None, randomize_seed=False, attention_window=None, emphasis=False, apg=None, solver='ddim'):
+        """api/ezaudio.py:132-207 (crop / pad / mask bookkeeping on the host, sampling on the GPU).  `solver`, `apg` and `attention_window` (seconds; quality on the real
         checkpoints unmeasured) as in generate_audio.  `gt_file` is a path or a
         1-D numpy waveform at the model's sample rate.
 
@@ -302,9 +323,10 @@ class EzAudio:
         `latent_lengths` (this package's Autoencoder does)."""
         check_solver(solver, eta)
         radius = self._window_radius(attention_window)
+        apg_kw = self._apg_kw(apg, text, guidance_scale, guidance_rescale)
         if not isinstance(text, str):
             return self._editing_audio_batch(list(text), boundary, gt_file, mask_start, mask_length, guidance_scale, guidance_rescale, ddim_steps, eta,
-                                             random_seed, randomize_seed, solver, radius, emphasis)
+                                             random_seed, randomize_seed, solver, radius, emphasis, apg_kw)
         for name, v in (('gt_file', gt_file), ('boundary', boundary), ('mask_start', mask_start), ('mask_length', mask_length),
                         ('guidance_scale', guidance_scale), ('guidance_rescale', guidance_rescale), ('eta', eta), ('random_seed', random_seed)):
             if isinstance(v, (list, tuple)):
@@ -328,7 +350,7 @@ class EzAudio:
             random_seed = random.randint(0, MAX_SEED)
         pred = inference(self.autoencoder, self.unet, gt_latent, gt_mask, self.tokenizer, self.text_encoder,
                          self.params, self.noise_scheduler, text, neg_text, L, guidance_scale, guidance_rescale,
-                         ddim_steps, eta, random_seed, self.device, solver=solver, attention_window=radius, **({} if not emphasis else dict(emphasis=True)))
+                         ddim_steps, eta, random_seed, self.device, solver=solver, attention_window=radius, **({} if not emphasis else dict(emphasis=True)), **apg_kw)
         pred = pred.cpu().numpy().squeeze(0).squeeze(0)
         pred = pred[:round(req['chunk_length'] * sr)]
         output_audio = req['output_audio']
@@ -336,7 +358,7 @@ class EzAudio:
         return sr, output_audio
 
     def _editing_audio_batch(self, text, boundary, gt_file, mask_start, mask_length, guidance_scale, guidance_rescale, ddim_steps, eta, random_seed,
-                             randomize_seed, solver, radius=None, emphasis=False):
+                             randomize_seed, solver, radius=None, emphasis=False, apg_kw=None):
         """editing_audio for a list of prompts: N crops in one ragged encode, one sampler call at per-request latent lengths, one ragged decode."""
         n = len(text)
         if isinstance(ddim_steps, (list, tuple)):
@@ -375,7 +397,7 @@ class EzAudio:
             random_seed = [random.randint(0, MAX_SEED) for _ in text]
         pred = inference(self.autoencoder, self.unet, gt_latent, gt_mask, self.tokenizer, self.text_encoder,
                          self.params, self.noise_scheduler, text, None, frames, guidance_scale, guidance_rescale,
-                         ddim_steps, eta, random_seed, self.device, solver=solver, attention_window=radius, **({} if not emphasis else dict(emphasis=True)))
+                         ddim_steps, eta, random_seed, self.device, solver=solver, attention_window=radius, **({} if not emphasis else dict(emphasis=True)), **(apg_kw or {}))
         pred = pred.cpu().numpy()
         outs = []
         for i, r in enumerate(reqs):
@@ -385,11 +407,11 @@ class EzAudio:
         return sr, outs
 
     def audio_to_audio(self, text, audio, strength=0.5, guidance_scale=5, guidance_rescale=0.75, ddim_steps=100, eta=1, random_seed=None,
-                       randomize_seed=False, attention_window=None, solver='ddim', emphasis=False):
+                       randomize_seed=False, attention_window=None, solver='ddim', emphasis=False, apg=None):
         """Re-render a recording under a prompt, staying as close to it as `strength` says (not in the reference: the standard "start the sampler from the
         noised clip" of image-to-image, SDEdit).  `audio` is a path or a 1-D numpy waveform at the model's sample rate, peak-normalised and encoded whole;
         `strength` in (0, 1] is the share of the `ddim_steps` that are run (scheduler.start_step): 1 starts from pure noise, the plain generate_audio of the
-        clip's length, small values change little.  Returns (sr, waveform) of latent_frames * ratio samples.  `solver` as in generate_audio.
+        clip's length, small values change little.  Returns (sr, waveform) of latent_frames * ratio samples.  `solver` and `apg` as in generate_audio.
 
         Batched extension: `text` may be a list of prompts, one request per entry in ONE ragged encode, ONE sampler call and ONE ragged decode; the result is
         then (sr, [one 1-D array per request]).  `audio` is then a list of the same size, or one clip shared by all requests; `strength`, `guidance_scale`,
@@ -402,6 +424,7 @@ class EzAudio:
         Audio quality versus strength, and of windowed sampling, on the real checkpoints is unmeasured."""
         check_solver(solver, eta)
         radius = self._window_radius(attention_window)
+        apg_kw = self._apg_kw(apg, text, guidance_scale, guidance_rescale)
         if isinstance(ddim_steps, (list, tuple)):
             raise ValueError('ddim_steps must be one value per call: per-prompt step counts are not supported')
         sr = self.params['autoencoder']['sr']
@@ -440,7 +463,7 @@ class EzAudio:
             L = latent.shape[-1]
             pred = inference(self.autoencoder, self.unet, None, None, self.tokenizer, self.text_encoder, self.params, self.noise_scheduler, text, None, L,
                              guidance_scale, guidance_rescale, ddim_steps, eta, random_seed, self.device, solver=solver, init_latents=latent,
-                             strength=strength, attention_window=radius, **({} if not emphasis else dict(emphasis=True)))
+                             strength=strength, attention_window=radius, **({} if not emphasis else dict(emphasis=True)), **apg_kw)
             return sr, pred.cpu().numpy().squeeze(0).squeeze(0)
         text = list(text)
         if '' in text:
@@ -456,7 +479,7 @@ class EzAudio:
         frames = [int(v) for v in self.autoencoder.latent_lengths(samples)]
         pred = inference(self.autoencoder, self.unet, None, None, self.tokenizer, self.text_encoder, self.params, self.noise_scheduler, text, None, frames,
                          guidance_scale, guidance_rescale, ddim_steps, eta, random_seed, self.device, solver=solver, init_latents=latent,
-                         strength=per(strength), attention_window=radius, **({} if not emphasis else dict(emphasis=True)))
+                         strength=per(strength), attention_window=radius, **({} if not emphasis else dict(emphasis=True)), **apg_kw)
         pred = pred.cpu().numpy()
         up = pred.shape[-1] // max(frames)                                     # samples per latent frame, as decoded
         return sr, [pred[i, 0, :f * up] for i, f in enumerate(frames)]

@@ -165,6 +165,10 @@ struct ezdit_handle {
     // [c_0 | .. | c_{K-1} | u], B = (cw_K + 1) P, and the last two kernels of the step run their composed instantiations (launch_cfg_compose).  K is a kernel argument
     Table<float> cw;
     int cw_K = 1;
+    // [P][4] (eta_apg, norm_threshold, momentum, on) of adaptive projected guidance (ezdit_sampler_set_apg): the last two kernels of the step run their APG
+    // instantiations (launch_cfg_apg), always both.  The momentum buffer apg_mom is the caller's and a kernel argument, like ms_hist
+    Table<float> apg;
+    float* apg_mom = nullptr;
 
     int launches = 0;
     bool is_cn = false;          // ControlNet variant (cfg.controlnet)
@@ -554,6 +558,7 @@ size_t carve(const ezdit_handle* h, int B, int L, int Lc, int n_slots, std::map<
         add("tlsup", (size_t)B * (Lcp / 128) * 8);       // supports, behind `canvas` for the same reason: B L 4 bytes at one prompt
         add("cw", (size_t)B * sizeof(float));            // weights of composed guidance [P][K], P K < B = (K + 1) P; at the very end for the same reason
         add("kbias", (size_t)B * Lcp * 4);               // prompt emphasis (ezdit_set_context_token_weights): one score bias per context key, behind `cw` for the same reason
+        add("apg", (size_t)B * 4 * sizeof(float));       // adaptive projected guidance (ezdit_sampler_set_apg): [P][4], P <= B; at the very end for the same reason: 16 B bytes
     }
     return off;
 }
@@ -741,6 +746,7 @@ void resolve_workspace(ezdit_handle* h) {
     h->tl.dev = h->buf<float>("tlb"); h->tlsup = h->buf<int2>("tlsup");
     h->cw.dev = h->buf<float>("cw");
     h->tw.dev = h->buf<float>("kbias");
+    h->apg.dev = h->buf<float>("apg");
     p.zstat = h->buf<float2>("zstat"); p.zt_qkv = h->buf<float>("zt_qkv"); p.zt_geglu = h->buf<float>("zt_geglu"); p.zt_q2 = h->buf<float>("zt_q2");
     p.zstat_skip = h->buf<float2>("zstat_skip"); p.zt_skip = h->buf<float>("zt_skip"); p.ucat_z = h->buf<bf16_t>("ucat_z");
     if (h->is_cn) { p.cembed = h->buf<float>("cembed"); p.cnres = h->buf<float>("cnres"); p.skipbf = h->buf<bf16_t>("skipbf"); }
@@ -901,6 +907,7 @@ void reset_call_state(ezdit_handle* h) {
     h->start.set(h, false); h->start_min = 0;
     h->canvas.set(h, false); h->canvas_loop = false;
     h->cw.set(h, false); h->cw_K = 1;
+    h->apg.set(h, false); h->apg_mom = nullptr;
 }
 
 // the values of a composed call's weight table [P][K]: finite, the primary condition's above 0
@@ -1250,6 +1257,7 @@ int ezdit_set_step(ezdit_handle* h, int step, ezdit_stream stream) {
     if (h->start.on && step != h->start_min)
         return fail(EZDIT_E_STATE, "start table: step %d is not the run's first step %d (only a rewind to it keeps every sample's trajectory)", step, h->start_min);
     if (h->coef.on && !h->start.on && step != 0) return fail(EZDIT_E_STATE, "multistep solver: the history is not step %d's (only a rewind to step 0 keeps it right)", step - 1);
+    if (h->apg.on && !h->start.on && step != 0) return fail(EZDIT_E_STATE, "projected guidance: the momentum is not step %d's (only a rewind to step 0 keeps it right)", step - 1);
     launch_set_int(h->p.ints, step, 0, (hipStream_t)stream);
     h->steps_done = step;
     return EZDIT_OK;
@@ -1918,9 +1926,12 @@ static int sampler_step(ezdit_handle* h, hipStream_t st) {
     if (h->cw.on) {   // composed guidance: the same arguments plus the weight table, the composed instantiations
         a.K = h->cw_K; a.cw = h->cw.dev;
         if (launch_cfg_compose(a, h->p.cfgpart, st)) return fail(EZDIT_E_STATE, "composed guidance with K = %d", h->cw_K);
+    } else if (h->apg.on) {   // projected guidance: the same arguments plus the table and the momentum, the APG instantiations, always both launches
+        a.apg = h->apg.dev; a.apg_m = h->apg_mom;
+        if (launch_cfg_apg(a, h->p.cfgpart, st)) return fail(EZDIT_E_STATE, "projected guidance without its momentum buffer");
     } else
     launch_cfg_ddim(a, h->p.cfgpart, st);   // its last kernel also advances the device step counter
-    h->launches += (h->sp.on || (h->gscale > 0.f && h->grescale > 0.f)) ? 2 : 1;
+    h->launches += (h->apg.on || h->sp.on || (h->gscale > 0.f && h->grescale > 0.f)) ? 2 : 1;
     if (h->canvas.on) {   // long-form canvas: the windows' shared frames are averaged on the updated latents (x0_hist stays per window)
         CanvasBlendArgs cb;
         cb.latents = h->latents; cb.off = h->canvas.dev; cb.P = h->P; cb.C = h->C; cb.L = h->L; cb.T = h->canvas_T; cb.ramp = h->canvas_ramp;
@@ -1983,6 +1994,49 @@ int ezdit_cfg_compose_step(const float* pred, float* latents, const float* noise
     a.x0_hist = x0_hist;
     a.K = K; a.cw = weights;
     return hook_launch("k_cfg_*", "composed guidance", [&] { return launch_cfg_compose(a, scratch, (hipStream_t)stream); });
+}
+
+// Adaptive projected guidance (include/ezdit.h, "adaptive projected guidance"): the table [P][4] and the caller's momentum buffer.  Every check comes before the first change of state
+int ezdit_sampler_set_apg(ezdit_handle* h, const float* eta_apg, const float* norm_threshold, const float* momentum, const int32_t* on, int P, float* momentum_buf,
+                          ezdit_stream stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = setter_checks(h, "ezdit_sampler_set_apg", Needs::Begun, st)) return rc;
+    if ((!eta_apg && !norm_threshold && !momentum && !on) || P == 0) {   // off: the plain step again
+        h->apg.set(h, false); h->apg_mom = nullptr;
+        return EZDIT_OK;
+    }
+    if (!eta_apg || !norm_threshold || !momentum || !on) return fail(EZDIT_E_INVALID, "eta_apg, norm_threshold, momentum and on must be given together");
+    if (!momentum_buf) return fail(EZDIT_E_INVALID, "a table without a momentum buffer");
+    if (P != h->P) return fail(EZDIT_E_INVALID, "P = %d, the sampler was begun with P = %d", P, h->P);
+    std::vector<float> v((size_t)P * 4);
+    for (int p = 0; p < P; ++p) {
+        if (!std::isfinite(eta_apg[p]) || !std::isfinite(norm_threshold[p]) || !std::isfinite(momentum[p])) return fail(EZDIT_E_INVALID, "non-finite value of sample %d", p);
+        if (norm_threshold[p] < 0.f) return fail(EZDIT_E_INVALID, "norm_threshold[%d] = %g: a norm is >= 0 (0 = no cap)", p, (double)norm_threshold[p]);
+        if (on[p] && h->B != 2 * P) return fail(EZDIT_E_INVALID, "on[%d] on a sampler begun without CFG rows (B = %d, P = %d)", p, h->B, P);
+        v[p * 4 + 0] = eta_apg[p]; v[p * 4 + 1] = norm_threshold[p]; v[p * 4 + 2] = momentum[p]; v[p * 4 + 3] = on[p] ? 1.f : 0.f;
+    }
+    if (h->cw.on) return fail(EZDIT_E_UNSUPPORTED, "projected guidance with composed guidance (ezdit_sampler_begin_composed)");
+    if (h->canvas.on) return fail(EZDIT_E_UNSUPPORTED, "projected guidance with a canvas (ezdit_sampler_set_canvas, ezdit_sampler_set_canvas_loop)");
+    if (int rc = upload_table(h->apg, std::move(v), st)) return rc;
+    h->apg.set(h, true, momentum_buf != h->apg_mom);   // (another momentum buffer is another kernel argument)
+    h->apg_mom = momentum_buf;
+    return EZDIT_OK;
+}
+
+// The APG form of the per-sample operators (include/ezdit.h): params [P][12] on the device, the momentum rewritten in place
+int ezdit_cfg_apg_step(const float* pred, float* latents, const float* noise, float* x0_hist, float* momentum, const float* params, const int32_t* lens, int L,
+                       int P, int n, float* scratch, ezdit_stream stream) {
+    if (!pred || !latents || !momentum || !params || P < 1 || n < 2) return fail(EZDIT_E_INVALID, "bad argument");
+    if (!scratch) return fail(EZDIT_E_INVALID, "the APG step needs %d scratch floats", P * 256);
+    if (lens && (L < 1 || n % L)) return fail(EZDIT_E_INVALID, "lens given: L = %d must divide n = %d", L, n);
+    if (noise && x0_hist) return fail(EZDIT_E_INVALID, "noise together with a history: the multistep form is deterministic");
+    CfgDdimArgs a = standalone_step(pred, latents, noise, P, n, lens, L);
+    a.sp_g = params; a.sp_g_stride = 12;
+    a.sp_c = params + 2; a.sp_c_stride = 12;
+    a.apg = params + 8; a.apg_stride = 12;
+    a.apg_m = momentum;
+    a.x0_hist = x0_hist;
+    return hook_launch("k_cfg_*", "projected guidance", [&] { return launch_cfg_apg(a, scratch, (hipStream_t)stream); });
 }
 
 int ezdit_sampler_set_multistep(ezdit_handle* h, const float* c_hist, int n_steps, float* x0_hist, ezdit_stream stream) {
@@ -2084,6 +2138,7 @@ static int set_canvas_table(ezdit_handle* h, const char* who, const int32_t* off
     if (h->cn) return fail(EZDIT_E_UNSUPPORTED, "a canvas with a ControlNet attached");
     if (h->tl.on) return fail(EZDIT_E_UNSUPPORTED, "a canvas with context weights (ezdit_set_context_weights): a window has one prompt");
     if (h->cw.on) return fail(EZDIT_E_UNSUPPORTED, "a canvas with composed guidance (ezdit_sampler_begin_composed)");
+    if (h->apg.on) return fail(EZDIT_E_UNSUPPORTED, "a canvas with projected guidance (ezdit_sampler_set_apg): the momentum is not blended across windows");
     if (int rc = upload_table(h->canvas, std::vector<int>(offsets, offsets + P), st)) return rc;
     h->canvas.set(h, true, T != h->canvas_T || ramp != h->canvas_ramp || loop != h->canvas_loop);   // (T and the ramp are kernel arguments; the other form is another kernel)
     h->canvas_T = T; h->canvas_ramp = ramp; h->canvas_loop = loop;

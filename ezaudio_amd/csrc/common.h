@@ -407,10 +407,19 @@ struct CfgDdimArgs {   // (the defaults are the stand-alone operator with everyt
     // ascending, v = u + guidance_scale d; everything behind v is the body it has always been, the rescale reference is c_0.  A weight of exactly 0: row k P + p is
     // not read; guidance_scale <= 0: only c_0 is.  Read at run time: one captured step serves every set of weights.  At the END of the struct: the offsets above stay
     int K = 1; const float* cw = nullptr;
+    // adaptive projected guidance (null apg = off: the kernels they have always been; launch_cfg_apg).  On: apg fp32 (device) holds (eta_apg, norm_threshold, momentum,
+    // on) of sample p at apg[p * apg_stride ..], apg_m fp32 [P][n] the guidance direction of the step before.  A sample with guidance and on != 0 takes the APG update
+    // (k_cfg_stats writes S(d^2), S(d x0c), S(x0c^2) into its partial sums, k_cfg_apply forms the cap and the projection from them) and no rescale;
+    // apg_m = d on its valid frames, 0 on its padded ones.  Any other sample takes the body it has always taken and its rows of apg_m are neither read nor written.
+    // The momentum is not applied (apg_m not read) at the sample's own first step: device step 0, or start[p]; the stand-alone operator (null cur_step) applies the
+    // value it is given.  sp_c_stride: floats between the rows of sp_c, read by the APG instantiations only (the stand-alone operator's rows are 12 wide).  At the END
+    // of the struct: the offsets above stay
+    float* apg_m = nullptr; const float* apg = nullptr; int apg_stride = 4, sp_c_stride = 8;
 };
 constexpr int CFG_KMAX = 8;   // conditions per sample of composed guidance: 1 <= CfgDdimArgs.K <= CFG_KMAX (the weights of a sample ride in registers)
 void launch_cfg_ddim(const CfgDdimArgs& a, float* partial /* [P][64][4] scratch */, hipStream_t st);
 int launch_cfg_compose(const CfgDdimArgs& a, float* partial /* [P][64][4] scratch */, hipStream_t st);   // the composed form (a.cw given); non-zero = refused, nothing launched
+int launch_cfg_apg(const CfgDdimArgs& a, float* partial /* [P][64][4] scratch */, hipStream_t st);       // the APG form (a.apg and a.apg_m given, no a.cw): always both kernels; non-zero = refused
 void launch_set_int(int* p, int v, int add, hipStream_t st);  // *p = add ? *p + v : v
 struct AddNoiseArgs {  // latents[p][i] = sa_p * ((clean[p][i] + shift) * scale) + sb_p * latents[p][i]: a clean VAE latent noised to sample p's start step
     const float* clean;   // [P][n] in VAE space (before scale_shift); row p is not read when params[p] is exactly (0, 1)

@@ -495,13 +495,64 @@ __device__ __forceinline__ float compose_dir(const CfgDdimArgs& a, const float (
     return d;
 }
 
-template <bool ST, bool CP>
+//   AP (CfgDdimArgs.apg given): adaptive projected guidance, on the data prediction.  For a sample with guidance and `on` in its table row
+//                 x0c = sa x - sb c;  d = sb (u - c) + beta m;  m <- d;  s = min(1, r / |d|);  U = s d - (1 - eta) s <d, x0c> / |x0c|^2 x0c;
+//                 x0 = x0c + (w - 1) U;  v = c - (w - 1) U / sb;  everything behind x0 and v is the body it has always been, without the rescale.
+//                 k_cfg_stats writes the sample's S(d^2), S(d x0c), S(x0c^2) where the rescale sums go (same chunking, the valid frames only); k_cfg_apply
+//                 reduces them in double in the fixed order and forms s and the projection coefficient in double, workgroup-uniform.  beta is 0 at the sample's
+//                 own first step (m is not read there).  Every other sample of the call takes the branches it has always taken and never touches m.
+//                 AP = false is the source as it was.
+struct ApgRow { bool on; float eta, r, beta; };
+template <bool ST>
+__device__ __forceinline__ ApgRow apg_row(const CfgDdimArgs& a, int p, int step, float gs) {
+    const float* q = a.apg + (long)p * a.apg_stride;
+    bool first = false;   // (the stand-alone operator is handed beta_eff itself)
+    if (a.cur_step) { if constexpr (ST) first = step == a.start[p]; else first = step == 0; }
+    return {gs > 0.f && q[3] != 0.f, q[0], q[1], first ? 0.f : q[2]};
+}
+// the (sa, sb, ...) row of sample p at this step, as k_cfg_apply selects it, with the row width of the APG forms
+__device__ __forceinline__ const float* apg_coef_row(const CfgDdimArgs& a, int p, int step) {
+    return a.sp_g ? a.sp_c + ((long)step * a.P + p) * a.sp_c_stride : a.cur_step ? a.coef + step * 8 : a.hc;
+}
+
+template <bool ST, bool CP, bool AP = false>
 __global__ __launch_bounds__(256) void k_cfg_stats(CfgDdimArgs a, float* partial) {
     __shared__ float red[4];
     const int p = blockIdx.y, blk = blockIdx.x;
     const int n = a.n;
     if constexpr (ST) {   // held sample (workgroup-uniform): k_cfg_apply does not read its partial sums
         if ((a.cur_step ? *a.cur_step : 0) < a.start[p]) return;
+    }
+    if constexpr (AP) {   // (workgroup-uniform: the row belongs to the sample)
+        const int step = a.cur_step ? *a.cur_step : 0;
+        const ApgRow q = apg_row<ST>(a, p, step, a.sp_g ? a.sp_g[(long)p * a.sp_g_stride] : a.guidance_scale);
+        if (q.on) {
+            const float* cf = apg_coef_row(a, p, step);
+            const float sa = cf[0], sb = cf[1];
+            const float* pc = a.pred + (long)p * n;
+            const float* pu = a.pred + (long)(a.P + p) * n;
+            const float* x = a.latents + (long)p * n;
+            const float* m = a.apg_m + (long)p * n;
+            const int len = a.lens ? a.lens[p] : 0;
+            float dd = 0.f, dc = 0.f, cc = 0.f;
+            for (int i = blk * 256 + threadIdx.x; i < n; i += CFG_NB * 256) {
+                if (a.lens && i % a.L >= len) continue;   // padded frame: not part of the sample
+                const float c = pc[i];
+                const float x0c = sa * x[i] - sb * c;
+                float d = sb * (pu[i] - c);
+                if (q.beta != 0.f) d += q.beta * m[i];
+                dd += d * d; dc += d * x0c; cc += x0c * x0c;
+            }
+            // (a workgroup without a valid element arrives here with zeros and writes them: k_cfg_apply adds up all CFG_NB slots)
+            dd = block_sum4(dd, red); dc = block_sum4(dc, red); cc = block_sum4(cc, red);
+            if (threadIdx.x == 0) {
+                float* o = partial + ((long)p * CFG_NB + blk) * 4;
+                o[0] = dd; o[1] = dc; o[2] = cc; o[3] = 0.f;
+            }
+            return;
+        }
+        // this launch is unconditional: without the sample table the rescale sums are wanted only where launch_cfg_ddim would have launched them
+        if (!a.sp_g && !(a.guidance_scale > 0.f && a.guidance_rescale > 0.f)) return;
     }
     const float* pc = a.pred + (long)p * n;
     const float* pu = a.pred + (long)(a.P + p) * n;
@@ -531,7 +582,7 @@ __global__ __launch_bounds__(256) void k_cfg_stats(CfgDdimArgs a, float* partial
     }
 }
 
-template <bool MS, bool ST, bool CP>
+template <bool MS, bool ST, bool CP, bool AP = false>
 __global__ __launch_bounds__(256) void k_cfg_apply(CfgDdimArgs a, const float* partial) {
     const int p = blockIdx.y, blk = blockIdx.x;
     const int n = a.n;
@@ -542,13 +593,17 @@ __global__ __launch_bounds__(256) void k_cfg_apply(CfgDdimArgs a, const float* p
     if constexpr (ST) { const int s0 = a.start[p]; held = step < s0; first = step == s0; }
     // the seven settings of this sample: the call's scalars, or its row of the per-sample table (one arithmetic body below either way)
     const float* cf = a.sp_g ? a.sp_c + ((long)step * a.P + p) * 8 : a.cur_step ? a.coef + step * 8 : a.hc;
+    if constexpr (AP) cf = apg_coef_row(a, p, step);   // (the same row; the stand-alone APG operator's rows are wider)
     const float sa = cf[0], sb = cf[1], cx0 = cf[2], cdir = cf[3], sigma = cf[4];
     const float gs = a.sp_g ? a.sp_g[(long)p * a.sp_g_stride] : a.guidance_scale;
     const float phi = a.sp_g ? a.sp_g[(long)p * a.sp_g_stride + 1] : a.guidance_rescale;
     const bool cfg = gs > 0.f;
+    ApgRow aq{false, 0.f, 0.f, 0.f};   // APG sample (workgroup-uniform): no rescale, the element body of its own below.  Constant off without AP
+    bool apg_on = false;
+    if constexpr (AP) { aq = apg_row<ST>(a, p, step, gs); apg_on = aq.on && !held; }
     const bool rescale = cfg && phi > 0.f && !held;
     float ratio = 1.f;
-    if (rescale) {   // wave-uniform
+    if (AP ? rescale && !apg_on : rescale) {   // wave-uniform
         // the CFG_NB partial sums of this sample: one 16-byte load per thread into LDS, then every thread adds them up in the SAME order as before
         // (broadcast LDS reads).  The former loop of CFG_NB dependent scalar loads was 10 of the kernel's 12.5 us.
         __shared__ float4 part_l[CFG_NB];
@@ -565,6 +620,27 @@ __global__ __launch_bounds__(256) void k_cfg_apply(CfgDdimArgs a, const float* p
         const double v1 = (q1 - s1 * s1 / nv) / (nv - 1);  // torch.std default: unbiased
         const double v2 = (q2 - s2 * s2 / nv) / (nv - 1);
         ratio = (float)(sqrt(v1) / sqrt(v2));
+    }
+    float ap_s = 1.f, ap_k = 0.f, ap_g = 0.f, ap_gsb = 0.f;
+    float* mom = nullptr;
+    if constexpr (AP) {
+        if (apg_on) {   // the sample's three sums, added up in double in the fixed order as the rescale sums are; the cap s and the projection coefficient in double
+            __shared__ float4 apg_l[CFG_NB];
+            if (threadIdx.x < CFG_NB) apg_l[threadIdx.x] = reinterpret_cast<const float4*>(partial)[(long)p * CFG_NB + threadIdx.x];
+            __syncthreads();
+            double dd = 0, dc = 0, cc = 0;
+#pragma unroll 8
+            for (int i = 0; i < CFG_NB; ++i) {
+                const float4 o = apg_l[i];
+                dd += o.x; dc += o.y; cc += o.z;
+            }
+            const double s = (aq.r > 0.f && dd > 0) ? fmin(1.0, (double)aq.r / sqrt(dd)) : 1.0;
+            ap_s = (float)s;
+            ap_k = cc > 0 ? (float)((1.0 - (double)aq.eta) * s * dc / cc) : 0.f;
+            ap_g = gs - 1.f;
+            ap_gsb = sb != 0.f ? ap_g / sb : 0.f;   // (sb == 0: d is 0 and so is U; v stays c)
+            mom = a.apg_m + (long)p * n;
+        }
     }
     const float* pc = a.pred + (long)p * n;
     const float* pu = cfg ? a.pred + (long)(a.P + p) * n : nullptr;
@@ -583,6 +659,7 @@ __global__ __launch_bounds__(256) void k_cfg_apply(CfgDdimArgs a, const float* p
     if constexpr (MS) {
         ch = (a.cur_step ? a.coef + step * 8 : a.sp_g ? a.sp_c + (long)p * 8 : a.hc)[5];
         hist = a.x0_hist + (long)p * n;
+        if constexpr (AP) { if (!a.cur_step && a.sp_g) ch = a.sp_c[(long)p * a.sp_c_stride + 5]; }
         if (first) ch = 0.f;   // the sample's own step 0: first-order, the history is not its
     }
     if (!held)   // (the loop keeps its indentation: a held sample skips it whole and goes on to the arrival counter)
@@ -590,9 +667,31 @@ __global__ __launch_bounds__(256) void k_cfg_apply(CfgDdimArgs a, const float* p
         if (a.lens && i % a.L >= len) {   // padded frame: zero, whatever pred / noise / the latents hold there
             lat[i] = 0.f;
             if constexpr (MS) hist[i] = 0.f;
+            if constexpr (AP) { if (apg_on) mom[i] = 0.f; }
             continue;
         }
         float v = pc[i];
+        if constexpr (AP) {
+            if (apg_on) {
+                const float c = v, x = lat[i];
+                const float x0c = sa * x - sb * c;
+                float d = sb * (pu[i] - c);
+                if (aq.beta != 0.f) d += aq.beta * mom[i];
+                mom[i] = d;   // before the cap
+                const float U = ap_s * d - ap_k * x0c;
+                const float x0 = x0c + ap_g * U;
+                v = c - ap_gsb * U;
+                const float eps = sa * v + sb * x;
+                float prev = cx0 * x0 + cdir * eps;
+                if (z) prev += sigma * z[i];
+                if constexpr (MS) {
+                    if (ch != 0.f) prev += ch * (x0 - hist[i]);
+                    hist[i] = x0;
+                }
+                lat[i] = prev;
+                continue;
+            }
+        }
         if (cfg) {
             const float u = pu[i];
             if constexpr (CP) v = u + gs * compose_dir(a, cw, v, u, p, i);
@@ -844,6 +943,23 @@ int launch_cfg_compose(const CfgDdimArgs& a, float* partial, hipStream_t st) {
         else hipLaunchKernelGGL((k_cfg_apply<false, true, true>), grid, dim3(256), 0, st, a, partial);
     } else if (a.x0_hist) hipLaunchKernelGGL((k_cfg_apply<true, false, true>), grid, dim3(256), 0, st, a, partial);
     else hipLaunchKernelGGL((k_cfg_apply<false, false, true>), grid, dim3(256), 0, st, a, partial);
+    return 0;
+}
+
+// adaptive projected guidance (CfgDdimArgs.apg): the AP instantiations, a launcher of their own -- launch_cfg_ddim is what it was.  Always both kernels: which
+// samples take APG, and which of the others rescale, are run-time values.  Non-zero: nothing launched
+int launch_cfg_apg(const CfgDdimArgs& a, float* partial, hipStream_t st) {
+    if (!a.apg || !a.apg_m || !partial || a.cw || a.K != 1) return 1;
+    const dim3 grid(CFG_NB, a.P);
+    if (a.start) {
+        hipLaunchKernelGGL((k_cfg_stats<true, false, true>), grid, dim3(256), 0, st, a, partial);
+        if (a.x0_hist) hipLaunchKernelGGL((k_cfg_apply<true, true, false, true>), grid, dim3(256), 0, st, a, partial);
+        else hipLaunchKernelGGL((k_cfg_apply<false, true, false, true>), grid, dim3(256), 0, st, a, partial);
+    } else {
+        hipLaunchKernelGGL((k_cfg_stats<false, false, true>), grid, dim3(256), 0, st, a, partial);
+        if (a.x0_hist) hipLaunchKernelGGL((k_cfg_apply<true, false, false, true>), grid, dim3(256), 0, st, a, partial);
+        else hipLaunchKernelGGL((k_cfg_apply<false, false, false, true>), grid, dim3(256), 0, st, a, partial);
+    }
     return 0;
 }
 

@@ -41,6 +41,16 @@ def shard_range(n_items, rank, world):
     return start, start + base + (1 if rank < rem else 0)
 
 
+def slice_per_prompt(value, start, end, n_prompts):
+    """A per-prompt setting of a sharded call for the prompts [start, end): a list or tuple with one entry per prompt is sliced, one value for the call goes to
+    every shard as it is (what the entries of `apg` need: dicts and None are values, not sequences)."""
+    if isinstance(value, (list, tuple)):
+        if len(value) != n_prompts:
+            raise ValueError(f'{len(value)} per-prompt entries for {n_prompts} prompts')
+        return list(value[start:end])
+    return value
+
+
 def gather_samples(local, n_total, group=None):
     """local: [n_local, ...] on this rank (contiguous shard per shard_range) -> [n_total, ...] on every rank."""
     if not dist.is_initialized() or dist.get_world_size(group) == 1:

@@ -7,6 +7,7 @@ Beyond the reference: ``P`` independent prompts per call (the reference hard-cod
 src/inference.py:67); each prompt's cond/uncond pair stays on one GPU.
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -44,6 +45,54 @@ def _collapse(value, n_prompts, name):
     if len(set(vals)) == 1:
         return vals[0], None
     return None, vals
+
+
+APG_DEFAULTS = dict(eta=0.0, norm_threshold=0.0, momentum=-0.5)   # what apg=True means: no parallel part, momentum -0.5, NO norm cap (which cap suits the EzAudio latent is unmeasured)
+
+
+def apg_entries(apg, n_prompts):
+    """``apg`` of prepare() / inference() / generate_audio() as a list of n_prompts rows (eta_apg, norm_threshold, momentum, on), or None when nobody asks for
+    it (the plain call).  ``apg`` is True or a dict with keys among eta, norm_threshold, momentum (APG_DEFAULTS fill the rest) -- for every prompt -- or a list
+    with one such entry, or None / False, per prompt.  ValueError: a list of another size, an unknown key, a non-finite value, a negative norm_threshold."""
+    if apg is None or apg is False:
+        return None
+    entries = list(apg) if isinstance(apg, (list, tuple)) else [apg] * n_prompts
+    if len(entries) != n_prompts:
+        raise ValueError(f'apg: True, a dict, or one entry (or None) per prompt; got {len(entries)} entries for {n_prompts} prompts')
+    rows = []
+    for i, e in enumerate(entries):
+        if e is None or e is False:
+            rows.append((0.0, 0.0, 0.0, 0))
+            continue
+        if e is True:
+            e = {}
+        if not isinstance(e, dict) or set(e) - set(APG_DEFAULTS):
+            raise ValueError(f'apg of prompt {i}: expected True or a dict with keys among {sorted(APG_DEFAULTS)}, got {e!r}')
+        v = {k: float(e.get(k, d)) for k, d in APG_DEFAULTS.items()}
+        if not all(math.isfinite(x) for x in v.values()):
+            raise ValueError(f'apg of prompt {i}: {e!r} is not finite')
+        if v['norm_threshold'] < 0:
+            raise ValueError(f'apg of prompt {i}: norm_threshold {v["norm_threshold"]} is negative (0 = no cap)')
+        rows.append((v['eta'], v['norm_threshold'], v['momentum'], 1))
+    return rows if any(r[3] for r in rows) else None
+
+
+def check_apg(rows, guidance_scale, guidance_rescale, compose=False, canvas=False):
+    """What APG does not combine with, on the host: ``rows`` of apg_entries(), the guidance settings as scalars or per-prompt lists."""
+    if rows is None:
+        return
+    if compose:
+        raise ValueError('apg does not combine with composed guidance (compose)')
+    if canvas:
+        raise ValueError('apg does not combine with a canvas or a loop: the momentum is not blended across windows')
+    n = len(rows)
+    per = lambda v, k: [float(x or 0.0) for x in (_per_prompt(v, n, k) or [v] * n)]   # noqa: E731
+    gs, gr = per(guidance_scale, 'guidance_scale'), per(guidance_rescale, 'guidance_rescale')
+    for i, r in enumerate(rows):
+        if r[3] and not gs[i] > 0:
+            raise ValueError(f'apg of prompt {i} without guidance: projected guidance needs a guidance_scale above 0')
+        if r[3] and gr[i] > 0:
+            raise ValueError(f'apg of prompt {i} with guidance_rescale {gr[i]}: the rescale is not applied to projected guidance, ask for one of the two')
 
 
 TIMELINE_SEG = 128     # context rows of one prompt of a timeline: one key tile of the cross-attention kernel (csrc/attn.hip TL)
@@ -131,7 +180,7 @@ class LatentSampler:
     def prepare(self, text, text_mask, uncond_text, uncond_mask, init_noise, step_noises, guidance_scale,
                 guidance_rescale, ddim_steps, eta, gt=None, gt_mask=None, controlnet=None, condition=None,
                 conditioning_scale=1.0, lengths=None, init_latents=None, start_steps=None, latent_scale=1.0, latent_shift=0.0, context_weights=None, compose_text=None, compose_mask=None,
-                compose_weights=None, token_weights=None, uncond_token_weights=None, compose_token_weights=None, canvas=None, canvas_loop=None, solver='ddim'):
+                compose_weights=None, token_weights=None, uncond_token_weights=None, compose_token_weights=None, apg=None, canvas=None, canvas_loop=None, solver='ddim'):
         """``lengths`` (list of P ints): init_noise / step_noises / gt / gt_mask are padded to L = max(lengths) frames and sample p is valid on
         [0, lengths[p]) -- its final latent is what a call with that sample alone at its own length gives, zero beyond (include/ezdit.h
         ezdit_set_lengths).  With a ControlNet the table goes to the attached pair (ezdit_sampler_set_pair_lengths) and ``condition`` is
@@ -183,8 +232,17 @@ class LatentSampler:
         block's cross-attention, as if it stood there that many times (parse_emphasis() / emphasis_weights() make such weights from '(words:1.6)' markup).
         ``uncond_token_weights`` [P, Lt] does the same for the unconditional rows (default: 1) and ``compose_token_weights`` [P, K-1, Lt] for the extra conditions of
         ``compose_text``.  The [B, Lc] table is built here in the layout of the batch; values at masked tokens are not read.  It combines with composed guidance, a canvas
-        or loop, lengths, init_latents and ``solver``; not with a ControlNet or a timeline.  Weights that are equal within every row call nothing new: the same bits."""
+        or loop, lengths, init_latents and ``solver``; not with a ControlNet or a timeline.  Weights that are equal within every row call nothing new: the same bits.
+
+        ``apg`` (adaptive projected guidance, include/ezdit.h ezdit_sampler_set_apg): True, a dict(eta=, norm_threshold=, momentum=) or a list with one such
+        entry (or None) per sample (apg_entries()).  A sample with an entry is guided on its data prediction -- the guidance direction keeps a momentum across
+        steps, is capped at norm_threshold (0: no cap) and loses its part parallel to the conditional prediction (eta: the share that stays) -- in place of
+        v = u + w (c - u); the others are guided as always.  The momentum buffer is allocated here and lives on the sampler, next to the multistep history;
+        set_apg() replaces the values of a prepared call without a re-capture.  It combines with lengths, per-sample settings, ``solver``, step noise,
+        init_latents, gt / gt_mask, a ControlNet, a timeline and token weights; not with composed guidance, a canvas or a loop, and a sample that asks for it
+        needs guidance and no guidance_rescale.  Nobody asking calls nothing new: the same bits."""
         check_solver(solver, eta)
+        apg = apg_entries(apg, init_noise.shape[0])
         if token_weights is not None or uncond_token_weights is not None or compose_token_weights is not None:
             if controlnet is not None or context_weights is not None:
                 raise ValueError('token weights do not combine with a ControlNet or a prompt timeline')
@@ -211,6 +269,7 @@ class LatentSampler:
                 if controlnet is not None or canvas is not None or canvas_loop is not None or context_weights is not None:
                     raise ValueError('composed guidance does not combine with a ControlNet, a canvas, a loop or a prompt timeline')
                 compose = cw.contiguous()
+        check_apg(apg, guidance_scale, guidance_rescale, compose=compose is not None, canvas=canvas is not None or canvas_loop is not None)
         if context_weights is not None:
             if canvas is not None or canvas_loop is not None or controlnet is not None:
                 raise ValueError('a prompt timeline does not combine with a canvas, a loop or a ControlNet')
@@ -387,6 +446,7 @@ class LatentSampler:
         self.n_steps = ddim_steps
         self.P = P
         self.x0_hist = None
+        self.apg_m = None
         self.first_step = 0
         if starts is not None:
             with torch.cuda.stream(self.stream):
@@ -412,6 +472,25 @@ class LatentSampler:
             self.x0_hist = torch.zeros_like(self.latents)
             ch = self.scheduler.multistep_coefficients()
             self._table_call(u.lib.ezdit_sampler_set_multistep, (C.c_float * ddim_steps)(*ch), ddim_steps, _ptr(self.x0_hist))
+        if apg is not None:   # after the sample table (a sample's guidance comes from it) and the multistep setter
+            self._set_apg_rows(apg)
+
+    def set_apg(self, apg=None):
+        """Adaptive projected guidance of the call prepare() began: what prepare(apg=) takes -- True, a dict, or one entry (or None) per sample -- or no
+        argument to switch it off (classifier-free guidance again, the plain call's bits).  The captured step reads the table at run time: new values need no
+        re-capture.  The momentum buffer is the sampler's and is kept across calls of this method; a run that is rewound starts without momentum anyway."""
+        self._set_apg_rows(apg_entries(apg, self.P))
+
+    def _set_apg_rows(self, rows):
+        setter = self.unet.lib.ezdit_sampler_set_apg
+        if rows is None:
+            self._table_call(setter, None, None, None, None, 0, None)
+            return
+        if self.apg_m is None:
+            self.apg_m = torch.zeros_like(self.latents)
+        P = self.P
+        cols = [(C.c_float * P)(*[r[k] for r in rows]) for k in range(3)]
+        self._table_call(setter, *cols, (C.c_int32 * P)(*[r[3] for r in rows]), P, _ptr(self.apg_m))
 
     def _table_call(self, setter, *args, ok=()):
         """One call of a table setter of the library (include/ezdit.h, "Run-time tables of the step") for this sampler's handle, on the sampler stream.  Its
@@ -892,9 +971,18 @@ def inference_controlnet(autoencoder, unet, controlnet, gt, gt_mask, condition, 
 def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, noise_scheduler, text_raw,
               neg_text=None, audio_frames=500, guidance_scale=3, guidance_rescale=0.0, ddim_steps=50, eta=1,
               random_seed=2024, device='cuda', use_graph=True, controlnet=None, condition=None, conditioning_scale=1.0,
-              first_index=None, init_latents=None, strength=None, attention_window=None, prompt_weights=None, compose=None, emphasis=False, token_weights=None, canvas_loop=None, decode_context=None, canvas_offsets=None, canvas_ramp=None,
+              first_index=None, init_latents=None, strength=None, attention_window=None, prompt_weights=None, compose=None, emphasis=False, token_weights=None, apg=None, canvas_loop=None, decode_context=None, canvas_offsets=None, canvas_ramp=None,
               solver='ddim'):
     """Same signature and semantics as the reference's ``inference`` (src/inference.py:26-107).
+
+    Extension (adaptive projected guidance, Sadat et al.): ``apg`` is True, a dict(eta=, norm_threshold=, momentum=) or a list with one such entry (or None) per
+    prompt (apg_entries()): a prompt with an entry is guided on its data prediction -- the guidance direction carries a (negative) momentum across steps, is capped
+    at norm_threshold and loses its component parallel to the conditional prediction (eta: the share of it that stays) -- which is what keeps a high guidance_scale
+    from over-driving the latent; the other prompts are guided as always.  True means eta 0, momentum -0.5 and NO cap: which norm_threshold suits the EzAudio latent
+    is unmeasured, so none is invented.  It combines with ``audio_frames`` lists, per-prompt settings, ``solver``, gt / gt_mask, ``init_latents``, a ControlNet, a
+    timeline, emphasis and ``attention_window``, and is sliced with the prompts on a call sharded over ranks; ValueError with ``compose``, a canvas or loop, for a
+    prompt that asks for it without guidance or together with a guidance_rescale above 0 (the rescale is not applied to projected guidance).  No entry for any
+    prompt is the plain call, bit for bit.  Audio quality on the real checkpoints -- which cap, eta and momentum sound best -- is unmeasured.
 
     Extension (prompt emphasis): ``emphasis=True`` parses '(words:1.6)' markup (parse_emphasis) in every prompt of the call -- ``text_raw``, the extra prompts of
     ``compose`` and ``neg_text`` -- the text encoder sees the clean text, and token j of a prompt weighs its group's weight in every block's cross-attention
@@ -968,7 +1056,7 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
             return inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, noise_scheduler, text_raw, neg_text, audio_frames, guidance_scale,
                              guidance_rescale, ddim_steps, eta, random_seed, device, use_graph, controlnet, condition, conditioning_scale, first_index=first_index,
                              init_latents=init_latents, strength=strength, canvas_loop=canvas_loop, decode_context=decode_context, canvas_offsets=canvas_offsets,
-                             canvas_ramp=canvas_ramp, solver=solver, prompt_weights=prompt_weights, compose=compose, emphasis=emphasis, token_weights=token_weights)
+                             canvas_ramp=canvas_ramp, solver=solver, prompt_weights=prompt_weights, compose=compose, emphasis=emphasis, token_weights=token_weights, apg=apg)
         finally:
             for m, prev in zip(models, previous):
                 m.set_attention_window(prev)
@@ -1014,6 +1102,10 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
                     ('conditioning_scale', conditioning_scale), ('strength', strength)):
         _per_prompt(v, len(text_raw), name)   # a list has one entry per prompt
     check_solver(solver, eta)
+    # one entry per prompt of the call (an entry of a timeline is one prompt here), in the form prepare() takes; None when nobody asks
+    apg_rows = apg_entries(apg, len(text_raw))
+    check_apg(apg_rows, guidance_scale, guidance_rescale, canvas=canvas_offsets is not None)
+    apg = None if apg_rows is None else [dict(eta=r[0], norm_threshold=r[1], momentum=r[2]) if r[3] else None for r in apg_rows]
     import torch.distributed as dist
     frames = _frames_list(audio_frames, len(text_raw))
     timeline = None
@@ -1032,13 +1124,14 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
             raise ValueError('composed guidance is not sharded over ranks: call it with one rank\'s prompts')
         lists, cw = compose_entries(compose, len(text_raw))
         if lists is not None:
+            check_apg(apg_rows, guidance_scale, guidance_rescale, compose=True)
             composed = (len(text_raw), cw)
             # every prompt of the call in ONE text-encoder batch: the primaries, then extra condition k of every prompt (a missing one: the prompt's own text, weight 0)
             text_raw = list(text_raw) + [lists[i][k][0] if k < len(lists[i]) else text_raw[i] for k in range(cw.shape[1] - 1) for i in range(len(text_raw))]
     if controlnet is not None:
         condition = pad_conditions(condition, frames if frames is not None else audio_frames, len(text_raw))
     if canvas_offsets is None and composed is None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and len(text_raw) > 1 and first_index is None:
-        from .dist import sample_sharded
+        from .dist import sample_sharded, slice_per_prompt
         n_all = len(text_raw)
         ratio_ = params['autoencoder']['sr'] // params['autoencoder']['latent_sr']
         t_all = (max(frames) if frames is not None else audio_frames) * ratio_   # every shard is gathered at the GLOBAL duration
@@ -1057,7 +1150,7 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
                             list(text_raw[s:e]), neg_all[s:e], audio_frames if frames is None else frames[s:e], pp(guidance_scale), pp(guidance_rescale),
                             ddim_steps, pp(eta), pp(random_seed), device, use_graph, controlnet, cut(condition, 2), pp(conditioning_scale), first_index=s,
                             solver=solver, init_latents=cut(init_latents), strength=pp(strength), emphasis=emphasis,
-                            token_weights=None if token_weights is None else torch.as_tensor(token_weights)[s:e])
+                            token_weights=None if token_weights is None else torch.as_tensor(token_weights)[s:e], apg=slice_per_prompt(apg, s, e, n_all))
             if frames is None:
                 return wav
             out = torch.zeros(wav.shape[0], wav.shape[1], t_all, dtype=wav.dtype, device=wav.device)
@@ -1143,6 +1236,8 @@ def inference(autoencoder, unet, gt, gt_mask, tokenizer, text_encoder, params, n
             kw['uncond_token_weights'] = w_neg.expand(n_primary, -1) if w_neg.shape[0] == 1 else w_neg
     if composed is not None:
         kw.update(compose_text=comp_text.float(), compose_mask=comp_mask, compose_weights=composed[1])
+    if apg is not None:
+        kw['apg'] = apg
     if canvas_loop is not None:
         kw['canvas_loop'] = (canvas_offsets, canvas_loop, canvas_ramp)
     elif long_form:

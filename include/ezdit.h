@@ -11,11 +11,11 @@
  *     allocates or frees persistent device memory.  Weights live in one caller-owned blob laid out
  *     by ezdit_param_info(); all activations / tables live in one caller-owned workspace.
  *   - the PER-STEP entry points (ezdit_forward, ezdit_controlnet_forward, ezdit_sampler_run, ezdit_set_step,
- *     ezdit_cfg_ddim_step, ezdit_cfg_ddim_step_per_sample, ezdit_cfg_multistep_step, ezdit_add_noise, ezdit_canvas_blend, ezdit_canvas_blend_loop, the ezvae_* ops) are ASYNCHRONOUS on their stream: no device sync, no host read of
+ *     ezdit_cfg_ddim_step, ezdit_cfg_ddim_step_per_sample, ezdit_cfg_multistep_step, ezdit_cfg_apg_step, ezdit_add_noise, ezdit_canvas_blend, ezdit_canvas_blend_loop, the ezvae_* ops) are ASYNCHRONOUS on their stream: no device sync, no host read of
  *     device data (a sampler step is hipGraph-capturable).  The once-per-call SET-UP entry points synchronise the
  *     stream and must not be called inside a stream capture: ezdit_bind_workspace (diagnostic builds only),
  *     ezdit_prepare_context (reads the context mask back to find single-key batch elements when `xkey1` is on),
- *     ezdit_prepare_timesteps, ezdit_sampler_begin, ezdit_sampler_set_sample_params, ezdit_sampler_set_multistep, ezdit_sampler_set_start, ezdit_sampler_set_canvas and ezdit_sampler_set_canvas_loop (host staging
+ *     ezdit_prepare_timesteps, ezdit_sampler_begin, ezdit_sampler_set_sample_params, ezdit_sampler_set_multistep, ezdit_sampler_set_start, ezdit_sampler_set_apg, ezdit_sampler_set_canvas and ezdit_sampler_set_canvas_loop (host staging
  *     buffers of the timestep / coefficient tables), ezdit_set_lengths, ezdit_sampler_set_pair_lengths and ezdit_sampler_set_cn_scales
  *     (host mirrors of the length / scale tables), ezdit_set_context_weights (host mirror of the prompt timeline; reads the context mask back).
  *   - return 0 = OK, negative = error; ezdit_last_error() gives a thread-local message.  No C++
@@ -144,7 +144,9 @@ int    ezdit_bind_workspace(ezdit_handle* h, void* dev_ws, size_t bytes, int B, 
  *       compose weights (.._begin_composed         off <-> on, another K: only a      ezdit_bind_workspace, ezdit_sampler_begin,
  *         switches it on, .._set_compose_weights     begin does either                  ezdit_sampler_begin_composed (which sets its own)
  *         replaces the values)
- * ezdit_bind_workspace ends the sampler call as well: ezdit_sampler_run and the call-scoped setters (the last five) return EZDIT_E_STATE
+ *       projected guidance (.._set_apg)           off <-> on, another momentum buffer ezdit_bind_workspace, ezdit_sampler_begin,
+ *                                                                                       ezdit_sampler_begin_composed
+ * ezdit_bind_workspace ends the sampler call as well: ezdit_sampler_run and the call-scoped setters (the last six) return EZDIT_E_STATE
  * until the next ezdit_sampler_begin, whatever shape was bound. */
 
 /* ---- step-invariant work, hoisted (reference recomputes it every step) ----------------------- */
@@ -361,6 +363,43 @@ int ezdit_sampler_set_compose_weights(ezdit_handle* h, const float* weights, int
  * [1, EZDIT_COMPOSE_MAX]; P < 1, n < 2; L not dividing n with dev_lens; noise together with a history. */
 int ezdit_cfg_compose_step(const float* dev_pred, float* dev_latents, const float* dev_noise, float* dev_x0_hist, const float* dev_params,
                            const float* dev_weights, int K, const int32_t* dev_lens, int L, int P, int n, float* dev_scratch, ezdit_stream stream);
+
+/* ---- adaptive projected guidance (APG) in the fused step ------------------------------------------------------------------------- */
+/* Sadat et al., "Eliminating Oversaturation and Artifacts of High Guidance Scales in Diffusion Models": guidance on the DATA prediction with a capped norm, a
+ * momentum across steps and the component parallel to the conditional prediction removed (or scaled by eta_apg).  Per sample, over its valid elements only,
+ * with w the sample's guidance_scale (the call's scalar or its row of ezdit_sampler_set_sample_params) and (sa, sb, ...) its ezdit_ddim_coef of the step:
+ *   x0c = sa x - sb c ;  d = sb (u - c) + beta_eff m ;  m <- d   (stored before the cap)
+ *   s = min(1, r / |d|) if r > 0 and |d| > 0, else 1 ;  a = s <d, x0c> / |x0c|^2   (0 when |x0c|^2 = 0)
+ *   U = s d - (1 - eta_apg) a x0c ;  x0 = x0c + (w - 1) U ;  v = c - (w - 1) U / sb ;  eps = sa v + sb x
+ *   x_next = c_x0 x0 + c_dir eps (+ sigma z) (+ c_hist (x0 - x0_hist), x0_hist <- x0 with the multistep solver)
+ * The element-wise arithmetic is fp32; the three sums are 64 chunked fp32 partial sums per sample added up in double, s and a are formed in double.
+ * beta_eff is the sample's momentum, and 0 at the sample's own first step (step 0, or start_steps[p] with a start table): there the momentum buffer is not
+ * read and may hold anything, NaN included.  eta_apg = 1, r = 0, momentum = 0 is plain classifier-free guidance (to rounding).
+ * ezdit_sampler_set_apg takes HOST arrays of P values -- eta_apg, norm_threshold (r; 0 = no cap), momentum, on -- and dev_momentum, a caller-owned fp32
+ * [P][C][L] device buffer that must live as long as the sampler runs: the last kernel of every step rewrites the rows of the APG samples with d (0 on the
+ * padded frames of ezdit_set_lengths).  A sample with on = 0 takes classifier-free guidance and guidance_rescale exactly as without the table; a sample with
+ * guidance_scale <= 0 takes its conditional prediction alone; the momentum rows of either are neither read nor written, nor are those of a sample the start
+ * table holds.  guidance_rescale is NOT applied to an APG sample.
+ * A run-time table of the step (contract above), call-scoped, in a workspace region of its own: ezdit_workspace_bytes grows by 16 B bytes, rounded up to a
+ * multiple of 256.  All four arrays NULL (or P = 0) switches it off: the plain step again, bit for bit.  While it is on both tail kernels of the step are launched
+ * (the plain step at guidance_rescale 0 launches one).  ezdit_set_step(k) follows the multistep rule while it is on: only k = 0, or min(start_steps) with a start
+ * table, else EZDIT_E_STATE (the momentum would not be step k - 1's).
+ * Per-sample lengths, the per-sample settings table, the multistep solver, a start table, step noise, gt / gt_mask, an attached ControlNet, an attention
+ * window, context weights and token weights work unchanged; none of them is touched.
+ * EZDIT_E_UNSUPPORTED: a call begun composed (ezdit_sampler_begin_composed; a begin ends the table, so the other direction cannot arise), a canvas or a ring
+ * that is on -- and the canvas setters refuse likewise while the table is on.  EZDIT_E_INVALID: P is not the sampler's; only some of the arrays, or no
+ * dev_momentum; a non-finite value; norm_threshold < 0; on != 0 on a sampler begun without CFG rows (B = P). */
+int ezdit_sampler_set_apg(ezdit_handle* h, const float* eta_apg, const float* norm_threshold, const float* momentum, const int32_t* on, int P,
+                          float* dev_momentum, ezdit_stream stream);
+
+/* The APG form of ezdit_cfg_ddim_step_per_sample / ezdit_cfg_multistep_step, for callers that keep their own loop: dev_pred fp32 [2 P][n], dev_params fp32
+ * [P][12] ON THE DEVICE = (guidance_scale, guidance_rescale, sa, sb, c_x0, c_dir, sigma, c_hist, eta_apg, norm_threshold, beta_eff, on) -- beta_eff is the
+ * momentum this step applies (the caller passes 0 at a sample's first step; dev_momentum is not read then) --, dev_momentum fp32 [P][n] rewritten as above.
+ * dev_x0_hist NULL: the DDIM form (dev_noise [P][n] of this step, or NULL; c_hist is not applied); given: the multistep form (dev_noise must be NULL).
+ * dev_lens, L, dev_scratch (>= P*256 floats, always needed) as there.  Asynchronous, no handle needed.  EZDIT_E_INVALID: a NULL pointer among pred, latents,
+ * momentum, params, scratch; P < 1, n < 2; L not dividing n with dev_lens; noise together with a history. */
+int ezdit_cfg_apg_step(const float* dev_pred, float* dev_latents, const float* dev_noise, float* dev_x0_hist, float* dev_momentum, const float* dev_params,
+                       const int32_t* dev_lens, int L, int P, int n, float* dev_scratch, ezdit_stream stream);
 
 /* ---- audio-to-audio: start the sampler from a noised clip, per sample ------------------------------------------------------------ */
 /* Noise a clean VAE latent into the model's space at each sample's start step, in place of the init noise:
